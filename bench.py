@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark: NMPC RTI throughput at batch x N = 1024 x 40 per GPU (BASELINE.json config C3/C4).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, the QP's
+iteration counts).  --full adds every other measurement to that line: per-step latency, per-kernel times
+and rooflines, the preparation phase alone, the B = 1, C1, C2, scene and C5 legs and the CPU baselines.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 
 A "step" is one SQP-RTI solve (acados SQP_RTI, sdf_nmpc/ocp.py:110) for every one of the B instances
 on this GPU: the preparation phase over all N+1 shooting nodes (SDF forward + position-Jacobian, ERK4 +
@@ -80,11 +85,47 @@ def lin_bytes_per_instance(N, np_=145):
     return reads + writes
 
 
+# --dump-outputs: the arrays a caller of the timed step receives (the updated iterate and u_0, the QP step and
+# its status, the linearisation the QP was built from), in the order they are written
+DUMP_NAMES = ("x", "u", "u0", "dx", "du", "res", "status", "iters", "xn", "AB", "y", "Jy", "yN", "JyN", "h", "Jh",
+              "sdf", "latent")
+DUMP_ARRAY_BYTES = 3 << 20  # per array: 18 arrays stay under 64 MB in all
+
+
+def dump_outputs(path, tensors, rank=0):
+    """Write the device tensors `tensors` (name -> tensor, first axis = instance) as path/<name>.npy, float32
+    or float64 (integer arrays as float64).  An array above DUMP_ARRAY_BYTES is written as a sample of its
+    instances, drawn with a fixed seed, so two runs with the same arguments write the same rows.  Ranks above
+    0 write under path/rank<r>/."""
+    if rank:
+        path = os.path.join(path, f"rank{rank}")
+    os.makedirs(path, exist_ok=True)
+    for name in DUMP_NAMES:
+        t = tensors.get(name)
+        if t is None:
+            continue
+        nbytes = t.numel() * t.element_size()
+        if nbytes > DUMP_ARRAY_BYTES:
+            k = max(1, DUMP_ARRAY_BYTES // (nbytes // t.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], k, replace=False))
+            t = t[rows.tolist()]
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 50; --config c5: 10)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default: 10; c5: 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline figure (latency, per-kernel times and "
+                         "rooflines, preparation phase alone, B=1 / C1 / C2 / scene / C5 legs, CPU baselines); "
+                         "the --no-* and --prep-steps options select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=1024, help="instances per GPU (weak scaling)")
     ap.add_argument("--global-batch", type=int, default=0,
                     help="if > 0: this many instances in total, split by shard.instance_range (strong scaling)")
@@ -104,6 +145,12 @@ def main():
                     help="c3: the headline 1024 x 40 RTI (default); c5: 4x-wide SDF MLP + in-loop VAE encode, "
                          "N = 60, 4096 instances over 8 GPUs (512 per GPU)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 10 if args.config == "c5" else 50
+    if args.warmup is None:
+        args.warmup = 3 if args.config == "c5" else 10
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config == "c5":
         return main_c5(args)
 
@@ -213,6 +260,35 @@ def main():
     value = total * args.steps / elapsed
     it = bufs["iters"].cpu().numpy()
     st = bufs["status"].cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(bufs, u0=u0), rank)
+
+    out = {
+        "metric": "NMPC solves/sec at batch×N=1024×40 on 1/2/4/8 GPUs; p50 control-step latency",
+        "value": value,
+        "unit": "instance-RTI-solves/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if args.global_batch > 0 else "weak",
+        "vs_baseline": None,
+        "dtype": "f64 (QP, linearisation) + f32 (SDF MLP on MFMA)",
+        "data": "synthetic (seeded x0/latent/waypoints, SIREN-init weights seed 0; real weights are LFS pointers)",
+        "config": {"workload": f"C3/C4: batch={B} instances per GPU x N={N}, one SQP-RTI solve per step "
+                               "(preparation: SDF fwd+d/dpos, ERK4+sens, NLS, h+J_h; feedback: batched Riccati IPM "
+                               "QP to tol 1e-8; iterate update), 'att' model, default flags",
+                   "global_batch": total, "horizon": N, "parallelism": f"instances sharded over {world} GPU(s)",
+                   "tile_rows": args.tile_rows},
+        "qp_iters_mean": float(it.mean()), "qp_iters_max": int(it.max()), "qp_converged_frac": float((st == 0).mean()),
+    }
+    if not args.full:  # the plain run ends here; everything below is a measurement of its own
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # control-step latency: each step synchronised on its own
     lat = []
@@ -385,27 +461,9 @@ def main():
                # x the host's physical cores is the ideal-scaling bound of an all-core run
                "projected_all_cores": (S1 / cpu1_s * host["physical_cores"]) if host.get("physical_cores") else None}
 
-    out = {
-        "metric": "NMPC solves/sec at batch×N=1024×40 on 1/2/4/8 GPUs; p50 control-step latency",
-        "value": value,
-        "unit": "instance-RTI-solves/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if args.global_batch > 0 else "weak",
-        "vs_baseline": None,
-        "dtype": "f64 (QP, linearisation) + f32 (SDF MLP on MFMA)",
-        "data": "synthetic (seeded x0/latent/waypoints, SIREN-init weights seed 0; real weights are LFS pointers)",
-        "config": {"workload": f"C3/C4: batch={B} instances per GPU x N={N}, one SQP-RTI solve per step "
-                               "(preparation: SDF fwd+d/dpos, ERK4+sens, NLS, h+J_h; feedback: batched Riccati IPM "
-                               "QP to tol 1e-8; iterate update), 'att' model, default flags",
-                   "global_batch": total, "horizon": N, "parallelism": f"instances sharded over {world} GPU(s)",
-                   "tile_rows": args.tile_rows},
+    out.update({
         "p50_step_ms": p50,
         "p50_step_ms_b1": lat1,
-        "qp_iters_mean": float(it.mean()), "qp_iters_max": int(it.max()), "qp_converged_frac": float((st == 0).mean()),
         "kernel_ms": kms,
         "roofline": {"bound": "mfma", "kernel": "rti_qp", "achieved": qp_tf, "peak": FP64_PEAK_TFLOPS,
                      "unit": "TFLOP/s", "frac": qp_tf / FP64_PEAK_TFLOPS,
@@ -429,7 +487,7 @@ def main():
         "c1": c1,
         "scene": scene,
         "c5": c5,
-    }
+    })
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
@@ -656,19 +714,19 @@ def main_c5(args):
     if args.global_batch > 0:
         lo, hi = shard.instance_range(args.global_batch, world, rank)
         B = hi - lo
-    steps = args.steps if args.steps != 50 else 10
-    warm = args.warmup if args.warmup != 10 else 3
-    out = c5_leg(local, dev, world, rank, B, N, steps, warm, args.no_cpu_baseline, args.global_batch)
+    out = c5_leg(local, dev, world, rank, B, N, args.steps, args.warmup, args.no_cpu_baseline, args.global_batch,
+                 full=args.full, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
 
 
-def c5_leg(local, dev, world, rank, B, N, steps, warm, no_cpu, global_batch=0):
+def c5_leg(local, dev, world, rank, B, N, steps, warm, no_cpu, global_batch=0, full=True, dump=None):
     """Config C5 on this GPU (main_c5, and the c5 sub-block of the default line): B instances at horizon N,
     per step the VAE encode of B depth images, the latents packed into p on the device, one SQP-RTI solve
-    with the 4x-wide SDF.  Returns the C5 result dict (value over all ranks)."""
+    with the 4x-wide SDF.  Returns the C5 result dict (value over all ranks); full=False stops after the
+    timed steps (no per-kernel times, rooflines or CPU baseline), dump names the --dump-outputs directory."""
     import torch
     import torch.distributed as dist
     from sdf_nmpc_amd import _lib, shard, synth, vae as V, weights as W
@@ -745,6 +803,32 @@ def c5_leg(local, dev, world, rank, B, N, steps, warm, no_cpu, global_batch=0):
     total = global_batch if global_batch > 0 else world * B
     it = bufs["iters"].cpu().numpy()
     st = bufs["status"].cpu().numpy()
+    if dump:
+        dump_outputs(dump, dict(bufs, u0=u0, latent=lat64), rank)
+
+    def close():
+        ctx.synchronize()
+        vae.close()
+        net.close()
+        ctx.close()
+
+    out = {
+        "metric": "NMPC solves/sec, config C5: 4x-wide SDF MLP + in-loop VAE encode, N=60, batch 4096 over 8 GPUs",
+        "value": total * steps / el,
+        "unit": "instance-RTI-solves/s (incl. VAE encode)",
+        "n_gpus": world, "steps": steps, "warmup": warm, "ms_per_step": el / steps * 1e3,
+        "higher_is_better": True, "scaling": "strong" if global_batch > 0 else "weak", "vs_baseline": None,
+        "dtype": "f32 (VAE convs as fp32-exact bf16 splits on the bf16 MFMA; wide SDF MLP on the f32 MFMA) + f64 "
+                 "(linearisation, QP)",
+        "data": "synthetic depth images (seeded scenes + noise), synthetic VAE weights, SIREN-init wide SDF seed 0",
+        "config": {"workload": f"C5: batch={B} instances per GPU x N={N}; per step: VAE encode of B 1x270x480 depth "
+                               "images -> latent -> p, then one SQP-RTI solve with the [1024,1024,512,256] SDF",
+                   "global_batch": total, "horizon": N, "parallelism": f"instances sharded over {world} GPU(s)"},
+        "qp_iters_mean": float(it.mean()), "qp_iters_max": int(it.max()), "qp_converged_frac": float((st == 0).mean()),
+    }
+    if not full:
+        close()
+        return out
     ctx.enable_timing(True)
     ctx.reset_stats()
     reps = 5
@@ -763,19 +847,7 @@ def c5_leg(local, dev, world, rank, B, N, steps, warm, no_cpu, global_batch=0):
     wide_ms = sum(kms[k] for k in ("sdf_wide_hoist", "sdf_wide_emb", "sdf_wide_gemm", "sdf_wide_final"))
     conv_tf = conv_flop / (kms["vae_conv"] * 1e-3) / 1e12
     wide_tf = (wide_flop - B * 2 * 128 * 1536) / (kms["sdf_wide_gemm"] * 1e-3) / 1e12
-    out = {
-        "metric": "NMPC solves/sec, config C5: 4x-wide SDF MLP + in-loop VAE encode, N=60, batch 4096 over 8 GPUs",
-        "value": total * steps / el,
-        "unit": "instance-RTI-solves/s (incl. VAE encode)",
-        "n_gpus": world, "steps": steps, "warmup": warm, "ms_per_step": el / steps * 1e3,
-        "higher_is_better": True, "scaling": "strong" if global_batch > 0 else "weak", "vs_baseline": None,
-        "dtype": "f32 (VAE convs as fp32-exact bf16 splits on the bf16 MFMA; wide SDF MLP on the f32 MFMA) + f64 "
-                 "(linearisation, QP)",
-        "data": "synthetic depth images (seeded scenes + noise), synthetic VAE weights, SIREN-init wide SDF seed 0",
-        "config": {"workload": f"C5: batch={B} instances per GPU x N={N}; per step: VAE encode of B 1x270x480 depth "
-                               "images -> latent -> p, then one SQP-RTI solve with the [1024,1024,512,256] SDF",
-                   "global_batch": total, "horizon": N, "parallelism": f"instances sharded over {world} GPU(s)"},
-        "qp_iters_mean": float(it.mean()), "qp_iters_max": int(it.max()), "qp_converged_frac": float((st == 0).mean()),
+    out.update({
         "kernel_ms_per_step": kms,
         # the convolutions run each fp32 product as six bf16 products (csrc/vae_enc.hip): the matrix pipe they
         # load is the bf16 one, so the fraction is of the dense bf16 peak at 6 pipe FLOP per fp32 FLOP;
@@ -790,7 +862,7 @@ def c5_leg(local, dev, world, rank, B, N, steps, warm, no_cpu, global_batch=0):
                                       "bf16 splits on the bf16 pipe (sdf_wide.hip SPLIT; SDFNMPC_WIDE_F32=1: f32 MFMA)"},
         "vae_ms": vae_ms, "wide_sdf_ms": wide_ms,
         "cpu_baseline": None,
-    }
+    })
     if rank == 0 and world == 1 and not no_cpu:
         # the same per-instance work on the host: fp64 C encoder (oracle/vae.c) of the instance's image,
         # the wide network's preparation phase (oracle/oracle.c) and the structured C IPM, a bounded sample
@@ -819,10 +891,7 @@ def c5_leg(local, dev, world, rank, B, N, steps, warm, no_cpu, global_batch=0):
                                "sample": f"{S} instances: fp64 C encoder (oracle/vae.c, OpenMP) of one 270x480 image "
                                          f"each, the wide network's preparation phase at N={N} and the structured "
                                          "C IPM (oracle/oracle.c, oracle/qp_ipm.c)"}
-    ctx.synchronize()
-    vae.close()
-    net.close()
-    ctx.close()
+    close()
     return out
 
 

@@ -20,18 +20,18 @@ cat $O/smoke.log
 fi
 if [ "$PART" = all ] || [ "$PART" = 2 ]; then
 cd /tmp
-timeout -k 10 400 python $R/bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python $R/bench.py --full > $O/bench.json 2> $O/bench.err
 cat $O/bench.json
-timeout -k 10 400 python $R/bench.py --config c5 > $O/bench_c5.json 2> $O/bench_c5.err
+timeout -k 10 400 python $R/bench.py --full --config c5 > $O/bench_c5.json 2> $O/bench_c5.err
 cat $O/bench_c5.json
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- \
-    python3 $R/bench.py --no-cpu-baseline --no-b1 --no-c2 --no-c1 --no-scene > $O/bench_traced.json 2> $O/trace.err
+    python3 $R/bench.py --full --no-cpu-baseline --no-b1 --no-c2 --no-c1 --no-scene > $O/bench_traced.json 2> $O/trace.err
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_c5 -o bench -- \
-    python3 $R/bench.py --config c5 --no-cpu-baseline > $O/bench_c5_traced.json 2> $O/trace_c5.err
+    python3 $R/bench.py --full --config c5 --no-cpu-baseline > $O/bench_c5_traced.json 2> $O/trace_c5.err
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o p -- \
-    python3 $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 --prep-steps 2 --no-b1 --no-c2 --no-c1 --no-scene > /dev/null 2> $O/fetch.err
+    python3 $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --prep-steps 2 --no-b1 --no-c2 --no-c1 --no-scene > /dev/null 2> $O/fetch.err
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o p -- \
-    python3 $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 --prep-steps 2 --no-b1 --no-c2 --no-c1 --no-scene > /dev/null 2> $O/write.err
+    python3 $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --prep-steps 2 --no-b1 --no-c2 --no-c1 --no-scene > /dev/null 2> $O/write.err
 fi
 if [ "$PART" = all ] || [ "$PART" = 3 ]; then
 # the stamps driver is rebuilt from the current rti_qp.hip, so the stamps always describe this tree's kernel
