@@ -78,7 +78,6 @@ struct sdfnmpc_ctx {
     bool own_stream = false;
     hipStream_t aux = nullptr;                       // low-priority side stream (fork/join per call)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool lin_first = false;
     bool serial_prep = false;  // diagnostic (SDFNMPC_SERIAL_PREP=1): linearize after the SDF kernel, same stream
     int qp_kernel = SDFNMPC_QP_AUTO;  // SDFNMPC_QP_KERNEL=serial|segmented, or sdfnmpc_ctx_set_qp_kernel
     int tile_rows = 32;
@@ -193,8 +192,6 @@ extern "C" int sdfnmpc_ctx_create(int device, void* stream, sdfnmpc_ctx** out) {
         sdfnmpc_ctx_destroy(c);
         return fail(SDFNMPC_E_HIP, std::string("aux stream/events: ") + hipGetErrorString(e));
     }
-    const char* lf = getenv("SDFNMPC_LIN_FIRST");
-    c->lin_first = lf && *lf == '1';
     const char* sp = getenv("SDFNMPC_SERIAL_PREP");
     c->serial_prep = sp && *sp == '1';
     if (const char* qk = getenv("SDFNMPC_QP_KERNEL")) {
@@ -610,19 +607,6 @@ void pack_operand(std::vector<float>& dst, int N, int K, F&& W) {
 
 }  // namespace
 
-struct WideDev {  // plain row-major [N][K] fp32 operands of the wide schedule (sdf_wide.hip)
-    const float *F1 = nullptr, *F2 = nullptr, *F3 = nullptr, *F4 = nullptr;
-    const float *B4 = nullptr, *B3h = nullptr, *B3e = nullptr, *B2 = nullptr, *B1e = nullptr;
-    const float *Bz = nullptr, *Hz = nullptr, *bz = nullptr, *b2 = nullptr, *b4 = nullptr, *w5 = nullptr;
-    const float4* emb_tab = nullptr;
-    int P1 = 0, P2 = 0, P3 = 0, P4 = 0;  // layer widths padded to multiples of 128
-    int NEK = NE, NEB = 128;             // embedding width as a K segment / as the d e GEMMs' output
-    int nb = 0;                          // projected frequencies (n_dirs x nb_freqs)
-    int LH = L, LZ = L;                  // size_latent, and padded to a multiple of 128 (the GEMMs' K / N)
-    bool e3 = true;                      // layer 3 sees the embedding (res 'full' / 'state')
-    int act = 0;                         // 0 sin, 1 relu, 2 softplus
-};
-
 struct sdfnmpc_net {
     int device = 0;
     HostNet host;
@@ -633,8 +617,7 @@ struct sdfnmpc_net {
     const float* bias13 = nullptr;
     uint64_t fingerprint = 0;
     bool wide = false;
-    WideDev wd;
-    WideRowArgs wrow{};    // the row evaluator's operands (sdf_row_wide.hip); per-call fields left zero
+    WideRowArgs wrow{};    // a wide network's operands (sdf_wide.hip, sdf_row_wide.hip); per-call fields left zero
     bool wrow_ok = false;  // the row evaluator and its server fit this network (LDS, weight bytes)
     // process-unique id: caches keyed on a network (the host path's hoist) never confuse a freed
     // network with a new one allocated at the same address
@@ -749,7 +732,7 @@ static int upload_wide(sdfnmpc_ctx* ctx, HostNet&& h, sdfnmpc_net** out) {
         return fail(SDFNMPC_E_HIP, "wide net: device upload failed");
     }
     const float* d = (const float*)net->dmem;
-    WideDev& w = net->wd;
+    WideDev& w = net->wrow.w;
     int i = 0;
     w.F1 = d + off[i++]; w.F2 = d + off[i++]; w.F3 = d + off[i++]; w.F4 = d + off[i++];
     w.B4 = d + off[i++]; w.B3h = d + off[i++]; w.B3e = d + off[i++]; w.B2 = d + off[i++]; w.B1e = d + off[i++];
@@ -757,19 +740,12 @@ static int upload_wide(sdfnmpc_ctx* ctx, HostNet&& h, sdfnmpc_net** out) {
     w.Hz = d + off[i++]; w.bz = d + off[i++]; w.b2 = d + off[i++]; w.b4 = d + off[i++]; w.w5 = d + off[i++];
     w.emb_tab = (const float4*)(d + off[i++]);
     w.P1 = P1; w.P2 = P2; w.P3 = P3; w.P4 = P4; w.NEK = NEK; w.NEB = NEB;
-    w.nb = h.nd * h.nf; w.e3 = e3; w.act = h.act; w.LH = Lh; w.LZ = LZ;
-    net->args.b5 = h.b5[0];
-    net->args.w0 = h.w0;
-    WideRowArgs& ra = net->wrow;
-    ra.F1 = w.F1; ra.F2 = w.F2; ra.F3 = w.F3; ra.F4 = w.F4;
-    ra.B4 = w.B4; ra.B3h = w.B3h; ra.B3e = w.B3e; ra.B2 = w.B2; ra.B1e = w.B1e;
-    ra.Bz = w.Bz; ra.Hz = w.Hz; ra.bz = w.bz; ra.b2 = w.b2; ra.b4 = w.b4; ra.w5 = w.w5; ra.emb_tab = w.emb_tab;
-    ra.b5 = h.b5[0]; ra.w0 = h.w0;
-    ra.P1 = P1; ra.P2 = P2; ra.P3 = P3; ra.P4 = P4; ra.NEK = NEK; ra.NEB = NEB; ra.nb = w.nb;
-    ra.LH = Lh; ra.LZ = LZ; ra.e3 = e3 ? 1 : 0; ra.act = h.act;
+    w.nb = h.nd * h.nf; w.e3 = e3 ? 1 : 0; w.act = h.act; w.LH = Lh; w.LZ = LZ;
+    w.b5 = h.b5[0];
+    w.w0 = h.w0;
     // one workgroup per row streams every weight once per row: worth it while the weights are L2 / MALL
     // sized (a C5-sized network is faster on the layer-by-layer GEMMs)
-    const size_t srv_lds = wide_row_lds_bytes(ra) + 2 * SDF_MBOX_FLOATS * sizeof(float);
+    const size_t srv_lds = wide_row_lds_bytes(w) + 2 * SDF_MBOX_FLOATS * sizeof(float);
     net->wrow_ok = srv_lds <= 160 * 1024 && blob.size() * sizeof(float) <= wide_row_weight_cap();
     net->fingerprint = net_fingerprint(h);
     net->host = std::move(h);
@@ -812,25 +788,13 @@ static int upload_net(sdfnmpc_ctx* ctx, HostNet&& h, sdfnmpc_net** out) {
     while (blob.size() % 4) blob.push_back(0.0f);
     mark();
     emb_table(h, blob);
-    // plain torch-layout copies for the single-row latency path (sdf_row.hip)
-    auto plain = [&](const std::vector<float>& v) {
-        mark();
-        blob.insert(blob.end(), v.begin(), v.end());
-        while (blob.size() % 4) blob.push_back(0.0f);
-    };
-    auto padded = [&](const std::vector<float>& v, int J, int K) {  // rows padded to a multiple of 4 floats
-        const int K4 = (K + 3) / 4 * 4;
-        std::vector<float> t((size_t)J * K4, 0.0f);
-        for (int j = 0; j < J; ++j)
-            for (int k = 0; k < K; ++k) t[(size_t)j * K4 + k] = v[(size_t)j * K + k];
-        plain(t);
-    };
-    padded(h.W1, N1, c1); padded(h.W2, N2, N1); padded(h.W3, N3, c3); padded(h.W4, N4, N3);
+    // torch-layout weights transposed ([K][J], J a multiple of 4) for the single-row latency path (sdf_row.hip)
     auto transposed = [&](const std::vector<float>& v, int J, int K) {
-        std::vector<float> t((size_t)J * K);
+        mark();
+        blob.resize(blob.size() + (size_t)J * K);
+        float* t = blob.data() + off.back();
         for (int j = 0; j < J; ++j)
             for (int k = 0; k < K; ++k) t[(size_t)k * J + j] = v[(size_t)j * K + k];
-        plain(t);
     };
     transposed(h.W1, N1, c1); transposed(h.W2, N2, N1); transposed(h.W3, N3, c3); transposed(h.W4, N4, N3);
     for (size_t o : off)
@@ -874,10 +838,6 @@ static int upload_net(sdfnmpc_ctx* ctx, HostNet&& h, sdfnmpc_net** out) {
     a.b5 = h.b5[0];
     a.w0 = h.w0;
     SdfRowArgs& ra = net->row;
-    ra.W1 = d + off[i++];
-    ra.W2 = d + off[i++];
-    ra.W3 = d + off[i++];
-    ra.W4 = d + off[i++];
     ra.W1T = d + off[i++];
     ra.W2T = d + off[i++];
     ra.W3T = d + off[i++];
@@ -979,7 +939,7 @@ static int run_wide(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, long long rows, co
                     const double* zd, long long zstride, int n_inst, int rows_per_inst, float4* out4,
                     const SdfArgs* cons, float* glat = nullptr) {
     if (rows > 0x7fffffffLL / 2) return fail(SDFNMPC_E_ARG, "too many rows");
-    const WideDev& w = net->wd;
+    const WideDev& w = net->wrow.w;
     const int n1 = w.P1, n2 = w.P2, n3 = w.P3, n4 = w.P4, nz = n1 + n3, R = (int)rows;
     const int NEK = w.NEK, NEB = w.NEB, LH = w.LH, LZ = w.LZ;
     const bool zpad = LH != LZ;  // size_latent not a multiple of 128: padded latent and d z staging
@@ -1004,7 +964,7 @@ static int run_wide(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, long long rows, co
         HIPCHK(timed(ctx, "sdf_wide_hoist", [&] { return launch_wide_latent<float>(zf, LH, n_inst, LH, LZ, z, st); }));
         zf = z;
     }
-    const float w0 = net->args.w0;
+    const float w0 = w.w0;
     auto gemm = [&](const float* A1, int K1, const float* A2, int K2, const float* W, int M, int N, int epi,
                     const float* bias, const float* c, const float* d, int ldd, float* o1, float* o2,
                     const char* name) -> hipError_t {
@@ -1048,7 +1008,7 @@ static int run_wide(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, long long rows, co
             HIPCHK(hipMemcpy2DAsync(glat, (size_t)LH * sizeof(float), gz, (size_t)LZ * sizeof(float),
                                     (size_t)LH * sizeof(float), (size_t)R, hipMemcpyDeviceToDevice, st));
     }
-    ea.H4 = H4; ea.GE3 = GE3; ea.GE1 = GE1; ea.w5 = w.w5; ea.b5 = net->args.b5; ea.out = out4;
+    ea.H4 = H4; ea.GE3 = GE3; ea.GE1 = GE1; ea.w5 = w.w5; ea.b5 = w.b5; ea.out = out4;
     HIPCHK(timed(ctx, "sdf_wide_final", [&] { return launch_wide_final(ea, st); }));
     return SDFNMPC_OK;
 }
@@ -1198,7 +1158,7 @@ static int srv_call(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, int rows, const fl
     S.acc[1] += (double)(vm->t_done - vm->t_staged) * 1e3 / S.khz;
     S.acc[2] += std::chrono::duration<double>(S.last - t0).count() * 1e6;
     S.acc[3] += 1.0;
-    if (!net->wide)  // row_eval's phase stamps (the variant server keeps none)
+    if (!net->wide)  // row_eval's phase stamps (row_eval_wide writes none)
         for (int i = 0; i < 14; ++i)
             S.ph[i] += (double)(vm->t_phase[i] - (i ? vm->t_phase[i - 1] : vm->t_staged)) * 1e3 / S.khz;
     return SDFNMPC_OK;
@@ -1226,6 +1186,18 @@ extern "C" int sdfnmpc_ctx_set_sdf_server(sdfnmpc_ctx* ctx, int on) {
     if (!on && !srv_stop(ctx)) return SDFNMPC_E_HIP;
     ctx->srv.mode = on;
     return SDFNMPC_OK;
+}
+
+// one launch of the network's row evaluator on the context's stream
+static hipError_t launch_row(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const RowCall& c) {
+    if (net->wide) {
+        WideRowArgs ra = net->wrow;
+        ra.c = c;
+        return timed(ctx, "sdf_row_wide", [&] { return launch_sdf_row_wide(ra, ctx->stream); });
+    }
+    SdfRowArgs ra = net->row;
+    ra.c = c;
+    return timed(ctx, "sdf_row", [&] { return launch_sdf_row(ra, ctx->stream); });
 }
 
 extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, int rows, const double* in,
@@ -1261,50 +1233,27 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
         if (rc != SDFNMPC_OK && rc != SRV_FALLBACK) return rc;
         served = rc == SDFNMPC_OK;
     }
-    if (!served && use_row) {  // the latency path: one launch, no hoist (sdf_row.hip).  Zero-copy (the kernel reading
-        // and writing the pinned block over PCIe) was measured equal in wall time: the PCIe reads add
-        // ~2 us to the kernel, as much as the two staging copies cost.
-        HIPCHK(ctx->hin.ensure(nin * sizeof(float)));
-        HIPCHK(ctx->hout.ensure(nin * sizeof(float)));
-        float* dpos = (float*)ctx->hin.p;
-        float* dout = (float*)ctx->hout.p;
-        HIPCHK(hipMemcpyAsync(dpos, hp, nin * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        if (net->wide) {
-            WideRowArgs ra = net->wrow;
-            ra.pos = (const float4*)dpos;
-            ra.latent = dpos + (size_t)rows * 4;
-            ra.out = (float4*)dout;
-            ra.grad_latent = grad ? dout + (size_t)rows * 4 : nullptr;
-            ra.rows = rows;
-            HIPCHK(timed(ctx, "sdf_row_wide", [&] { return launch_sdf_row_wide(ra, ctx->stream); }));
-        } else {
-            SdfRowArgs ra = net->row;
-            ra.pos = (const float4*)dpos;
-            ra.latent = dpos + (size_t)rows * 4;
-            ra.out = (float4*)dout;
-            ra.grad_latent = grad ? dout + (size_t)rows * 4 : nullptr;
-            ra.rows = rows;
-            HIPCHK(timed(ctx, "sdf_row", [&] { return launch_sdf_row(ra, ctx->stream); }));
-        }
-        HIPCHK(hipMemcpyAsync(ho, dout, (grad ? nin : (size_t)rows * 4) * sizeof(float), hipMemcpyDeviceToHost,
-                              ctx->stream));
-        HIPCHK(host_wait(ctx));
-    } else if (!served) {
+    if (!served) {
         HIPCHK(ctx->hin.ensure(nin * sizeof(float)));
         HIPCHK(ctx->hout.ensure(nin * sizeof(float)));
         float* dpos = (float*)ctx->hin.p;
         float* dlat = dpos + (size_t)rows * 4;
         float* dout = (float*)ctx->hout.p;
-        float* dglat = dout + (size_t)rows * 4;
-        // the latent hoist depends on the latents only: reuse it while they repeat (the same image's
-        // latent at every shooting node of an RTI); the positions go up every call
-        const bool same_lat = !net->wide && ctx->h_net == net->uid && ctx->h_lat.size() == (size_t)rows * L &&
+        float* dglat = grad ? dout + (size_t)rows * 4 : nullptr;
+        // the batched path's latent hoist depends on the latents only: reuse it while they repeat (the same
+        // image's latent at every shooting node of an RTI); the positions go up every call
+        const bool same_lat = !use_row && !net->wide && ctx->h_net == net->uid &&
+                              ctx->h_lat.size() == (size_t)rows * L &&
                               !memcmp(ctx->h_lat.data(), hl, (size_t)rows * L * sizeof(float));
         HIPCHK(hipMemcpyAsync(dpos, hp, (same_lat ? (size_t)rows * 4 : nin) * sizeof(float), hipMemcpyHostToDevice,
                               ctx->stream));
         int rc = SDFNMPC_OK;
-        if (net->wide) {
-            rc = sdfnmpc_sdf_eval(ctx, net, rows, dpos, dlat, 1, dout, grad ? dglat : nullptr);
+        if (use_row) {  // the latency path: one launch, no hoist.  Zero-copy (the kernel reading and writing the
+            // pinned block over PCIe) was measured equal in wall time: the PCIe reads add ~2 us to the kernel,
+            // as much as the two staging copies cost.
+            HIPCHK(launch_row(ctx, net, RowCall{(const float4*)dpos, dlat, (float4*)dout, dglat, rows}));
+        } else if (net->wide) {
+            rc = sdfnmpc_sdf_eval(ctx, net, rows, dpos, dlat, 1, dout, dglat);
         } else {
             if (!same_lat) {
                 HIPCHK(ctx->hc13.ensure((size_t)rows * C13_STRIDE * sizeof(float)));
@@ -1313,8 +1262,8 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
                 ctx->h_lat.assign(hl, hl + (size_t)rows * L);
                 ctx->h_net = net->uid;
             }
-            rc = run_sdf(ctx, net, rows, (const float4*)dpos, (const float*)ctx->hc13.p, 1, (float4*)dout,
-                         grad ? dglat : nullptr, grad ? 32 : ctx->tile_rows);
+            rc = run_sdf(ctx, net, rows, (const float4*)dpos, (const float*)ctx->hc13.p, 1, (float4*)dout, dglat,
+                         grad ? 32 : ctx->tile_rows);
         }
         if (rc) {
             ctx->h_net = 0;
@@ -1430,7 +1379,6 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
         HIPCHK(timed(ctx, "linearize", [&] { return launch_linearize(la, ctx->stream); }, ctx->stream));
         return finish_pack();
     }
-    if (ctx->lin_first && (rc = fork_lin())) return rc;
     // 2. latent hoisting (latent = p[.][17:] as fp32)
     const long long stride = a->latent_mode == 0 ? (long long)(a->N + 1) * a->np : (long long)a->np;
     SdfArgs cons{};
@@ -1441,44 +1389,36 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
     cons.Jh = a->Jh;
     cons.max_df = net->host.max_df;
     if (net->wide) {  // layer-by-layer schedule, linearisation forked first so it overlaps the GEMMs
-        if (!ctx->lin_first && (rc = fork_lin())) return rc;
+        if ((rc = fork_lin())) return rc;
         rc = run_wide(ctx, net, rows, nullptr, nullptr, a->p + 17, stride, n_inst, a->latent_mode == 0 ? a->N + 1 : 1,
                       sdf4, &cons);
         if (rc) return rc;
-        if (serial) {
-            HIPCHK(timed(ctx, "linearize", [&] { return launch_linearize(la, ctx->stream); }, ctx->stream));
-            return finish_pack();
-        }
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        return finish_pack();
-    }
-    if (rows <= SDF_ROW_PREP_MAX) {  // a few rows (B = 1): one workgroup per row, no hoist
+    } else if (rows <= SDF_ROW_PREP_MAX) {  // a few rows (B = 1): one workgroup per row, no hoist
         // the row kernel is the critical path: queued right after the fork mark, before the host spends
         // the auxiliary stream's API calls (≈15 µs at B = 1, round 5 trace), which the mark keeps it
         // independent of
-        if (!ctx->lin_first && (rc = fork_mark())) return rc;
+        if ((rc = fork_mark())) return rc;
         SdfRowArgs ra = net->row;
         ra.x = a->x; ra.p = a->p; ra.np = a->np;
         ra.zd = a->p + 17; ra.zstride = stride; ra.rows_per_inst = a->latent_mode == 0 ? a->N + 1 : 1;
         ra.h = a->h; ra.Jh = a->Jh; ra.max_df = net->host.max_df;
-        ra.out = sdf4;
-        ra.rows = (int)rows;
+        ra.c.out = sdf4;
+        ra.c.rows = (int)rows;
         HIPCHK(timed(ctx, "sdf_row", [&] { return launch_sdf_row(ra, ctx->stream); }));
-        if (!ctx->lin_first && (rc = fork_launch())) return rc;
+        if ((rc = fork_launch())) return rc;
     } else {
         rc = run_hoist<double>(ctx, net, a->p + 17, stride, n_inst, (float*)ctx->c13.p);
         if (rc) return rc;
-        if (!ctx->lin_first && (rc = fork_lin())) return rc;
+        if ((rc = fork_lin())) return rc;
         // 3. network forward + position gradient, with the sdf row of h / J_h in its epilogue
         rc = run_sdf(ctx, net, rows, nullptr, (const float*)ctx->c13.p,
                      a->latent_mode == 0 ? a->N + 1 : 1, sdf4, nullptr, ctx->tile_rows, &cons);
         if (rc) return rc;
     }
-    if (serial) {
+    if (serial)
         HIPCHK(timed(ctx, "linearize", [&] { return launch_linearize(la, ctx->stream); }, ctx->stream));
-        return finish_pack();
-    }
-    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    else
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     return finish_pack();
 }
 

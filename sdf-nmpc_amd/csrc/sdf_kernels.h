@@ -59,21 +59,24 @@ struct SdfArgs {
     int rows_per_inst;      // row r uses c13[r / rows_per_inst]
 };
 
-// single-row latency path (sdf_row.hip): plain row-major torch-layout weights, value + full input gradient
+// per-call fields of the single-row latency paths (sdf_row.hip, sdf_row_wide.hip); LH = size_latent
+struct RowCall {
+    const float4* pos;      // [rows] (Co_p_B, pad)
+    const float* latent;    // [rows][LH]
+    float4* out;            // [rows] (df, d df / d pos)
+    float* grad_latent;     // [rows][LH] or NULL
+    int rows;
+};
+
+// single-row latency path (sdf_row.hip): the torch-layout weights transposed, value + full input gradient
 struct SdfRowArgs {
-    const float *W1, *b1;   // [N1][E + L], [N1]     (rows padded to a multiple of 4 floats)
-    const float *W2, *b2;   // [N2][N1]
-    const float *W3, *b3;   // [N3][N2 + E + L]
-    const float *W4, *b4;   // [N4][N3]
-    const float *W1T, *W2T, *W3T, *W4T;  // the same, transposed ([K][J]): the forward's coalesced operand
+    const float *W1T, *W2T, *W3T, *W4T;  // [E + L][N1], [N1][N2], [N2 + E + L][N3], [N3][N4]: W^T ([K][J]),
+                                         // the coalesced operand of both directions
+    const float *b1, *b2, *b3, *b4;      // [N1], [N2], [N3], [N4]
     const float* w5;        // [N4]
     float b5, w0;
     const float4* emb_tab;  // [NE]
-    const float4* pos;      // [rows] (Co_p_B, pad)
-    const float* latent;    // [rows][L]
-    float4* out;            // [rows] (df, d df / d pos)
-    float* grad_latent;     // [rows][L] or NULL
-    int rows;
+    RowCall c;
     // preparation-phase variant (sdfnmpc_linearize at a few rows, x != NULL): Co_p_B from x / p and the
     // constraint epilogue exactly as sdf_mlp_kernel forms them (SdfArgs), the latent from the fp64
     // stage parameters of the row's instance
@@ -88,10 +91,10 @@ struct SdfRowArgs {
 constexpr int SDF_ROW_MAX = 16;       // host-path calls with at most this many rows use sdf_row_kernel
 constexpr int SDF_ROW_PREP_MAX = 64;  // and preparation phases with at most this many rows (B=1 at N <= 63)
 
-// Resident SDF server (the C2 latency path, sdf_row.hip): one persistent workgroup polls this mailbox in
+// Resident SDF server (the C2 latency path; sdf_server_loop, sdf_row_dev.h): one persistent workgroup polls this mailbox in
 // pinned, coherent host memory, so a CasADi-external call costs no kernel launch and no copies.  The host
 // writes rows / grad / in, then seq_in (release); the server stages the request into LDS, evaluates the
-// rows with sdf_row's arithmetic, writes out, then seq_out = seq_in (release).  The server exits on
+// rows with its network's row evaluator, writes out, then seq_out = seq_in (release).  The server exits on
 // `stop`, after `idle` wall-clock ticks without a request, or after `life` ticks in total; the host
 // relaunches it when it finds it gone.  Sequence words sit on their own 128-byte lines.
 struct alignas(128) SdfMbox {
@@ -157,26 +160,35 @@ struct WideSdfArgs {
     double* h; double* Jh; double max_df;
 };
 
-// Single-row latency path for every network other than the deployed one (sdf_row_wide.hip): the wide
-// schedule's row-major [N][K] operands (engine.cpp upload_wide) as GEMVs inside one 512-thread workgroup per
-// row, value + full input gradient (d df / d pos and d df / d latent), served by the resident server or
-// launched per call.  Same semantics as wide_gemm's layers (activations, res modes, padding).
-struct WideRowArgs {
+// Device weights of a wide network (engine.cpp upload_wide): plain row-major [N][K] fp32 operands, read by
+// the layer-by-layer schedule (sdf_wide.hip) and by the row evaluator (sdf_row_wide.hip)
+struct WideDev {
     const float *F1, *F2, *F3, *F4;            // forward [P1][NEK], [P2][P1], [P3][P2 (+ NEK)], [P4][P3]
     const float *B4, *B3h, *B3e, *B2, *B1e;    // backward [P3][P4], [P2][P3], [NEB][P3], [P1][P2], [NEB][P1]
     const float *Bz, *Hz, *bz, *b2, *b4, *w5;  // [LZ][P1 + P3], [P1 + P3][LZ], [P1 + P3], [P2], [P4], [P4]
     const float4* emb_tab;                     // [NEK]
     float b5, w0;
-    int P1, P2, P3, P4, NEK, NEB, nb, LH, LZ, e3, act;
-    // per call
-    const float4* pos;      // [rows] (Co_p_B, pad)
-    const float* latent;    // [rows][LH]
-    float4* out;            // [rows] (df, d df / d pos)
-    float* grad_latent;     // [rows][LH] or NULL
-    int rows;
+    int P1, P2, P3, P4;  // layer widths padded to multiples of 128
+    int NEK, NEB;        // embedding width as a K segment / as the d e GEMMs' output
+    int nb;              // projected frequencies (n_dirs x nb_freqs)
+    int LH, LZ;          // size_latent, and padded to a multiple of 128 (the GEMMs' K / N)
+    int e3;              // layer 3 sees the embedding (res 'full' / 'state')
+    int act;             // 0 sin, 1 relu, 2 softplus
 };
-size_t wide_row_lds_bytes(const WideRowArgs& a);        // the evaluator's dynamic LDS
-int wide_row_max_rows(int LH);                           // rows per server request (the mailbox's capacity)
+
+// Single-row latency path for every network other than the deployed one (sdf_row_wide.hip): the wide
+// schedule's operands as GEMVs inside one 512-thread workgroup per row, value + full input gradient
+// (d df / d pos and d df / d latent), served by the resident server or launched per call.  Same semantics
+// as wide_gemm's layers (activations, res modes, padding).
+struct WideRowArgs {
+    WideDev w;
+    RowCall c;
+};
+size_t wide_row_lds_bytes(const WideDev& a);            // the evaluator's dynamic LDS
+__host__ __device__ inline int wide_row_max_rows(int LH) {  // rows per server request (the mailbox's capacity)
+    const int n = SDF_MBOX_FLOATS / (4 + LH);
+    return n < SDF_ROW_MAX ? n : SDF_ROW_MAX;
+}
 hipError_t launch_sdf_row_wide(const WideRowArgs& a, hipStream_t s);
 hipError_t launch_sdf_server_wide(const WideRowArgs& a, SdfMbox* mb_dev, long long idle_ticks, long long life_ticks,
                                   unsigned long long epoch, hipStream_t s);

@@ -15,10 +15,7 @@
 // returns; the arithmetic of the embedding and its derivative is sdf_mlp.hip's / sdf_wide.hip's.
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
-#include "sdf_kernels.h"
-#include "sincos.h"
+#include "sdf_row_dev.h"
 
 namespace sdfn {
 
@@ -28,12 +25,6 @@ constexpr int RW = 8;             // waves per row workgroup
 constexpr int C1 = E + L;         // W1 row length (211)
 constexpr int C3 = N2 + E + L;    // W3 row length (467)
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // A layer at one row is a GEMV over ~0.25 MB of L2/MALL-resident weights: its time is the memory
 // latency unless every load of the layer is in flight at once.  Both directions therefore give each
 // thread one float4 column quad and a slice of the reduction dimension, issue the slice's loads
@@ -42,24 +33,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // out[j] = bias[j] + W[j][:K] . in  for j < J, from the transposed copy WT [K][J] (row k of WT: the
 // k-th input's weights of every output, 16-byte aligned): thread t owns outputs 4q..4q+3, q = t % (J/4),
-// over the K-slice t / (J/4)
-// The weight pointer of a layer is laundered at the layer: in the resident server's request loop the
-// compiler would otherwise issue every layer's weight loads up front (or hoist them out of the loop)
-// and spill them to scratch.
-template <typename T>
-__device__ __forceinline__ const T* launder(const T* p) {
-    asm volatile("" : "+s"(p));
-    return p;
-}
-
-// threadIdx.x behind an opaque copy: in the server's request loop the compiler would otherwise hoist
-// every lane-dependent index and address of the evaluation out of the loop and spill them
-__device__ __forceinline__ int tix() {
-    int t = threadIdx.x;
-    asm volatile("" : "+v"(t));
-    return t;
-}
-
+// over the K-slice t / (J/4).  The weight pointer is laundered at the layer (sdf_row_dev.h).
 template <int J, int K>
 __device__ __forceinline__ void fwd(const float* __restrict__ WT_, const float* __restrict__ bias, const float* in,
                                     float* part, float* out) {
@@ -92,22 +66,6 @@ __device__ __forceinline__ void fwd(const float* __restrict__ WT_, const float* 
         for (int r = 0; r < S; ++r) v += part[r * J + t];
         out[t] = v + bias[t];
     }
-}
-
-// sum over aligned groups of QR lanes (QR = 4, 8 or 16, inside one DPP row), every lane of a group
-// receiving the group's sum: quad butterflies, then the half-row and row mirrors
-template <int QR>
-__device__ __forceinline__ float group_sum(float v) {
-    static_assert(QR == 4 || QR == 8 || QR == 16, "group of 4, 8 or 16 lanes");
-    auto dpp = [](float x, auto ctrl) {
-        constexpr int C = decltype(ctrl)::value;
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), C, 0xf, 0xf, false));
-    };
-    v += dpp(v, std::integral_constant<int, 0xB1>{});  // quad_perm [1, 0, 3, 2]
-    v += dpp(v, std::integral_constant<int, 0x4E>{});  // quad_perm [2, 3, 0, 1]
-    if constexpr (QR >= 8) v += dpp(v, std::integral_constant<int, 0x141>{});  // row_half_mirror
-    if constexpr (QR >= 16) v += dpp(v, std::integral_constant<int, 0x140>{});  // row_mirror
-    return v;
 }
 
 // out[k] = sum_j W[j][k] d[j] for k < K from the TRANSPOSED copy WT [K][J] (the forward's operand, so
@@ -160,7 +118,7 @@ __device__ __forceinline__ void bwd_t(const float* __restrict__ WT_, const float
     } while (0)
 
 // value + gradient of row r by the whole (64 RW)-thread workgroup; shared by the per-call kernel and the
-// resident server (A.pos / A.latent may point into LDS there)
+// resident server (A.c's pointers are into LDS there)
 __device__ __forceinline__ void row_eval(const SdfRowArgs& A, const int r) {
     const int lane = tix() & 63, wave = tix() >> 6;
     __shared__ float in1[C1], in3[C3], gm[NE];             // [e | z], [h2 | e | z], d e / d xb
@@ -179,20 +137,12 @@ __device__ __forceinline__ void row_eval(const SdfRowArgs& A, const int r) {
         p = make_float4((float)((e0 * R[0] + e1 * R[3]) + e2 * R[6]), (float)((e0 * R[1] + e1 * R[4]) + e2 * R[7]),
                         (float)((e0 * R[2] + e1 * R[5]) + e2 * R[8]), 0.0f);
     } else {
-        p = A.pos[r];
+        p = A.c.pos[r];
     }
-    // ---- embedding (e = [x, sin(xb), sin(xb + pi/2)], sdf_wide.hip's arithmetic) and the latent
+    // ---- embedding and the latent
     for (int m = tix(); m < NE; m += 64 * RW) {
-        float e = 0.0f, g = 0.0f;
-        if (m < 3) {
-            e = m == 0 ? p.x : (m == 1 ? p.y : p.z);
-            g = 1.0f;
-        } else if (m < E) {
-            const float4 t = A.emb_tab[m];
-            float xb = p.x * t.x + p.y * t.y + p.z * t.z;
-            if (m >= 3 + EMB_NB) xb = xb + 1.57079637050628662109375f;
-            sdfn_sincosf(xb, &e, &g);
-        }
+        float e, g;
+        embed_feature(p, m, EMB_NB, A.emb_tab, e, g);
         gm[m] = g;
         if (m < E) {
             in1[m] = e;
@@ -200,7 +150,7 @@ __device__ __forceinline__ void row_eval(const SdfRowArgs& A, const int r) {
         }
     }
     for (int k = tix(); k < L; k += 64 * RW) {
-        const float z = A.zd ? (float)A.zd[(size_t)(r / A.rows_per_inst) * A.zstride + k] : A.latent[(size_t)r * L + k];
+        const float z = A.zd ? (float)A.zd[(size_t)(r / A.rows_per_inst) * A.zstride + k] : A.c.latent[(size_t)r * L + k];
         in1[E + k] = z;
         in3[N2 + E + k] = z;
     }
@@ -273,29 +223,14 @@ __device__ __forceinline__ void row_eval(const SdfRowArgs& A, const int r) {
     bwd_t<N1, C1>(A.W1T, a1, g1);             // [d e | d z]
     ROW_STAMP(12);
     // ---- outputs: df, d df / d pos (through the embedding), d df / d latent
-    if (A.grad_latent)
-        for (int k = tix(); k < L; k += 64 * RW) A.grad_latent[(size_t)r * L + k] = g3[N2 + E + k] + g1[E + k];
+    if (A.c.grad_latent)
+        for (int k = tix(); k < L; k += 64 * RW) A.c.grad_latent[(size_t)r * L + k] = g3[N2 + E + k] + g1[E + k];
     if (wave == 0) {
-        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-        for (int m = lane; m < E; m += 64) {
-            const float u = (g3[N2 + m] + g1[m]) * gm[m];
-            if (m < 3) {
-                s0 += m == 0 ? u : 0.0f;
-                s1 += m == 1 ? u : 0.0f;
-                s2 += m == 2 ? u : 0.0f;
-            } else {
-                const float4 t = A.emb_tab[m];
-                s0 = fmaf(u, t.x, s0);
-                s1 = fmaf(u, t.y, s1);
-                s2 = fmaf(u, t.z, s2);
-            }
-        }
-        s0 = wave_sum(s0);
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
+        float s0, s1, s2;
+        dpos_sum(g3 + N2, g1, gm, A.emb_tab, E, lane, s0, s1, s2);
         if (lane == 0) {
             const float df = red[0];
-            A.out[r] = make_float4(df, s0, s1, s2);
+            A.c.out[r] = make_float4(df, s0, s1, s2);
             if (A.h) {  // sdf row of the constraint vector and its Jacobian (gen_model.py:46-61), as sdf_mlp_kernel
                 const double* pr = A.p + (size_t)r * A.np;
                 const double flag = pr[0];
@@ -314,77 +249,14 @@ __device__ __forceinline__ void row_eval(const SdfRowArgs& A, const int r) {
 
 __global__ __launch_bounds__(64 * RW) void sdf_row_kernel(SdfRowArgs A) { row_eval(A, blockIdx.x); }
 
-
-// system-scope (host-coherent) accesses of the mailbox: vector loads / stores that bypass the GPU caches
-__device__ __forceinline__ unsigned long long mb_load(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ unsigned int mb_load_u32(const unsigned int* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__device__ __forceinline__ void mb_store(long long* p, long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// The resident server (SdfMbox, sdf_kernels.h): thread 0 polls seq_in; the request is staged into LDS
-// with one PCIe read per word; the rows are evaluated by row_eval with the outputs written straight into
-// the mailbox; after a system-scope fence seq_out publishes them.  Every exit path (stop, idle, life) is
-// taken by the whole workgroup together (the decision goes through LDS behind a barrier), between
-// requests, and ends with the launch's epoch stored to `gone`, so a caller that posted a request the
-// leaving server did not see relaunches at once instead of waiting for the stream to drain.  The life
-// bound (0.8 ms by default) is what a device-wide synchronisation elsewhere in the process can wait.
+// the resident server (sdf_server_loop, sdf_row_dev.h): request and results in static LDS, row_eval's
+// phase stamps into the mailbox
 __global__ __launch_bounds__(64 * RW) void sdf_server_kernel(SdfRowArgs A, SdfMbox* mb, long long idle,
                                                               long long life, unsigned long long epoch) {
     __shared__ __align__(16) float s_in[SDF_ROW_MAX * (4 + L)], s_out[SDF_ROW_MAX * (4 + L)];
-    __shared__ unsigned long long s_seq;
-    __shared__ int s_go, s_rows, s_grad;
-    const long long t0 = wall_clock64();
-    long long last = t0;
-    unsigned long long done = 0;
-    if (threadIdx.x == 0) done = mb_load(&mb->seq_out);
-    for (;;) {
-        if (threadIdx.x == 0) {
-            int go = 0;
-            unsigned long long q = done;
-            for (;;) {
-                q = mb_load(&mb->seq_in);
-                if (q != done) {
-                    go = 1;
-                    break;
-                }
-                const long long now = wall_clock64();
-                if (mb_load(&mb->stop) || now - last > idle || now - t0 > life) break;
-                __builtin_amdgcn_s_sleep(2);
-            }
-            s_go = go;
-            s_seq = q;
-            if (go) {
-                const int rows = (int)mb_load_u32((const unsigned int*)&mb->rows);
-                s_rows = rows < 1 ? 1 : (rows > SDF_ROW_MAX ? SDF_ROW_MAX : rows);
-                s_grad = (int)mb_load_u32((const unsigned int*)&mb->grad);
-            }
-        }
-        __syncthreads();
-        if (!s_go) {
-            if (threadIdx.x == 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(&mb->gone, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            break;
-        }
-        const long long t_seen = wall_clock64();
-        const int rows = s_rows;
-        for (int i = threadIdx.x; i < rows * (4 + L); i += 64 * RW)
-            s_in[i] = __uint_as_float(mb_load_u32((const unsigned int*)mb->in + i));
-        __syncthreads();
-        const long long t_staged = wall_clock64();
+    sdf_server_loop<64 * RW>(mb, idle, life, epoch, s_in, s_out, L, SDF_ROW_MAX, [&](int rows, int grad) {
         SdfRowArgs B = A;
-        B.pos = (const float4*)s_in;
-        B.latent = s_in + rows * 4;
-        B.out = (float4*)s_out;  // results go to LDS first, then to the mailbox with write-through stores
-        B.grad_latent = s_grad ? s_out + rows * 4 : nullptr;
-        B.rows = rows;
+        B.c = staged_call(s_in, s_out, rows, grad);
         B.x = nullptr;
         B.zd = nullptr;
         B.h = nullptr;
@@ -393,27 +265,7 @@ __global__ __launch_bounds__(64 * RW) void sdf_server_kernel(SdfRowArgs A, SdfMb
             row_eval(B, r);
             __syncthreads();  // row_eval's LDS is reused by the next row
         }
-        const long long t_done = wall_clock64();
-        // Publishing without an L2 write-back (__threadfence_system's buffer_wbl2, ~1.7 us each): the
-        // results leave with system-scope stores, which write through the GPU caches to host memory; once
-        // every wave's stores have completed (vmcnt(0)) and met at the barrier, one lane stores seq_out.
-        // (Plain stores would stay in the L2 and the host would read stale results.)
-        for (int i = threadIdx.x; i < rows * (s_grad ? 4 + L : 4); i += 64 * RW)
-            __hip_atomic_store((unsigned int*)mb->out + i, __float_as_uint(s_out[i]), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            mb_store(&mb->t_seen, t_seen);
-            mb_store(&mb->t_staged, t_staged);
-            mb_store(&mb->t_done, t_done);
-            mb_store(&mb->t_phase[13], t_done);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(&mb->seq_out, s_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            done = s_seq;
-        }
-        last = wall_clock64();
-    }
+    });
 }
 
 hipError_t launch_sdf_server(const SdfRowArgs& a, SdfMbox* mb_dev, long long idle_ticks, long long life_ticks,
@@ -423,8 +275,8 @@ hipError_t launch_sdf_server(const SdfRowArgs& a, SdfMbox* mb_dev, long long idl
 }
 
 hipError_t launch_sdf_row(const SdfRowArgs& a, hipStream_t s) {
-    if (a.rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sdf_row_kernel, dim3((unsigned)a.rows), dim3(64 * RW), 0, s, a);
+    if (a.c.rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sdf_row_kernel, dim3((unsigned)a.c.rows), dim3(64 * RW), 0, s, a);
     return hipGetLastError();
 }
 

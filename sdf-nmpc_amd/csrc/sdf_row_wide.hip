@@ -18,10 +18,8 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <type_traits>
 
-#include "sdf_kernels.h"
-#include "sincos.h"
+#include "sdf_row_dev.h"
 
 namespace sdfn {
 
@@ -33,32 +31,6 @@ constexpr int GRP = 16;         // lanes per GEMV row
 constexpr int RPP = WT / GRP;   // rows per pass
 constexpr int U = 8;            // passes whose loads are in flight together
 constexpr int CI = 4;           // float4 chunks per lane per batch (U x CI float4 = 128 VGPRs of loads)
-
-// threadIdx.x behind an opaque copy (the server's request loop would otherwise hoist and spill every
-// lane-dependent address out of the loop, as in sdf_row.hip)
-__device__ __forceinline__ int tix() {
-    int t = threadIdx.x;
-    asm volatile("" : "+v"(t));
-    return t;
-}
-template <typename T>
-__device__ __forceinline__ const T* launder(const T* p) {
-    asm volatile("" : "+s"(p));
-    return p;
-}
-
-// sum over the 16 lanes of a DPP row, every lane receiving it (quad butterflies, half-row and row mirrors)
-__device__ __forceinline__ float row16_sum(float v) {
-    auto dpp = [](float x, auto ctrl) {
-        constexpr int C = decltype(ctrl)::value;
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), C, 0xf, 0xf, false));
-    };
-    v += dpp(v, std::integral_constant<int, 0xB1>{});
-    v += dpp(v, std::integral_constant<int, 0x4E>{});
-    v += dpp(v, std::integral_constant<int, 0x141>{});
-    v += dpp(v, std::integral_constant<int, 0x140>{});
-    return v;
-}
 
 __device__ __forceinline__ float dot4(float4 w, float4 x, float a) {
     a = fmaf(w.x, x.x, a);
@@ -108,7 +80,7 @@ __device__ __forceinline__ void gemv(const float* W_, int J, const float* x1, in
         float mine = 0.0f;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const float v = row16_sum(a[u]);
+            const float v = group_sum<GRP>(a[u]);
             mine = q == u ? v : mine;
         }
         const int j = j0 + q * RPP;
@@ -136,11 +108,11 @@ struct RowLds {
     float *e, *gm, *z, *hz, *h1, *d1, *h2, *d2, *h3, *d3, *h4, *d4, *ge3, *ge1, *red;
 };
 __host__ __device__ inline int r4(int n) { return (n + 3) & ~3; }
-__host__ __device__ inline size_t row_lds_floats(const WideRowArgs& a) {
+__host__ __device__ inline size_t row_lds_floats(const WideDev& a) {
     return 2 * (size_t)r4(a.NEK) + (size_t)a.LZ + (a.P1 + a.P3) + 2 * (size_t)(a.P1 + a.P2 + a.P3 + a.P4) +
            2 * (size_t)a.NEB + 8;
 }
-__device__ inline RowLds carve(float* q, const WideRowArgs& a) {
+__device__ inline RowLds carve(float* q, const WideDev& a) {
     RowLds s;
     auto take = [&](int n) { float* r = q; q += r4(n); return r; };
     s.e = take(a.NEK); s.gm = take(a.NEK); s.z = take(a.LZ); s.hz = take(a.P1 + a.P3);
@@ -152,29 +124,21 @@ __device__ inline RowLds carve(float* q, const WideRowArgs& a) {
 
 }  // namespace
 
-// value + gradient of row r by the whole workgroup (A.pos / A.latent / A.out may point into LDS)
-__device__ __forceinline__ void row_eval_wide(const WideRowArgs& A, const int r, float* lds) {
+// value + gradient of row r by the whole workgroup (c.pos / c.latent / c.out may point into LDS)
+__device__ __forceinline__ void row_eval_wide(const WideDev& A, const RowCall& c, const int r, float* lds) {
     const RowLds s = carve(lds, A);
     const int lane = tix() & 63, wave = tix() >> 6;
     const float w0 = A.w0;
     const int act = A.act;
-    const float4 p = A.pos[r];
+    const float4 p = c.pos[r];
     // ---- embedding e = [x, sin(xb), sin(xb + pi/2)] and its derivative factors (wide_emb_kernel's arithmetic)
     for (int m = tix(); m < A.NEK; m += WT) {
-        float e = 0.0f, g = 0.0f;
-        if (m < 3) {
-            e = m == 0 ? p.x : (m == 1 ? p.y : p.z);
-            g = 1.0f;
-        } else if (m < 3 + 2 * A.nb) {
-            const float4 t = A.emb_tab[m];
-            float xb = p.x * t.x + p.y * t.y + p.z * t.z;
-            if (m >= 3 + A.nb) xb = xb + 1.57079637050628662109375f;
-            sdfn_sincosf(xb, &e, &g);
-        }
+        float e, g;
+        embed_feature(p, m, A.nb, A.emb_tab, e, g);
         s.e[m] = e;
         s.gm[m] = g;
     }
-    for (int k = tix(); k < A.LZ; k += WT) s.z[k] = k < A.LH ? A.latent[(size_t)r * A.LH + k] : 0.0f;
+    for (int k = tix(); k < A.LZ; k += WT) s.z[k] = k < A.LH ? c.latent[(size_t)r * A.LH + k] : 0.0f;
     if (!A.e3)
         for (int m = tix(); m < A.NEB; m += WT) s.ge3[m] = 0.0f;
     __syncthreads();
@@ -195,8 +159,7 @@ __device__ __forceinline__ void row_eval_wide(const WideRowArgs& A, const int r,
     if (wave == 0) {  // df = w5 . h4 + b5
         float v = 0.0f;
         for (int n = lane; n < A.P4; n += 64) v = fmaf(A.w5[n], s.h4[n], v);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        v = wave_sum(v);
         if (lane == 0) s.red[0] = v + A.b5;
     }
     // ---- backward: delta_{l-1} = (W_l^T delta_l) * act'(a_{l-1}) (* w0 for sin): torch's SinBackward then
@@ -213,125 +176,35 @@ __device__ __forceinline__ void row_eval_wide(const WideRowArgs& A, const int r,
         gemv(A.B3e, A.NEB, s.h3, A.P3, nullptr, 0, [&](int j, float v) { s.ge3[j] = v; });
     gemv(A.B2, A.P1, s.h2, A.P2, nullptr, 0, bwd(s.h1, s.d1));
     gemv(A.B1e, A.NEB, s.h1, A.P1, nullptr, 0, [&](int j, float v) { s.ge1[j] = v; });
-    if (A.grad_latent) {  // d df / d z = [delta1 | delta3] . [W1z ; W3z]
-        float* gl = A.grad_latent + (size_t)r * A.LH;
+    if (c.grad_latent) {  // d df / d z = [delta1 | delta3] . [W1z ; W3z]
+        float* gl = c.grad_latent + (size_t)r * A.LH;
         gemv(A.Bz, A.LH, s.h1, A.P1, s.h3, A.P3, [&](int j, float v) { gl[j] = v; });
     }
     // ---- d df / d pos through the embedding (wide_final_kernel's sums, by one wave)
     if (wave == 0) {
-        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-        for (int m = lane; m < A.NEK; m += 64) {
-            const float u = (s.ge3[m] + s.ge1[m]) * s.gm[m];
-            if (m < 3) {
-                s0 += m == 0 ? u : 0.0f;
-                s1 += m == 1 ? u : 0.0f;
-                s2 += m == 2 ? u : 0.0f;
-            } else {
-                const float4 t = A.emb_tab[m];
-                s0 = fmaf(u, t.x, s0);
-                s1 = fmaf(u, t.y, s1);
-                s2 = fmaf(u, t.z, s2);
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s0 += __shfl_xor(s0, o);
-            s1 += __shfl_xor(s1, o);
-            s2 += __shfl_xor(s2, o);
-        }
-        if (lane == 0) A.out[r] = make_float4(s.red[0], s0, s1, s2);
+        float s0, s1, s2;
+        dpos_sum(s.ge3, s.ge1, s.gm, A.emb_tab, A.NEK, lane, s0, s1, s2);
+        if (lane == 0) c.out[r] = make_float4(s.red[0], s0, s1, s2);
     }
     __syncthreads();
 }
 
 __global__ __launch_bounds__(WT) void sdf_row_wide_kernel(WideRowArgs A) {
     extern __shared__ __align__(16) float lds_w[];
-    row_eval_wide(A, blockIdx.x, lds_w);
+    row_eval_wide(A.w, A.c, blockIdx.x, lds_w);
 }
 
-// system-scope (host-coherent) mailbox accesses, as sdf_row.hip's server
-__device__ __forceinline__ unsigned long long mbw_load(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ unsigned int mbw_load_u32(const unsigned int* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// The resident server for these networks: sdf_server_kernel's mailbox protocol (sdf_row.hip) -- poll seq_in,
-// stage the request into LDS, evaluate, write the results through to the mailbox, publish seq_out; leave on
-// stop, idle or life, storing the launch epoch to `gone` -- with the request in dynamic LDS after the
-// evaluator's and at most wide_row_max_rows(LH) rows per request.
+// the resident server for these networks (sdf_server_loop, sdf_row_dev.h): request and results in dynamic
+// LDS after the evaluator's, at most wide_row_max_rows(LH) rows per request
 __global__ __launch_bounds__(WT) void sdf_server_wide_kernel(WideRowArgs A, SdfMbox* mb, long long idle, long long life,
                                                              unsigned long long epoch) {
     extern __shared__ __align__(16) float lds_w[];
-    float* s_in = lds_w + row_lds_floats(A);
+    float* s_in = lds_w + row_lds_floats(A.w);
     float* s_out = s_in + SDF_MBOX_FLOATS;
-    __shared__ unsigned long long s_seq;
-    __shared__ int s_go, s_rows, s_grad;
-    const long long t0 = wall_clock64();
-    long long last = t0;
-    unsigned long long done = 0;
-    const int LH = A.LH, max_rows = SDF_MBOX_FLOATS / (4 + LH) < SDF_ROW_MAX ? SDF_MBOX_FLOATS / (4 + LH) : SDF_ROW_MAX;
-    if (threadIdx.x == 0) done = mbw_load(&mb->seq_out);
-    for (;;) {
-        if (threadIdx.x == 0) {
-            int go = 0;
-            unsigned long long q = done;
-            for (;;) {
-                q = mbw_load(&mb->seq_in);
-                if (q != done) {
-                    go = 1;
-                    break;
-                }
-                const long long now = wall_clock64();
-                if (mbw_load(&mb->stop) || now - last > idle || now - t0 > life) break;
-                __builtin_amdgcn_s_sleep(2);
-            }
-            s_go = go;
-            s_seq = q;
-            if (go) {
-                const int rows = (int)mbw_load_u32((const unsigned int*)&mb->rows);
-                s_rows = rows < 1 ? 1 : (rows > max_rows ? max_rows : rows);
-                s_grad = (int)mbw_load_u32((const unsigned int*)&mb->grad);
-            }
-        }
-        __syncthreads();
-        if (!s_go) {
-            if (threadIdx.x == 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(&mb->gone, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            break;
-        }
-        const long long t_seen = wall_clock64();
-        const int rows = s_rows;
-        for (int i = threadIdx.x; i < rows * (4 + LH); i += WT)
-            s_in[i] = __uint_as_float(mbw_load_u32((const unsigned int*)mb->in + i));
-        __syncthreads();
-        const long long t_staged = wall_clock64();
-        WideRowArgs B = A;
-        B.pos = (const float4*)s_in;
-        B.latent = s_in + rows * 4;
-        B.out = (float4*)s_out;
-        B.grad_latent = s_grad ? s_out + rows * 4 : nullptr;
-        B.rows = rows;
-        for (int r = 0; r < rows; ++r) row_eval_wide(B, r, lds_w);
-        const long long t_done = wall_clock64();
-        for (int i = threadIdx.x; i < rows * (s_grad ? 4 + LH : 4); i += WT)
-            __hip_atomic_store((unsigned int*)mb->out + i, __float_as_uint(s_out[i]), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(&mb->t_seen, t_seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&mb->t_staged, t_staged, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&mb->t_done, t_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(&mb->seq_out, s_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            done = s_seq;
-        }
-        last = wall_clock64();
-    }
+    sdf_server_loop<WT>(mb, idle, life, epoch, s_in, s_out, A.w.LH, wide_row_max_rows(A.w.LH), [&](int rows, int grad) {
+        const RowCall c = staged_call(s_in, s_out, rows, grad);
+        for (int r = 0; r < rows; ++r) row_eval_wide(A.w, c, r, lds_w);
+    });
 }
 
 // the dynamic-LDS limit of a kernel, raised once to the largest size asked for so far (the launches on the
@@ -344,25 +217,20 @@ static hipError_t raise_lds(const void* k, size_t bytes, std::atomic<size_t>& se
     return e;
 }
 
-size_t wide_row_lds_bytes(const WideRowArgs& a) { return row_lds_floats(a) * sizeof(float); }
-
-int wide_row_max_rows(int LH) {
-    const int n = SDF_MBOX_FLOATS / (4 + LH);
-    return n < SDF_ROW_MAX ? n : SDF_ROW_MAX;
-}
+size_t wide_row_lds_bytes(const WideDev& a) { return row_lds_floats(a) * sizeof(float); }
 
 hipError_t launch_sdf_row_wide(const WideRowArgs& a, hipStream_t s) {
-    if (a.rows <= 0) return hipSuccess;
-    const size_t lds = wide_row_lds_bytes(a);
+    if (a.c.rows <= 0) return hipSuccess;
+    const size_t lds = wide_row_lds_bytes(a.w);
     hipError_t e = raise_lds((const void*)sdf_row_wide_kernel, lds, lds_row_set);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sdf_row_wide_kernel, dim3((unsigned)a.rows), dim3(WT), lds, s, a);
+    hipLaunchKernelGGL(sdf_row_wide_kernel, dim3((unsigned)a.c.rows), dim3(WT), lds, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_sdf_server_wide(const WideRowArgs& a, SdfMbox* mb_dev, long long idle_ticks, long long life_ticks,
                                   unsigned long long epoch, hipStream_t s) {
-    const size_t lds = wide_row_lds_bytes(a) + 2 * SDF_MBOX_FLOATS * sizeof(float);
+    const size_t lds = wide_row_lds_bytes(a.w) + 2 * SDF_MBOX_FLOATS * sizeof(float);
     hipError_t e = raise_lds((const void*)sdf_server_wide_kernel, lds, lds_srv_set);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sdf_server_wide_kernel, dim3(1), dim3(WT), lds, s, a, mb_dev, idle_ticks, life_ticks, epoch);
