@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 6
+#define SDFNMPC_ABI_VERSION 7
 
 enum {
     SDFNMPC_OK = 0,
@@ -67,7 +67,7 @@ typedef struct sdfnmpc_net sdfnmpc_net;
 #define SDFNMPC_NHN_MAX 8      /* terminal constraint rows (soft <= 3, hard <= 6) */
 #define SDFNMPC_NHE 6          /* terminal extra functions hE (sdfnmpc_lin_args) */
 
-/* 'att' model constants (model/quad_rollpitchyawrate.py; config robot.limits / sensor / mpc) and the
+/* 'att' / 'att_tau' model constants (model/quad_rollpitchyawrate.py; config robot.limits / sensor / mpc) and the
  * terminal ingredients of flags.recursive_feasibility / flags.stability (gen_model.py:72-149) */
 typedef struct {
     double gamma, roll, pitch, wz; /* robot.limits.{gamma, roll, pitch, wz}: u -> physical inputs */
@@ -82,7 +82,16 @@ typedef struct {
     int poly_deg;                  /* braking-distance polynomial degree (mpc.braking_dist.degree, <= 6) */
     double poly[SDFNMPC_POLY_MAX]; /* its coefficients in polynomial_3variate's term order (utils/math.py:
                                       307-314: total degree 0..deg, then x exponent a, then y exponent b) */
+    int kind;                      /* mpc.model: SDFNMPC_MODEL_ATT (0) or SDFNMPC_MODEL_ATT_TAU (1, model/
+                                      quad_rollpitchyawrate_tau.py: roll and pitch follow their commands with a
+                                      first-order lag; same dimensions, residual layout and bounds).  Any other
+                                      value, and kind 1 with rec_feas or stability (gen_model.py:74: "only for
+                                      'att'"), is refused with SDFNMPC_E_UNSUPPORTED */
+    double tau_roll, tau_pitch;    /* kind 1: the lags' time constants in seconds, > 0 (the reference's 0.12) */
 } sdfnmpc_quad_model;
+
+#define SDFNMPC_MODEL_ATT 0
+#define SDFNMPC_MODEL_ATT_TAU 1
 
 /* Batched preparation phase: B instances x (N+1) shooting nodes, fp64, row-major C arrays.
  * Jacobian blocks are column-major (column j contiguous), j over (x[0..9], u[0..3]). */

@@ -54,7 +54,12 @@ class QuadModelC(C.Structure):
     _fields_ = [("gamma", C.c_double), ("roll", C.c_double), ("pitch", C.c_double), ("wz", C.c_double),
                 ("g", C.c_double), ("B_p_C", C.c_double * 3), ("B_R_C", C.c_double * 9),
                 ("fov_const_offset", C.c_double), ("rec_feas", C.c_int), ("stability", C.c_int),
-                ("poly_deg", C.c_int), ("poly", C.c_double * POLY_MAX)]
+                ("poly_deg", C.c_int), ("poly", C.c_double * POLY_MAX), ("kind", C.c_int),
+                ("tau_roll", C.c_double), ("tau_pitch", C.c_double)]
+
+
+MODEL_KINDS = {"att": 0, "att_tau": 1}  # SDFNMPC_MODEL_ATT, SDFNMPC_MODEL_ATT_TAU
+TAU_ROLL = TAU_PITCH = 0.12  # quad_rollpitchyawrate_tau.py:19-20
 
 
 LIN_PTRS = ("x", "u", "p", "dt", "xn", "AB", "y", "Jy", "yN", "JyN", "h", "Jh", "sdf")
@@ -185,7 +190,7 @@ def load():
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 6:
+    if lib.sdfnmpc_abi_version() != 7:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -382,12 +387,21 @@ class Net:
 
 def quad_model(cfg, model=None) -> QuadModelC:
     """Model constants of a config; ``model`` (model.Quad) adds the terminal extras of its flags
-    (recursive_feasibility: the braking polynomial; stability)."""
+    (recursive_feasibility: the braking polynomial; stability).  The kind follows cfg.mpc.model ('att' 0,
+    'att_tau' 1 with the lags' time constants: the model's, else the reference's 0.12 s)."""
     lim = cfg.robot.limits
+    name = str(cfg.mpc.get("model", "att"))
+    if name not in MODEL_KINDS:
+        from .model import UnsupportedConfig
+        raise UnsupportedConfig(f"mpc.model '{name}': only {sorted(MODEL_KINDS)} are built")
     R = np.asarray(cfg.sensor.B_R_C, dtype=np.float64).ravel()
     m = QuadModelC(float(lim.gamma), float(lim.roll), float(lim.pitch), float(lim.wz), 9.81,
                    (C.c_double * 3)(*[float(v) for v in cfg.sensor.B_p_C]), (C.c_double * 9)(*R),
                    float(cfg.mpc.fov_const_offset))
+    m.kind = MODEL_KINDS[name]
+    if m.kind == 1:
+        m.tau_roll = float(getattr(model, "tau_roll", TAU_ROLL))
+        m.tau_pitch = float(getattr(model, "tau_pitch", TAU_PITCH))
     if model is not None:
         m.rec_feas, m.stability = int(model.rec_feas), int(model.stability)
         m.poly_deg = int(model.poly_deg)
@@ -410,7 +424,7 @@ def linearize(ctx: Context, net, model: QuadModelC, B: int, N: int, np_: int, bu
 
 
 def qp_opts(model, lm=10.0, cost_scaling=True, max_iter=100, tol=1e-8, lm_scaling=True, warm_start=False) -> QpOptsC:
-    """QP data of the 'att' model (model.Quad: bounds, the constraint set of its flags) + solver options
+    """QP data of the 'att' / 'att_tau' model (model.Quad: bounds, the constraint set of its flags) + solver options
     (ocp.py:113-120 defaults).  lm_scaling: the Levenberg-Marquardt term is lm dt_k at stages k < N and lm at
     N (acados' Ts-scaled term).  warm_start: HPIPM's primal warm start (ocp.py:116) -- the IPM starts from
     the du buffer's entry values."""

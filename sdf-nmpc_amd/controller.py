@@ -18,8 +18,8 @@ they touched; ``solve`` uploads exactly those regions.  Device-side setters (``g
 the host marks of what they wrote.  The last writer of a region wins, whichever side it is on.
 No tensor library is used on this path.
 
-``get_cmd_props`` exists in the reference only for the 'props' model; this build is the 'att' model
-(model.Quad), where the reference raises AttributeError too.
+``get_cmd_props`` exists in the reference only for the 'props' model; this build is the 'att' and 'att_tau'
+models (model.Quad, cfg.mpc.model), where the reference raises AttributeError too.
 """
 from __future__ import annotations
 

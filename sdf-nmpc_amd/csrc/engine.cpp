@@ -1293,6 +1293,14 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
 static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad_model* mdl,
                     const sdfnmpc_lin_args* a, const QpArgs* pk, bool* split_out = nullptr) {
     if (!ctx || !mdl || !a) return fail(SDFNMPC_E_ARG, "NULL argument");
+    if (mdl->kind != SDFNMPC_MODEL_ATT && mdl->kind != SDFNMPC_MODEL_ATT_TAU)
+        return fail(SDFNMPC_E_UNSUPPORTED, "model.kind: only 0 ('att') and 1 ('att_tau') are built");
+    if (mdl->kind == SDFNMPC_MODEL_ATT_TAU) {
+        if (mdl->rec_feas || mdl->stability)  // gen_model.py:74: implemented only for 'att'
+            return fail(SDFNMPC_E_UNSUPPORTED, "model.kind 1 ('att_tau') with rec_feas / stability");
+        if (!(mdl->tau_roll > 0.0) || !(mdl->tau_pitch > 0.0))
+            return fail(SDFNMPC_E_ARG, "model.kind 1 ('att_tau') needs tau_roll > 0 and tau_pitch > 0");
+    }
     const bool no_sdf = a->no_sdf != 0;
     if (!net && !no_sdf) return fail(SDFNMPC_E_ARG, "NULL network (only allowed with lin_args.no_sdf)");
     if (a->B < 0 || a->N < 1 || a->np < 17 + (net ? net->host.L : 0) || (a->latent_mode != 0 && a->latent_mode != 1))
@@ -1334,6 +1342,11 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
     la.m.stability = mdl->stability ? 1 : 0;
     la.m.poly_deg = mdl->poly_deg;
     for (int i = 0; i < SDFNMPC_POLY_MAX; ++i) la.m.poly[i] = mdl->poly[i];
+    la.m.kind = mdl->kind;
+    if (mdl->kind == SDFNMPC_MODEL_ATT_TAU) {
+        la.m.itau_roll = 1.0 / mdl->tau_roll;
+        la.m.itau_pitch = 1.0 / mdl->tau_pitch;
+    }
     la.hE = a->hE;
     la.JhE = a->JhE;
     la.nyN = nyN;

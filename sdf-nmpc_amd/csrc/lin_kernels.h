@@ -4,7 +4,8 @@
 
 namespace sdfn {
 
-// 'att' quadrotor model constants (quad_rollpitchyawrate.py, default.yaml robot.limits / sensor)
+// quadrotor model constants: 'att' (quad_rollpitchyawrate.py) and 'att_tau' (quad_rollpitchyawrate_tau.py);
+// default.yaml robot.limits / sensor
 struct QuadModel {
     double gamma, roll, pitch, wz;  // input scalings u -> (thrust/m, roll, pitch, yaw rate)
     double g;                       // 9.81 (base_model.py:10)
@@ -14,6 +15,8 @@ struct QuadModel {
     int rec_feas, stability;        // terminal extras (include/sdfnmpc.h sdfnmpc_quad_model)
     int poly_deg;                   // braking-distance polynomial (utils/math.py:294-321)
     double poly[84];
+    int kind;                       // 0 'att', 1 'att_tau' (sdfnmpc_quad_model.kind): which linearize_kernel runs
+    double itau_roll, itau_pitch;   // 'att_tau': 1 / tau of the roll and pitch lags
 };
 
 struct LinArgs {

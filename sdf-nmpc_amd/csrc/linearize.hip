@@ -7,7 +7,9 @@
 //           RK4 map); NONLINEAR_LS residual y_k (11) and J_y (11 x 14)
 //   k = N : terminal residual y_N (4) and J_yN (4 x 10)
 //   all k : h_k = [hfov, vfov, sdf] and J_h = d h / d x (3 x 10; d h / d u == 0)
-// Model: quad_rollpitchyawrate.py:19-55 ('att'), utils/math.py:7-54,169-192; constraints
+// Model: quad_rollpitchyawrate.py:19-55 ('att', QuadModel.kind 0), utils/math.py:7-54,169-192, or
+// quad_rollpitchyawrate_tau.py:19-58 ('att_tau', kind 1: roll and pitch follow their commands with a
+// first-order lag), utils/math.py:7-23,57-70,210-226; constraints
 // cost_const_helpers.py:48-75 (add_fov_const_trigo) and gen_model.py:46-70 (sdf with flag).
 //
 // Derivatives are forward-mode dual numbers with ONE tangent per lane: a node is served by 8 lanes,
@@ -102,6 +104,42 @@ __device__ __forceinline__ void quad_f(const QuadModel& m, const dd* x, dd gamma
     f[9] = r33 * b2 - C(m.g);
 }
 
+// f_expl of the 'att_tau' model (quad_rollpitchyawrate_tau.py:23-43): the attitude is the state's
+// quaternion, and roll / pitch approach their commands at the rates (cmd - angle) / tau.
+//   q = x[3:7] / |x[3:7]|;  eta = quat2euler(q):  roll = atan2(ay, ax), pitch = asin(sp) (math.py:62-63)
+//   w = deuler_avel_map(eta) [droll, dpitch, 0] (math.py:217-218; its row 1 is [0, cos(roll), -sin(pitch)],
+//       as the reference writes it),  dq = hamilton_prod(q, [0, w0, w1, wz]) / 2,  W_a = quat2rot(q) e_z gamma - g e_z
+// sin / cos of roll and 1 / cos(pitch) come from the atan2 / asin arguments (no trigonometric call):
+// (sin, cos)(roll) = (ay, ax) / |(ay, ax)|, cos(pitch) = sqrt((1 - sp)(1 + sp)).  The angles' values are
+// shared by the node's lanes: a lane pair splits them as atan2(ay, ax) and asin(sp) = atan2(sp, cos(pitch))
+// and swaps results.  No guard at |pitch| = pi / 2: the singularity is the reference's (NaN -> QP status 2).
+__device__ __forceinline__ void quad_f_tau(const QuadModel& m, const dd* x, dd gamma, dd roll_des, dd pitch_des, dd wz,
+                                           bool odd, dd* f) {
+    const dd inv = drsqrt(x[3] * x[3] + x[4] * x[4] + (x[5] * x[5] + x[6] * x[6]));
+    const dd q0 = x[3] * inv, q1 = x[4] * inv, q2 = x[5] * inv, q3 = x[6] * inv;
+    const dd ay = (q0 * q1 + q2 * q3) * 2.0, ax = C(1.0) - (q1 * q1 + q2 * q2) * 2.0;
+    const dd sp = (q0 * q2 - q3 * q1) * 2.0;
+    const dd cp2 = (C(1.0) - sp) * (C(1.0) + sp);
+    const dd icp = drsqrt(cp2);  // 1 / cos(pitch)
+    const dd rr = drsqrt(ax * ax + ay * ay);
+    const dd sr = ay * rr, cr = ax * rr;
+    const double at = atan2(odd ? sp.v : ay.v, odd ? cp2.v * icp.v : ax.v), atp = pair_swap(at);
+    const dd roll = datan2_v(ay, ax, odd ? atp : at);
+    const dd pitch = {odd ? at : atp, sp.t * icp.v};
+    const dd dr = (roll_des - roll) * m.itau_roll, dp = (pitch_des - pitch) * m.itau_pitch;
+    const dd w0 = dr + ((sp * sr) * icp) * dp, w1 = cr * dp;
+    f[0] = x[7];
+    f[1] = x[8];
+    f[2] = x[9];
+    f[3] = (-(q1 * w0) - q2 * w1 - q3 * wz) * 0.5;
+    f[4] = (q0 * w0 + q2 * wz - q3 * w1) * 0.5;
+    f[5] = (q0 * w1 - q1 * wz + q3 * w0) * 0.5;
+    f[6] = (q0 * wz + q1 * w1 - q2 * w0) * 0.5;
+    f[7] = ((q1 * q3 + q0 * q2) * 2.0) * gamma;
+    f[8] = ((q2 * q3 - q0 * q1) * 2.0) * gamma;
+    f[9] = (q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3) * gamma - C(m.g);
+}
+
 // (q_d (x) invert(q))[3] with q = x[3:7]/|x[3:7]| (|q| = 1 up to rounding): quad_rollpitchyawrate.py:48-51
 __device__ __forceinline__ dd qerr3(const dd* x, const double* qd) {
     const dd inv = drsqrt(x[3] * x[3] + x[4] * x[4] + (x[5] * x[5] + x[6] * x[6]));
@@ -117,6 +155,10 @@ __device__ __forceinline__ dd qerr3(const dd* x, const double* qd) {
 // RK4 accumulation's order; J_y: unit columns) and the lanes carry the eight others: slot s -> direction
 // q_{s} (s < 4) or u_{s-4}.  The fov rows of J_h depend on the position only: slots 0..2 seed p_s there.
 // The terminal node (all ten directions of x) takes two passes.
+// KIND = QuadModel.kind: 'att_tau' (1) has the same constant columns -- its f_expl does not depend on the
+// position either, and on the velocity only through f[0:3] = v -- and the same residual layout, with
+// W_a[2] (a function of q there) taken from the first RK4 stage as well.
+template <int KIND>
 __global__ __launch_bounds__(256, LIN_WAVES) void linearize_kernel(LinArgs A) {
     const int tid = threadIdx.x;
     const int sl = tid & 7;                           // lane slot within the node
@@ -142,8 +184,8 @@ __global__ __launch_bounds__(256, LIN_WAVES) void linearize_kernel(LinArgs A) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) U[i] = {ur[i], (10 + i == t) ? 1.0 : 0.0};
         const dd gamma = U[0] * m.gamma, roll = U[1] * m.roll, pitch = U[2] * m.pitch, wz = U[3] * m.wz;
-        double s_r, c_r, s_p, c_p;
-        {  // the node's lanes share roll and pitch: a lane pair splits the two sincos and swaps results
+        double s_r = 0.0, c_r = 0.0, s_p = 0.0, c_p = 0.0;
+        if constexpr (KIND == 0) {  // the node's lanes share roll and pitch: a lane pair splits the two sincos and swaps results
             const bool odd = sl & 1;
             double sa, ca;
             sincos(odd ? pitch.v : roll.v, &sa, &ca);
@@ -155,12 +197,18 @@ __global__ __launch_bounds__(256, LIN_WAVES) void linearize_kernel(LinArgs A) {
         }
         const dd sr = {s_r, c_r * roll.t}, cr = {c_r, -s_r * roll.t};
         const dd sp = {s_p, c_p * pitch.t}, cp = {c_p, -s_p * pitch.t};
+        auto f_expl = [&](const dd* xs, dd* f) {
+            if constexpr (KIND == 0)
+                quad_f(m, xs, gamma, sr, cr, sp, cp, wz, f);
+            else
+                quad_f_tau(m, xs, gamma, roll, pitch, wz, sl & 1, f);
+        };
         // ---- ERK4 (Butcher c = [0, 1/2, 1/2, 1], b = [1/6, 1/3, 1/3, 1/6]); acados-style
         //      accumulation x_out = x + (h b_1) k_1 + ... + (h b_4) k_4, stage input x + (h a_s) k_{s-1}
         const double dt = A.dt[k];
         const double hb[4] = {dt / 6, dt / 3, dt / 3, dt / 6}, ha[4] = {0.0, dt / 2, dt / 2, dt};
         dd xo[10], kk[10], tmp[10];
-        quad_f(m, X, gamma, sr, cr, sp, cp, wz, kk);
+        f_expl(X, kk);
         const dd W_a2 = kk[9];
 #pragma unroll
         for (int i = 0; i < 10; ++i) xo[i] = X[i] + kk[i] * hb[0];
@@ -168,7 +216,7 @@ __global__ __launch_bounds__(256, LIN_WAVES) void linearize_kernel(LinArgs A) {
         for (int st = 1; st < 4; ++st) {
 #pragma unroll
             for (int i = 0; i < 10; ++i) tmp[i] = X[i] + kk[i] * ha[st];
-            quad_f(m, tmp, gamma, sr, cr, sp, cp, wz, kk);
+            f_expl(tmp, kk);
 #pragma unroll
             for (int i = 0; i < 10; ++i) xo[i] = xo[i] + kk[i] * hb[st];
         }
@@ -303,7 +351,11 @@ __global__ __launch_bounds__(256, LIN_WAVES) void linearize_kernel(LinArgs A) {
 hipError_t launch_linearize(const LinArgs& a, hipStream_t s) {
     const long long rows = (long long)a.B * (a.N + 1);
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(linearize_kernel, dim3((unsigned)((rows + 31) / 32)), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((rows + 31) / 32));
+    if (a.m.kind == 1)
+        hipLaunchKernelGGL(linearize_kernel<1>, grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL(linearize_kernel<0>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -174,6 +174,11 @@ extern "C" int sdfnmpc_solver_create(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, c
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "solver opts: B, N >= 1, np >= 17, ny in {11, 12} == qp.ny, dt required");
     if (o->qp.nyN != 4 && o->qp.nyN != 5)
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "solver opts: qp.nyN must be 4 or 5");
+    // the model kinds the preparation phase is built for (sdfnmpc_quad_model.kind), refused here and not at the first step
+    if (o->model.kind != SDFNMPC_MODEL_ATT && o->model.kind != SDFNMPC_MODEL_ATT_TAU)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_UNSUPPORTED, "solver opts: model.kind: only 0 ('att') and 1 ('att_tau') are built");
+    if (o->model.kind == SDFNMPC_MODEL_ATT_TAU && (o->model.rec_feas || o->model.stability))
+        return sdfnmpc_solver_fail_(SDFNMPC_E_UNSUPPORTED, "solver opts: model.kind 1 ('att_tau') with rec_feas / stability");
     bool need_sdf = o->ny == 12;  // the constraint set or the cost reads the network
     for (int j = 0; j < o->qp.nh && j < 3; ++j) need_sdf = need_sdf || o->qp.h_col[j] == 2;
     for (int j = 0; j < o->qp.nhN && j < SDFNMPC_NHN_MAX; ++j) need_sdf = need_sdf || o->qp.hN_col[j] == 2;

@@ -1,4 +1,4 @@
-"""The default 'att' (roll/pitch/yaw-rate) quadrotor OCP: dimensions, bounds, reference layout.
+"""The 'att' (roll/pitch/yaw-rate, the default) and 'att_tau' quadrotor OCPs: dimensions, bounds, reference layout.
 
 Host-side description only -- the arithmetic (dynamics, residuals, constraints and their Jacobians)
 runs in csrc/linearize.hip and csrc/sdf_mlp.hip.  Mirrors (paths relative to the reference checkout):
@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 
 G = 9.81  # model/base_model.py:10
+MODELS = ("att", "att_tau")  # the mpc.model values built, of gen_model.py:15-20's acc, att, att_tau, rates, wrench, props
 
 
 class UnsupportedConfig(ValueError):
@@ -105,8 +106,11 @@ def _slack(v):
 
 
 class Quad:
-    """'att' model + the constraint set gen_model.get_model_from_cfg builds from the flags
-    (gen_model.py:26-149, cost_const_helpers.py:48-102, quad_rollpitchyawrate.py:48-55).
+    """'att' or 'att_tau' model (cfg.mpc.model; kind) + the constraint set gen_model.get_model_from_cfg builds
+    from the flags (gen_model.py:26-149, cost_const_helpers.py:48-102, quad_rollpitchyawrate.py:48-55).
+    'att_tau' (quad_rollpitchyawrate_tau.py) is 'att' with roll and pitch following their commands through a
+    first-order lag (tau_roll, tau_pitch): the same dimensions, residual layout, bounds and formate_ref, its own
+    dynamics in csrc/linearize.hip, and no recursive feasibility / stability (gen_model.py:74).
 
     Node functions (fixed columns of the preparation phase's h / J_h): 0 hfov, 1 vfov, 2 sdf.
     Stage rows (in the order the reference adds them): hfov if sensor.hfov < 3.14, vfov if
@@ -124,11 +128,17 @@ class Quad:
         self.cfg = cfg
         self.name = "quad_rollpitchyawrate"
         fl = cfg.flags
-        if cfg.mpc.model != "att":
-            # gen_model.py:74 asserts on cfg.control_mode (undefined in Config); this build
-            # is the 'att' model only (default model)
-            raise UnsupportedConfig(f"mpc.model '{cfg.mpc.model}': only 'att' is built (SURVEY.md §8: default model)")
+        if cfg.mpc.model not in MODELS:
+            raise UnsupportedConfig(f"mpc.model '{cfg.mpc.model}': only {', '.join(MODELS)} are built (SURVEY.md §8)")
+        self.kind = cfg.mpc.model
+        if self.kind == "att_tau":  # quad_rollpitchyawrate_tau.py:19-20
+            self.tau_roll = self.tau_pitch = 0.12
         E = bool(fl.get("enable_sdf"))
+        if self.kind != "att" and E and bool(fl.get("recursive_feasibility")):
+            # gen_model.py:74 (the assert reads cfg.control_mode, undefined in Config; its
+            # message is the intent): recursive feasibility and stability are implemented only for 'att'
+            raise UnsupportedConfig(f"mpc.model '{self.kind}' with flags.recursive_feasibility: implemented only for "
+                                    "'att' (gen_model.py:74)")
         H = E and cfg.sensor.hfov < 3.14
         V = E and bool(fl.get("vfov_constraint"))
         S = E and bool(fl.get("sdf_constraint"))
@@ -223,10 +233,13 @@ class Quad:
         x = np.asarray(x, dtype=float)
         gamma, roll, pitch, wz = self._att(u)
         q = x[..., 3:7] / np.linalg.norm(x[..., 3:7], axis=-1, keepdims=True)
-        th = np.arctan2(q[..., 3], q[..., 0])
-        W_R_V = quat2rot(np.stack([np.cos(th), 0 * th, 0 * th, np.sin(th)], axis=-1))
-        V_R_B = euler2rot_b(roll, pitch, 0 * roll)
-        W_R_B = W_R_V @ V_R_B
+        if self.kind == "att_tau":  # quad_rollpitchyawrate_tau.py:33,47: the attitude is the state's
+            W_R_B = quat2rot(q)
+        else:
+            th = np.arctan2(q[..., 3], q[..., 0])
+            W_R_V = quat2rot(np.stack([np.cos(th), 0 * th, 0 * th, np.sin(th)], axis=-1))
+            V_R_B = euler2rot_b(roll, pitch, 0 * roll)
+            W_R_B = W_R_V @ V_R_B
         W_a = W_R_B[..., :, 2] * gamma[..., None] - np.array([0.0, 0.0, self.g])
         acc = np.einsum("...ji,...j->...i", W_R_B, W_a)
         return np.concatenate([acc, wz[..., None]], axis=-1)
