@@ -35,6 +35,10 @@
  *                                      solve_for_x0 (ocp.py:169) -> _step + _wait.  It owns the device
  *                                      workspace of B instances, so a controller needs no tensor library
  *
+ *   sdfnmpc_colcheck                   ColChecker.check_image_points (utils/collision_checker.py:23-125)
+ *   sdfnmpc_udf / sdfnmpc_sdf_truth    DfComputer.get_udf / get_sdf (utils/df_computer.py:85-221): the distance
+ *                                      field the image itself implies, to label data and to score a network
+ *
  * The CasADi external-function symbols that acados links (sdf_l4c, jac_sdf_l4c, ...) are in
  * sdf_l4c.h / libsdf_l4c.so.
  */
@@ -48,7 +52,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 7
+#define SDFNMPC_ABI_VERSION 8
 
 enum {
     SDFNMPC_OK = 0,
@@ -378,6 +382,45 @@ int sdfnmpc_vae_size_latent(const sdfnmpc_vae* vae);
  * is owned by the encoder object and grows with B. */
 int sdfnmpc_vae_encode(sdfnmpc_ctx* ctx, sdfnmpc_vae* vae, const sdfnmpc_vae_opts* opts, const void* img,
                        float* latent, double* latent64);
+
+/* ---- ground truth from range images (csrc/df_truth.hip) ----
+ * What the image itself says about a point: the reference's Warp kernels ColChecker._kernel_colcheck
+ * (utils/collision_checker.py:23-90) and DfComputer._kernel_pixel_wise_udf / get_sdf (utils/df_computer.py:
+ * 85-221), restated as written in fp32.  img: device [n_img][H][W] float32, normalised by dmax; points: device
+ * [n][3] float32, unnormalised camera-frame coordinates; p_to_i: device [n] int32, the image of each point, or
+ * NULL for the reference's default ordering, point j -> image j / (n / n_img) (n must then be a multiple of
+ * n_img).  The entries of p_to_i must lie in [0, n_img): they are the caller's responsibility and are not
+ * checked on the device.  Launches are ordered on the context stream; n == 0 is a no-op.  SDFNMPC_E_ARG (nothing
+ * is launched, outputs untouched): outside not 0 / 1 / 2, non-positive dmax / hfov / vfov, n_img <= 0, H or W
+ * < 1, NULL p_to_i with n % n_img != 0, n < 0 or beyond 2^31 - 1, and for sdfnmpc_udf an H or W that is not a
+ * multiple of 5. */
+typedef struct {
+    float dmax, hfov, vfov;      /* sensor.dmax, half fields of view in radians */
+    int is_depth, is_spherical;  /* pixel value is depth (x) instead of range; spherical pixel coordinates */
+} sdfnmpc_img_opts;
+
+/* out[j] = 1 where point j collides: farther than its pixel, or past dmax; 0 inside the safe ball.  outside:
+ * what holds beyond the field of view -- 0 free, 1 collision, 2 extrapolate (angles clamped to the border). */
+int sdfnmpc_colcheck(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* opts, int outside, float safe_ball, const float* img,
+                     int n_img, int H, int W, const float* points, const int* p_to_i, long long n,
+                     unsigned char* out);
+/* Unsigned distance to the nearest pixel of the 5x5 min-pooled image (zeros skipped) or to the virtual wall at
+ * dmax, clamped to [0, max_df]; grad [n][3] = minus the unit direction to that pixel, 0 where udf == max_df;
+ * pix_idx [n] (may be NULL) = the pooled pixel chosen (row-major, ties to the lowest index).  The pooled image
+ * lives in a workspace of the context. */
+int sdfnmpc_udf(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* opts, float max_df, const float* img, int n_img, int H,
+                int W, const float* points, const int* p_to_i, long long n, float* udf, float* grad, int* pix_idx);
+/* Signed distance over a voxel grid around each point (grid [G][3] offsets, dist [G] their norms, device
+ * float32): the sign is the point's collision label (mode extrapolate, safe ball 0); a voxel counts when its own
+ * label differs from the point's; sdf = clamp(sign * min dist over counting voxels (max_df if none), min_df,
+ * max_df); grad [n][3] = -sign * grid[g] / |grid[g]| of that voxel g, 0 where sdf equals either clamp; ties go to
+ * the lowest voxel index; vox_idx [n] (may be NULL) = g, -1 where no voxel counts.  orig_idx NULL: the grid in any
+ * order, every voxel visited.  orig_idx [G] (device int32): the grid sorted by dist ascending, orig_idx the
+ * voxel's index before sorting (ties are decided on it and vox_idx reports it); the scan then stops early.  Both
+ * give bitwise the same outputs. */
+int sdfnmpc_sdf_truth(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* opts, float min_df, float max_df, const float* grid,
+                      const float* dist, const int* orig_idx, int G, const float* img, int n_img, int H, int W,
+                      const float* points, const int* p_to_i, long long n, float* sdf, float* grad, int* vox_idx);
 
 /* ---- device memory on a context (inputs of the device-side setters without a tensor library) ----
  * memcpy kind: 1 host -> device, 2 device -> host, 3 device -> device; ordered on the context stream,

@@ -31,6 +31,7 @@ SYMBOLS = [
     "sdfnmpc_linearize", "sdfnmpc_shooting_grid", "sdfnmpc_qp_solve", "sdfnmpc_rti_prepare", "sdfnmpc_qp_feedback",
     "sdfnmpc_rti_apply", "sdfnmpc_step_create", "sdfnmpc_step_launch", "sdfnmpc_step_destroy", "sdfnmpc_pack_refs",
     "sdfnmpc_vae_load", "sdfnmpc_vae_free", "sdfnmpc_vae_size_latent", "sdfnmpc_vae_encode",
+    "sdfnmpc_colcheck", "sdfnmpc_udf", "sdfnmpc_sdf_truth",
     "sdfnmpc_ctx_device", "sdfnmpc_dev_alloc", "sdfnmpc_dev_free", "sdfnmpc_memcpy",
     "sdfnmpc_solver_create", "sdfnmpc_solver_destroy", "sdfnmpc_solver_field", "sdfnmpc_solver_upload",
     "sdfnmpc_solver_download", "sdfnmpc_solver_init", "sdfnmpc_solver_shift", "sdfnmpc_solver_step",
@@ -106,6 +107,11 @@ class VaeOptsC(C.Structure):
                 ("yz", C.c_void_p)]
 
 
+class ImgOptsC(C.Structure):
+    _fields_ = [("dmax", C.c_float), ("hfov", C.c_float), ("vfov", C.c_float), ("is_depth", C.c_int),
+                ("is_spherical", C.c_int)]
+
+
 class SolverOptsC(C.Structure):
     _fields_ = [("B", C.c_int), ("N", C.c_int), ("np", C.c_int), ("ny", C.c_int), ("latent_mode", C.c_int),
                 ("dt", C.POINTER(C.c_double)), ("model", QuadModelC), ("qp", QpOptsC)]
@@ -173,6 +179,9 @@ def load():
         "sdfnmpc_vae_free": (None, [vp]),
         "sdfnmpc_vae_size_latent": (i, [vp]),
         "sdfnmpc_vae_encode": (i, [vp, vp, P(VaeOptsC), vp, vp, vp]),
+        "sdfnmpc_colcheck": (i, [vp, P(ImgOptsC), i, f, vp, i, i, i, vp, vp, ll, vp]),
+        "sdfnmpc_udf": (i, [vp, P(ImgOptsC), f, vp, i, i, i, vp, vp, ll, vp, vp, vp]),
+        "sdfnmpc_sdf_truth": (i, [vp, P(ImgOptsC), f, f, vp, vp, vp, i, vp, i, i, i, vp, vp, ll, vp, vp, vp]),
         "sdfnmpc_ctx_device": (i, [vp]),
         "sdfnmpc_dev_alloc": (i, [vp, sz, P(vp)]),
         "sdfnmpc_dev_free": (None, [vp, vp]),
@@ -190,7 +199,7 @@ def load():
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 7:
+    if lib.sdfnmpc_abi_version() != 8:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -579,6 +588,41 @@ def vae_encode(ctx: Context, vae: Vae, opts: VaeOptsC, img, yz, latent, latent64
     o = VaeOptsC(int(img.shape[0]), int(img.shape[-2]), int(img.shape[-1]), 1 if "uint16" in str(img.dtype) else 0,
                  float(opts.clip), _ptr(yz) if depth2range else None)
     _check(load().sdfnmpc_vae_encode(ctx.h, vae.h, C.byref(o), _ptr(img), _ptr(latent), _ptr(latent64)))
+
+
+# ---- ground truth from range images (csrc/df_truth.hip) ----
+OUTSIDE = {"free": 0, "col": 1, "extrapolate": 2}  # collision_checker.py:18
+
+
+def img_opts(dmax, hfov, vfov, is_depth=False, is_spherical=False) -> ImgOptsC:
+    return ImgOptsC(float(dmax), float(hfov), float(vfov), int(bool(is_depth)), int(bool(is_spherical)))
+
+
+def _img_dims(img):
+    n_img, H, W = (int(v) for v in img.shape)
+    return _ptr(img), n_img, H, W
+
+
+def colcheck(ctx: Context, opts: ImgOptsC, outside: int, safe_ball: float, img, points, p_to_i, out):
+    """Enqueue sdfnmpc_colcheck: img device float32 [n_img][H][W], points device float32 [n][3], p_to_i device
+    int32 [n] or None, out device uint8 [n]."""
+    _check(load().sdfnmpc_colcheck(ctx.h, C.byref(opts), int(outside), float(safe_ball), *_img_dims(img),
+                                   _ptr(points), _ptr(p_to_i), int(points.shape[0]), _ptr(out)))
+
+
+def udf(ctx: Context, opts: ImgOptsC, max_df: float, img, points, p_to_i, out_udf, out_grad, pix_idx=None):
+    """Enqueue sdfnmpc_udf: outputs device float32 [n], [n][3] and optionally int32 [n]."""
+    _check(load().sdfnmpc_udf(ctx.h, C.byref(opts), float(max_df), *_img_dims(img), _ptr(points), _ptr(p_to_i),
+                              int(points.shape[0]), _ptr(out_udf), _ptr(out_grad), _ptr(pix_idx)))
+
+
+def sdf_truth(ctx: Context, opts: ImgOptsC, min_df: float, max_df: float, grid, dist, orig_idx, img, points, p_to_i,
+              out_sdf, out_grad, vox_idx=None):
+    """Enqueue sdfnmpc_sdf_truth: grid device float32 [G][3], dist [G]; orig_idx device int32 [G] when the grid is
+    sorted by dist, else None (full scan)."""
+    _check(load().sdfnmpc_sdf_truth(ctx.h, C.byref(opts), float(min_df), float(max_df), _ptr(grid), _ptr(dist),
+                                    _ptr(orig_idx), int(dist.shape[0]), *_img_dims(img), _ptr(points), _ptr(p_to_i),
+                                    int(points.shape[0]), _ptr(out_sdf), _ptr(out_grad), _ptr(vox_idx)))
 
 
 class DeviceArray:

@@ -212,6 +212,47 @@ class Nmpc:
             out = np.concatenate([out, bd[:, None], (df - bd)[:, None]], axis=1)
         return out[0] if self.B == 1 else out
 
+    def check_openloop_traj(self, imgs, safe_ball_size=0.0, outside='col'):
+        """Collision labels of the predicted positions against the raw images the latents came from: the runtime
+        monitor behind mpc.allow_dead_reck ("if current position is unsafe"), one launch of the collision-check
+        kernel (csrc/df_truth.hip, the reference's utils/collision_checker.py) for the B x (N+1) nodes.
+
+        imgs: [B, H, W] (or [H, W] for one instance) float32, normalised by sensor.dmax: a host array, or a
+        device array used in place (DeviceArray or torch tensor, e.g. the images already there for the VAE in
+        config C5).  Node k of instance b is checked in the camera frame ``eval`` uses, Co_p = W_R_Co^T (x_k[:3]
+        - W_p_Co) with node k's parameters as the host setters left them (set_latent), against image b.
+        outside: what holds beyond the field of view ('col', 'free' or 'extrapolate').
+        Returns a numpy bool array [N+1], or [B, N+1] for a batch.  No tensor library is needed."""
+        from . import _lib
+        assert outside in _lib.OUTSIDE
+        s, idx, ctx = self.cfg.sensor, self.cfg.mpc.p_idx, self.ocp.ctx
+        Bn = max(self.B, 1)
+        if hasattr(imgs, "data_ptr"):
+            if np.dtype(str(imgs.dtype).replace("torch.", "")) != np.float32:
+                raise TypeError(f"device images must be float32, got {imgs.dtype}")
+            dimg = _lib.sync_producer(imgs)
+            shape = tuple(int(v) for v in imgs.shape)
+        else:
+            a = np.asarray(imgs, dtype=np.float32)
+            shape = a.shape
+            dimg = _lib.DeviceArray.from_numpy(ctx, a)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3:
+            raise AssertionError('input image must have size [B, H, W] or [H, W]')
+        if shape[0] != Bn:
+            raise ValueError(f"expected {Bn} images, got {shape[0]}")
+        x = self.ocp.download("x")
+        p = self.p if self.B > 1 else self.p[None]
+        W_R_Co = p[..., idx.W_R_Co].reshape(Bn, self.N + 1, 3, 3)
+        Co_p = np.einsum("bkji,bkj->bki", W_R_Co, x[..., :3] - p[..., idx.W_p_Co])
+        pts = _lib.DeviceArray.from_numpy(ctx, Co_p.reshape(-1, 3), dtype=np.float32)
+        out = _lib.DeviceArray(ctx, (pts.shape[0],), np.uint8)
+        _lib.colcheck(ctx, _lib.img_opts(s.dmax, s.hfov, s.vfov, s.is_depth, s.is_spherical), _lib.OUTSIDE[outside],
+                      safe_ball_size, _lib.FieldView(dimg.data_ptr(), shape, np.float32, ctx), pts, None, out)
+        lab = out.numpy().astype(bool)  # the copy waits for the launch; point j belongs to image j / (N+1)
+        return lab if self.B == 1 else lab.reshape(self.B, self.N + 1)
+
     # ---- device-side parameter packing (SURVEY.md §8(f) rank 3; csrc/ref_pack.hip)
     def _dev(self, a):
         """Host array -> device (fp64); a device array (DeviceArray / FieldView / torch tensor) passes through."""

@@ -24,6 +24,7 @@
 #include "ref_kernels.h"
 #include "sdf_kernels.h"
 #include "vae_kernels.h"
+#include "df_kernels.h"
 
 using namespace sdfn;
 
@@ -85,6 +86,7 @@ struct sdfnmpc_ctx {
     size_t lds_per_cu = 0;     // LDS bytes per CU (hipDeviceProp_t::maxSharedMemoryPerMultiProcessor)
     bool timing = false;
     DevBuf c13, sdf4, lat, out4, glat, qpw, qpst, wws;
+    DevBuf dfpool;  // sdfnmpc_udf: the 5x5 min-pooled images
     // host-pointer path (sdf_eval_host, the CasADi external): pinned staging, its own hoist buffer and
     // the latents it was computed for (consecutive acados calls share one latent: the hoist is reused)
     float* h_pin = nullptr;
@@ -1996,5 +1998,87 @@ extern "C" int sdfnmpc_vae_encode(sdfnmpc_ctx* ctx, sdfnmpc_vae* v, const sdfnmp
     }
     VaeHeadArgs ha{X, xps, F, v->head.w, v->head.b, latent, latent64, B, h, w, v->L};
     HIPCHK(timed(ctx, "vae_head", [&] { return launch_vae_head(ha, st); }));
+    return SDFNMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ground truth from range images (df_truth.hip)
+static int df_img_args(const char* who, sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* o, const float* img, int n_img, int H,
+                       int W, const float* points, const int* p_to_i, long long n, DfImg* im) {
+    const std::string w(who);
+    if (!ctx || !o) return fail(SDFNMPC_E_ARG, w + ": NULL context or options");
+    if (!(o->dmax > 0.f) || !(o->hfov > 0.f) || !(o->vfov > 0.f))
+        return fail(SDFNMPC_E_ARG, w + ": dmax, hfov and vfov must be positive");
+    if (n_img <= 0 || H < 1 || W < 1) return fail(SDFNMPC_E_ARG, w + ": bad image count or size");
+    if (n < 0 || n > 2147483647LL) return fail(SDFNMPC_E_ARG, w + ": n out of range");
+    if (!p_to_i && n % n_img != 0)
+        return fail(SDFNMPC_E_ARG, w + ": without p_to_i the points must divide evenly among the images");
+    if (n > 0 && (!img || !points)) return fail(SDFNMPC_E_ARG, w + ": NULL image or points");
+    *im = DfImg{img, n_img, H, W, o->dmax, o->hfov, o->vfov, o->is_depth != 0, o->is_spherical != 0,
+                points, p_to_i, n, std::max(1LL, n / n_img)};
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_colcheck(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* o, int outside, float safe_ball,
+                                const float* img, int n_img, int H, int W, const float* points, const int* p_to_i,
+                                long long n, unsigned char* out) {
+    ColcheckArgs a{};
+    if (int rc = df_img_args("colcheck", ctx, o, img, n_img, H, W, points, p_to_i, n, &a.im)) return rc;
+    if (outside < 0 || outside > 2) return fail(SDFNMPC_E_ARG, "colcheck: outside must be 0 (free), 1 (col) or 2 (extrapolate)");
+    if (n == 0) return SDFNMPC_OK;
+    if (!out) return fail(SDFNMPC_E_ARG, "colcheck: NULL output");
+    a.outside = outside;
+    a.safe_ball = safe_ball;
+    a.out = out;
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "colcheck", [&] { return launch_colcheck(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_udf(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* o, float max_df, const float* img, int n_img,
+                           int H, int W, const float* points, const int* p_to_i, long long n, float* udf, float* grad,
+                           int* pix_idx) {
+    UdfArgs a{};
+    if (int rc = df_img_args("udf", ctx, o, img, n_img, H, W, points, p_to_i, n, &a.im)) return rc;
+    if (H % 5 != 0 || W % 5 != 0) return fail(SDFNMPC_E_ARG, "udf: H and W must be multiples of 5 (the min-pool kernel)");
+    if (udf_lds_bytes(H / 5, W / 5) > UDF_LDS_MAX) return fail(SDFNMPC_E_ARG, "udf: image too large");
+    if (n == 0) return SDFNMPC_OK;
+    if (!udf || !grad) return fail(SDFNMPC_E_ARG, "udf: NULL output");
+    ScopedDevice sd(ctx->device);
+    HIPCHK(ctx->dfpool.ensure((size_t)n_img * (H / 5) * (W / 5) * sizeof(float)));
+    MinpoolArgs m{img, (float*)ctx->dfpool.p, n_img, H, W, o->dmax};
+    HIPCHK(timed(ctx, "minpool5", [&] { return launch_minpool5(m, ctx->stream); }));
+    a.im.img = (const float*)ctx->dfpool.p;
+    a.im.H = H / 5;
+    a.im.W = W / 5;
+    a.max_df = max_df;
+    a.udf = udf;
+    a.grad = grad;
+    a.pix_idx = pix_idx;
+    HIPCHK(timed(ctx, "udf", [&] { return launch_udf(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_sdf_truth(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* o, float min_df, float max_df,
+                                 const float* grid, const float* dist, const int* orig_idx, int G, const float* img,
+                                 int n_img, int H, int W, const float* points, const int* p_to_i, long long n,
+                                 float* sdf, float* grad, int* vox_idx) {
+    SdfGridArgs a{};
+    if (int rc = df_img_args("sdf_truth", ctx, o, img, n_img, H, W, points, p_to_i, n, &a.im)) return rc;
+    if (G < 0 || (G > 0 && (!grid || !dist))) return fail(SDFNMPC_E_ARG, "sdf_truth: bad grid");
+    if (!(min_df < max_df)) return fail(SDFNMPC_E_ARG, "sdf_truth: min_df must be below max_df");
+    if (n == 0) return SDFNMPC_OK;
+    if (!sdf || !grad) return fail(SDFNMPC_E_ARG, "sdf_truth: NULL output");
+    a.min_df = min_df;
+    a.max_df = max_df;
+    a.grid = grid;
+    a.dist = dist;
+    a.orig_idx = orig_idx;
+    a.G = G;
+    a.sdf = sdf;
+    a.grad = grad;
+    a.vox_idx = vox_idx;
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "sdf_grid", [&] { return launch_sdf_grid(a, ctx->stream); }));
     return SDFNMPC_OK;
 }
