@@ -263,6 +263,10 @@ int sdfnmpc_ctx_qp_kernel(const sdfnmpc_ctx* ctx, int N, int B);
  * rows), so the choice is the batch / horizon policy above.  Replaces acados' one HPIPM instance per solver
  * (ocp.py:113-120). */
 int sdfnmpc_ctx_qp_kernel_for(const sdfnmpc_ctx* ctx, int N, int B, const sdfnmpc_qp_opts* opts);
+/* segments (wavefronts) per instance of the SEGMENTED kernel at horizon N: 4 for 7 <= N <= 63, 3 for N = 5, 6,
+ * 2 for N = 3, 4; 0 where it does not serve N (the SERIAL kernel runs then).  Read-only; follows the
+ * diagnostic SDFNMPC_QP_NSEG as the launch does. */
+int sdfnmpc_qp_seg_count(int N);
 /* LDS bytes one instance of the serial QP kernel holds at horizon N (-1: N < 1) */
 long long sdfnmpc_qp_lds_bytes(int N);
 /* the occupancy gate of SURVEY.md §8(e): instances the context's device solves in one wave of QP

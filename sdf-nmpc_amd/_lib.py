@@ -24,7 +24,7 @@ L4C_PATH = os.path.join(LIB_DIR, "libsdf_l4c.so")
 SYMBOLS = [
     "sdfnmpc_abi_version", "sdfnmpc_last_error", "sdfnmpc_ctx_create", "sdfnmpc_ctx_destroy",
     "sdfnmpc_ctx_set_stream", "sdfnmpc_ctx_use_null_stream", "sdfnmpc_ctx_stream", "sdfnmpc_ctx_synchronize", "sdfnmpc_ctx_set_tile_rows",
-    "sdfnmpc_ctx_set_qp_kernel", "sdfnmpc_ctx_set_sdf_server", "sdfnmpc_ctx_sdf_server_stats", "sdfnmpc_ctx_qp_kernel", "sdfnmpc_ctx_qp_kernel_for", "sdfnmpc_qp_lds_bytes", "sdfnmpc_qp_capacity", "sdfnmpc_qp_capacity_for",
+    "sdfnmpc_ctx_set_qp_kernel", "sdfnmpc_ctx_set_sdf_server", "sdfnmpc_ctx_sdf_server_stats", "sdfnmpc_ctx_qp_kernel", "sdfnmpc_ctx_qp_kernel_for", "sdfnmpc_qp_seg_count", "sdfnmpc_qp_lds_bytes", "sdfnmpc_qp_capacity", "sdfnmpc_qp_capacity_for",
     "sdfnmpc_ctx_enable_timing", "sdfnmpc_ctx_kernel_stats", "sdfnmpc_ctx_reset_stats", "sdfnmpc_net_load",
     "sdfnmpc_net_load_file", "sdfnmpc_net_siren", "sdfnmpc_net_free", "sdfnmpc_net_max_df",
     "sdfnmpc_net_size_latent", "sdfnmpc_net_fingerprint", "sdfnmpc_sdf_eval", "sdfnmpc_sdf_eval_host",
@@ -150,6 +150,7 @@ def load():
         "sdfnmpc_ctx_sdf_server_stats": (i, [vp, P(d)]),
         "sdfnmpc_ctx_qp_kernel": (i, [vp, i, i]),
         "sdfnmpc_ctx_qp_kernel_for": (i, [vp, i, i, P(QpOptsC)]),
+        "sdfnmpc_qp_seg_count": (i, [i]),
         "sdfnmpc_qp_lds_bytes": (C.c_longlong, [i]),
         "sdfnmpc_qp_capacity": (C.c_longlong, [vp, i]),
         "sdfnmpc_qp_capacity_for": (C.c_longlong, [vp, i, P(QpOptsC)]),
@@ -462,6 +463,12 @@ def rti_prepare(ctx: Context, net, model: QuadModelC, opts: QpOptsC, B: int, N: 
     qa = QpArgsC(B, N, *[_ptr(bufs.get(k)) for k in QP_IN + QP_OUT])
     _check(load().sdfnmpc_rti_prepare(ctx.h, None if net is None else net.h, C.byref(model), C.byref(la),
                                       C.byref(opts), C.byref(qa)))
+
+
+def qp_seg_count(N: int) -> int:
+    """Segments (wavefronts) per instance of the segmented QP kernel at horizon N; 0: it does not serve N
+    (sdfnmpc_qp_seg_count; follows SDFNMPC_QP_NSEG as the launch does)."""
+    return int(load().sdfnmpc_qp_seg_count(N))
 
 
 def qp_feedback(ctx: Context, opts: QpOptsC, B: int, N: int, bufs: dict):

@@ -370,6 +370,8 @@ extern "C" int sdfnmpc_ctx_qp_kernel_for(const sdfnmpc_ctx* ctx, int N, int B, c
     return qp_kernel_for(ctx, N, B, o ? qp_is_seg_set(*o) : true);
 }
 
+extern "C" int sdfnmpc_qp_seg_count(int N) { return N < 1 ? 0 : rti_qp_seg_count(N); }
+
 extern "C" long long sdfnmpc_qp_lds_bytes(int N) {
     return N < 1 ? -1 : (long long)qp_lds_bytes(N);
 }

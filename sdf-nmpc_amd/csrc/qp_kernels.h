@@ -35,7 +35,7 @@ struct QpArgs {
     int ny;  // 11, or 12 with the sdf cost residual (formed in the pack kernel from h[2], J_h[2])
     int pack_part;  // 0: whole stage records; 1: all but the sdf row of C^T (row sdf_row; needs ny == 11), which
                     // rti_qp_kernel then copies from J_h itself (sdf_row_patch)
-    int sdf_row_patch;  // rti_qp_kernel: copy J_h[.][2] into the records' C^T row 2 before the sweeps
+    int sdf_row_patch;  // both QP kernels: copy J_h[.][2] into the records' C^T row sdf_row (where >= 0) before the sweeps
     int warm_start;     // 1: the IPM starts from the du found in du on entry (qp_solver_warm_start, ocp.py:116)
     int nhs;            // hard stage rows: the last nhs of the nh (slack weight None, base_model.py:142-155)
     int seg_rows;       // 1: a row set the segmented kernel serves (engine.cpp qp_is_seg_set)

@@ -319,7 +319,9 @@ __global__ __launch_bounds__(64 * NSEG, NSEG == 4 ? 2 : NSEG) void rti_qp_seg_ke
         s.fw[e] = 0.0;
         s.fg[e] = 0.0;
     }
-    if (A.sdf_row_patch) {  // records packed beside the SDF kernel (pack_part 1): their sdf row of C^T
+    // records packed beside the SDF kernel (pack_part 1): their sdf row of C^T.  No stage row reads the sdf
+    // (sdf_row -1: the network serves a terminal row only, whose C is assembled into ctn above): nothing to copy
+    if (A.sdf_row_patch && A.sdf_row >= 0) {
         for (int e = lane; e < (sb - sa) * NX; e += 64) {
             const int k = sa + e / NX, l = e % NX;
             Rw[(size_t)k * REC + R_CT + 10 * A.sdf_row + l] = A.Jh[((size_t)b * N1 + k) * 30 + l * 3 + 2];
@@ -332,8 +334,9 @@ __global__ __launch_bounds__(64 * NSEG, NSEG == 4 ? 2 : NSEG) void rti_qp_seg_ke
         F[(size_t)k * FRECS + S_C + q] = R[(size_t)k * REC + src];
     }
     // lane-owned rows: box pair (kb, ib) (rows 8 kb + ib, 8 kb + 4 + ib) of this wave's nodes; group (ks, js)
-    // of a stage node (lanes 0..47: at most 15 stage nodes x 3), soft (its four rows in ts / ls) or hard
-    // (lower, upper in ts[0..1] / ls[0..1]); in the last wave lanes 48 + j the terminal row j, soft or hard
+    // of a stage node (lanes 0..47: at most 16 stage nodes x 3), soft (its four rows in ts / ls) or hard
+    // (lower, upper in ts[0..1] / ls[0..1]); in the last wave (at most 15 stage nodes: lanes 0..44) lanes 48 + j
+    // the terminal row j, soft or hard
     const bool last = w == NSEG - 1;
     const int jt = lane - 48;
     const bool tlane = last && jt >= 0 && jt < QP_NHN;

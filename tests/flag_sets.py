@@ -23,6 +23,11 @@ FLAG_SETS = {
     "rec_feas": (RF, [0, 1, 2], [(0, -1, True), (1, -1, True), (2, 0, False), (-1, 1, False), (-1, 2, False)]),
     "rec_feas_soft_brake": (dict(RF, mpc__weights__slack_brake=[50.0, 10.0]), [0, 1, 2],
                             [(0, -1, True), (1, -1, True), (2, 0, True), (-1, 1, False), (-1, 2, False)]),
+    # the network read by terminal rows only (the braking row), no stage sdf row: need_sdf with sdf_row == -1
+    "rec_feas_no_sdf_row": (dict(RF, flags__sdf_constraint=False), [0, 1],
+                            [(0, -1, True), (1, -1, True), (2, 0, False), (-1, 1, False), (-1, 2, False)]),
+    "rec_feas_lidar_no_rows": (dict(RF, **LIDAR, flags__sdf_constraint=False, flags__vfov_constraint=False), [],
+                               [(2, 0, False), (-1, 1, False)]),
     "stability": (ST, [0, 1, 2], [(0, -1, True), (1, -1, True), (2, 0, False), (-1, 1, False), (-1, 2, False),
                                   (-1, 3, False), (-1, 4, False), (-1, 5, False)]),
     "stability_lidar_no_vfov": (dict(ST, **LIDAR, flags__vfov_constraint=False), [2],
@@ -36,6 +41,31 @@ FLAG_SETS = {
                          [(0, -1, True), (1, -1, True), (2, 0, False), (-1, 1, False), (-1, 2, False)]),
 }
 HARD_SETS = [n for n in FLAG_SETS if n.startswith("hard")]
+
+# Edges of the segmented QP kernel's horizon / segment-count space as (N, SDFNMPC_QP_NSEG set, segments P): the
+# partition is a_i = i (N + 1) / P.  Without the variable: N = 7 (P = 4, two nodes per segment), 36 (AUTO's lower
+# bound), 37 (38 nodes: segments of 9, 10, 9, 10), 63 (16 nodes per segment, the kernel's largest horizon), 5
+# (the smallest N with P = 3), 3 (the smallest with P = 2).  With it: the three- and two-segment instantiations at
+# a mid horizon and at their largest one (47, 31: 16 nodes per segment).
+SEG_EDGES = [(7, False, 4), (36, False, 4), (37, False, 4), (63, False, 4), (5, False, 3), (30, True, 3), (47, True, 3),
+             (3, False, 2), (20, True, 2), (31, True, 2)]
+
+
+# The phase-split runs (test_gpu_flags.test_phase_split_bitwise_per_flag_set) as (B, N, kernel, seed): the serial
+# kernel under AUTO; the segmented one under AUTO; the segmented one forced at a short horizon.  The test asks for
+# status 0 everywhere, so each seed is one at which every QP of every set below is feasible -- the C IPM on the
+# oracle linearisation converges on all of them (test_flags.test_phase_split_problems_converge_in_the_c_ipm).  At
+# (8, 20) seeds 13 and 14 each give hard_df_rec_feas one instance whose hard sdf row is infeasible (status 2 from
+# the C IPM as from both kernels): the next seed, 15.
+PHASE_SPLIT_SETS = ["no_vfov", "lidar_sdf_only", "sdf_cost_only", "no_sdf", "rec_feas", "stability", "hard_fov",
+                    "hard_df_rec_feas", "stability_lidar_no_vfov", "rec_feas_no_sdf_row", "rec_feas_lidar_no_rows"]
+PHASE_SPLIT_RUNS = [(24, 20, "auto", 13), (8, 40, "auto", 13), (8, 20, "segmented", 15)]
+
+
+def seg_edge_sets(N, P):
+    """The flag sets run at an edge: the default rows and the set with no stage sdf row everywhere, a set with a
+    hard stage row at P = 4's largest horizon and at one P = 3 case."""
+    return ["default", "rec_feas_no_sdf_row"] + (["hard_df_rec_feas"] if (N, P) in ((63, 4), (30, 3)) else [])
 
 
 def config(name, **more):

@@ -216,3 +216,31 @@ def test_segments_match_serial_riccati(oracle_lib, name):
     b = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, start=dict(seg=4))
     assert np.abs(a["iters"] - b["iters"]).max() <= 1
     np.testing.assert_allclose(a["du"], b["du"], rtol=0, atol=1e-6)  # rounding-level differences, amplified near tol
+
+
+@pytest.mark.parametrize("B,N,kernel,seed", F.PHASE_SPLIT_RUNS)
+def test_phase_split_problems_converge_in_the_c_ipm(oracle_lib, B, N, kernel, seed):
+    """The problems of test_gpu_flags.test_phase_split_bitwise_per_flag_set, which asks for status 0 on every
+    instance, are feasible: the C IPM (the recursion of the kernel the run uses) converges on all of them."""
+    for name in F.PHASE_SPLIT_SETS:
+        cfg, q, prob, x0, lin = _problem(oracle_lib, name, B, N, seed=seed)
+        seg = kernel == "segmented" or N >= 36
+        r = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, start=dict(seg=4) if seg else None)
+        assert (r["status"] == 0).all(), (name, r["status"])
+
+
+@pytest.mark.parametrize("N,P", [(N, P) for N, _, P in F.SEG_EDGES])
+def test_segment_edges_serial_vs_segmented_c_ipm(oracle_lib, N, P):
+    """The references of test_gpu_flags.test_segmented_qp_horizon_and_segment_edges meet its bars among
+    themselves: at every (N, P) edge, on that test's problems (B = 16, seed 12), the C IPM's serial recursion
+    and its recursion over P segments both converge everywhere, stop within one iteration of each other, and
+    agree in du to 5e-6 on >= 90 % of the instances (a degenerate instance -- one of 16 at (37, 4) default
+    and at (63, 4) hard_df_rec_feas, 7e-6 and 1.5e-5 -- moves along its flat direction)."""
+    for name in F.seg_edge_sets(N, P):
+        cfg, q, prob, x0, lin = _problem(oracle_lib, name, 16, N, seed=12)
+        a = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL)
+        b = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, start=dict(seg=P))
+        assert (a["status"] == 0).all() and (b["status"] == 0).all(), (name, a["status"], b["status"])
+        assert np.abs(a["iters"] - b["iters"]).max() <= 1, (name, a["iters"], b["iters"])
+        gap = np.abs(a["du"] - b["du"]).max(axis=(1, 2))
+        assert (gap <= 5e-6).mean() >= 0.9, (name, gap)

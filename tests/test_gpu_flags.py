@@ -108,15 +108,7 @@ def test_qp_per_flag_set_vs_c_ipm_and_exact(gpu_ctx, oracle_lib, name):
     _check_qp(gpu_ctx, oracle_lib, name, 16, 20, "serial")
 
 
-def _seg_set(name):
-    """A row set the segmented kernel serves (engine.cpp qp_is_seg_set): every flag set."""
-    return True
-
-
-SEG_SETS = [n for n in F.FLAG_SETS if _seg_set(n)]
-
-
-@pytest.mark.parametrize("name", SEG_SETS)
+@pytest.mark.parametrize("name", list(F.FLAG_SETS))
 def test_segmented_qp_per_flag_set(gpu_ctx, oracle_lib, name):
     """VERDICT r5 missing 2: the segmented kernel (rti_qp_seg.hip, four wavefronts per instance, the B = 1
     latency kernel) on every flag set -- 0..3 stage rows of hfov / vfov / sdf, soft or hard (slack None; the
@@ -141,15 +133,34 @@ def test_segmented_kernel_row_sets(gpu_ctx):
     gpu_ctx.set_qp_kernel("segmented")
     try:
         for name in F.FLAG_SETS:
-            want = "segmented" if _seg_set(name) else "serial"
-            assert gpu_ctx.qp_kernel(40, 1, _lib.qp_opts(F.quad(name), tol=QP_TOL)) == want, name
+            assert gpu_ctx.qp_kernel(40, 1, _lib.qp_opts(F.quad(name), tol=QP_TOL)) == "segmented", name
     finally:
         gpu_ctx.set_qp_kernel("auto")
 
 
-def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_frac=1.0, n_exact=None):
+@pytest.mark.parametrize("N,nseg_env,nseg,name", [
+    pytest.param(N, env, P, name, id=f"N{N}-P{P}{'env' if env else ''}-{name}")
+    for N, env, P in F.SEG_EDGES for name in F.seg_edge_sets(N, P)])
+def test_segmented_qp_horizon_and_segment_edges(gpu_ctx, oracle_lib, monkeypatch, N, nseg_env, nseg, name):
+    """The segmented kernel's three instantiations (<2,31>, <3,47>, <4,63>) at the edges of the horizon and
+    segment-count space (flag_sets.SEG_EDGES: two-node segments, AUTO's lower bound N = 36, the one-node
+    remainder at N = 37, sixteen-node segments at each instantiation's largest N -- the lane-ownership and
+    LDS limit -- and the smallest horizons that reach P = 3 and P = 2), against the C IPM's recursion over
+    the same partition a_i = i (N + 1) / P and the exact solution, to _check_qp's bars.  B = 16, seed 12:
+    test_flags.test_segment_edges_serial_vs_segmented_c_ipm holds the references to those bars on the CPU."""
+    if nseg_env:
+        monkeypatch.setenv("SDFNMPC_QP_NSEG", str(nseg))
+    else:
+        monkeypatch.delenv("SDFNMPC_QP_NSEG", raising=False)
+    assert _lib.qp_seg_count(N) == nseg  # the instantiation under test; 0 would run the serial kernel
+    _check_qp(gpu_ctx, oracle_lib, name, 16, N, "segmented", need_active=False, iters_frac=0.9,
+              n_exact=1 if N >= 47 else 2, nseg=nseg)
+
+
+def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_frac=1.0, n_exact=None, nseg=4):
     """n_exact: the exact solution (a dense KKT solve, ~2 s per instance at N = 40) for the first n_exact
-    instances and every instance whose du is off the C IPM's by more than the bar (None: all)."""
+    instances and every instance whose du is off the C IPM's by more than the bar (None: all).  nseg: the
+    segments of the segmented kernel at this N (the C IPM runs lqr_seg over the same partition)."""
     import qp_oracle
     from test_gpu_qp import _agree
     cfg, q, prob, x0, t = _setup(gpu_ctx, name, B, N, seed=12)
@@ -164,9 +175,13 @@ def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_f
         gpu_ctx.set_qp_kernel("auto")
     got = _np(t, OUT)
     lin = {k: got[k] for k in LIN}
-    # the segmented kernel against the C IPM's segmented recursion (oracle/qp_ipm.c lqr_seg: the same four
+    # the segmented kernel against the C IPM's segmented recursion (oracle/qp_ipm.c lqr_seg: the same
     # segments and couplings), the serial one against the serial recursion
-    c = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, start=dict(seg=4) if kernel == "segmented" else None)
+    c = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, start=dict(seg=nseg) if kernel == "segmented" else None)
+    gap = np.abs(got["du"] - c["du"]).max(axis=(1, 2))[(c["status"] == 0) & (got["status"] == 0)]
+    print(f"\n_check_qp {name} B={B} N={N} {kernel}" + (f" P={nseg}" if kernel == "segmented" else "") +
+          f": worst |du - du_C| = {gap.max() if gap.size else float('nan'):.2e}, share within {ORC_ATOL:g}: "
+          f"{(gap <= ORC_ATOL).mean() if gap.size else float('nan'):.3f}, iters GPU {got['iters'].tolist()} C {c['iters'].tolist()}")
     # a set with hard rows can make an instance's QP infeasible (the scene problems fly straight at the pillar:
     # a hard sdf row linearised inside it may demand more than the inputs give -- HPIPM fails there too);
     # the two solvers must agree on which instances fail, and the rest are compared
@@ -210,21 +225,33 @@ def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_f
     assert (got["slack"][:, :N, q.nh:] == 0).all() and (got["slack"][:, N, q.nsN:] == 0).all()
 
 
-@pytest.mark.parametrize("name", ["no_vfov", "lidar_sdf_only", "sdf_cost_only", "no_sdf", "rec_feas", "stability",
-                                  "hard_fov", "hard_df_rec_feas"])
-def test_phase_split_bitwise_per_flag_set(gpu_ctx, name):
+@pytest.mark.parametrize("name,B,N,kernel,seed", [
+    pytest.param(name, B, N, kernel, seed, id=name if (B, N, kernel) == F.PHASE_SPLIT_RUNS[0][:3] else f"{name}-{B}-{N}-{kernel}")
+    for B, N, kernel, seed in F.PHASE_SPLIT_RUNS for name in F.PHASE_SPLIT_SETS])
+def test_phase_split_bitwise_per_flag_set(gpu_ctx, name, B, N, kernel, seed):
     """rti_prepare (records packed beside the SDF kernel; the sdf row of C^T -- row 1 with no_vfov, row 0 with
-    lidar_sdf_only -- patched by the QP kernel) + qp_feedback == linearize + qp_solve, bit for bit."""
-    B, N = 24, 20
-    cfg, q, prob, x0, ta = _setup(gpu_ctx, name, B, N, seed=13)
-    _, _, _, _, tb = _setup(gpu_ctx, name, B, N, seed=13)
+    lidar_sdf_only, none (sdf_row == -1) where only the terminal braking row reads the network -- patched by
+    the QP kernel) + qp_feedback == linearize + qp_solve, bit for bit, on the serial and the segmented kernel
+    (flag_sets.PHASE_SPLIT_RUNS).  (A segmented kernel that patches with sdf_row == -1 writes J_h[:, 2] over
+    g_x[4..9] and g_u of every stage record: status 0 everywhere and du off by 0.39 on the two rec_feas sets
+    without a stage sdf row.)"""
+    cfg, q, prob, x0, ta = _setup(gpu_ctx, name, B, N, seed=seed)
+    _, _, _, _, tb = _setup(gpu_ctx, name, B, N, seed=seed)
     net, qm, opts = _net(gpu_ctx, q), _lib.quad_model(cfg, q), _lib.qp_opts(q)
-    _lib.linearize(gpu_ctx, net, qm, B, N, q.np, ta, nyN=q.nyN, no_sdf=not q.need_sdf)
-    _lib.qp_solve(gpu_ctx, opts, B, N, ta)
-    _lib.rti_prepare(gpu_ctx, net, qm, opts, B, N, q.np, tb, no_sdf=not q.need_sdf)
-    _lib.qp_feedback(gpu_ctx, opts, B, N, tb)
-    gpu_ctx.synchronize()
+    gpu_ctx.set_qp_kernel(kernel)
+    try:
+        want = "segmented" if (kernel == "segmented" or N >= 36) else "serial"
+        assert gpu_ctx.qp_kernel(N, B, opts) == want
+        _lib.linearize(gpu_ctx, net, qm, B, N, q.np, ta, nyN=q.nyN, no_sdf=not q.need_sdf)
+        _lib.qp_solve(gpu_ctx, opts, B, N, ta)
+        _lib.rti_prepare(gpu_ctx, net, qm, opts, B, N, q.np, tb, no_sdf=not q.need_sdf)
+        _lib.qp_feedback(gpu_ctx, opts, B, N, tb)
+        gpu_ctx.synchronize()
+    finally:
+        gpu_ctx.set_qp_kernel("auto")
     a, b = _np(ta, OUT), _np(tb, OUT)
+    print(f"\nphase split {name} B={B} N={N} {want}: max |du_split - du_whole| = {np.nan_to_num(np.abs(a['du'] - b['du']), nan=np.inf).max():.3e}, "
+          f"status whole {a['status'].tolist()} split {b['status'].tolist()}")
     assert (a["status"] == 0).all()
     for k in OUT:
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
@@ -275,13 +302,16 @@ def _nmpc(name, B, N, seed):
     return n, q, x0
 
 
-@pytest.mark.parametrize("name", ["no_sdf", "no_sdf_constraint", "lidar", "rec_feas_soft_brake", "stability",
-                                  "hard_all", "hard_df_rec_feas"])
-def test_controller_rti_step_per_flag_set(oracle_lib, name):
+@pytest.mark.parametrize("name,N", [pytest.param(n, 20, id=n) for n in (
+    "no_sdf", "no_sdf_constraint", "lidar", "rec_feas_soft_brake", "stability", "hard_all", "hard_df_rec_feas")] +
+    [pytest.param("rec_feas_no_sdf_row", 40, id="rec_feas_no_sdf_row-N40")])
+def test_controller_rti_step_per_flag_set(oracle_lib, name, N):
     """Nmpc.solve (host setters, solver object) for a flag set: one SQP-RTI step against the oracle pipeline
-    (oracle linearisation + the C IPM) on the same iterate; u0 within 2e-5."""
-    B, N = 6, 20
+    (oracle linearisation + the C IPM) on the same iterate; u0 within 2e-5.  At N = 40 AUTO runs the segmented
+    kernel on the solver object's split pack -- for rec_feas_no_sdf_row with no stage sdf row to patch."""
+    B = 6
     n, q, x0 = _nmpc(name, B, N, seed=21)
+    assert n.ocp.ctx.qp_kernel(N, B, _lib.qp_opts(q)) == ("segmented" if N >= 36 else "serial")
     xbar, ubar = n.ocp.download("x").copy(), n.ocp.download("u").copy()
     xbar[:, 0] = x0
     assert n.solve() == 0
