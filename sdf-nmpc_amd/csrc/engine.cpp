@@ -188,8 +188,12 @@ extern "C" int sdfnmpc_ctx_create(int device, void* stream, sdfnmpc_ctx** out) {
     int lo = 0, hi = 0;
     hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);  // lo = least urgent
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, lo);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
+    // the fork / join events order kernels of this device only and the host never waits on them (it
+    // synchronises on the stream), so they carry no system-scope fence: without its cache writeback the
+    // step is ≈6 µs shorter
+    const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, evf);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, evf);
     if (e != hipSuccess) {
         sdfnmpc_ctx_destroy(c);
         return fail(SDFNMPC_E_HIP, std::string("aux stream/events: ") + hipGetErrorString(e));
@@ -1424,9 +1428,13 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
         HIPCHK(timed(ctx, "sdf_row", [&] { return launch_sdf_row(ra, ctx->stream); }));
         if ((rc = fork_launch())) return rc;
     } else {
+        // the fork before the hoist (as the wide branch): linearize reads x, u, p and dt and nothing the hoist
+        // writes, and sdf_hoist's 32 workgroups leave the GPU to it until sdf_mlp starts.  The auxiliary stream
+        // keeps the lowest priority: at a higher one linearize and the pack take sdf_mlp's slots and the phase
+        // is slower
+        if ((rc = fork_lin())) return rc;
         rc = run_hoist<double>(ctx, net, a->p + 17, stride, n_inst, (float*)ctx->c13.p);
         if (rc) return rc;
-        if ((rc = fork_lin())) return rc;
         // 3. network forward + position gradient, with the sdf row of h / J_h in its epilogue
         rc = run_sdf(ctx, net, rows, nullptr, (const float*)ctx->c13.p,
                      a->latent_mode == 0 ? a->N + 1 : 1, sdf4, nullptr, ctx->tile_rows, &cons);

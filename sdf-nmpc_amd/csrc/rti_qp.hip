@@ -193,9 +193,15 @@ constexpr PackTri make_tri() {
 }
 __constant__ PackTri c_tri = make_tri();
 
-constexpr int PACK_NODES = 4;  // wavefronts (nodes) per workgroup
+constexpr int PACK_NODES = 4;  // wavefronts (nodes) per workgroup (two and one measured slower)
 
-__global__ __launch_bounds__(64 * PACK_NODES) void rti_qp_pack_kernel(QpArgs A) {
+// Register budget: the split pack runs beside sdf_mlp_kernel, whose two waves per SIMD hold 2 x 224 of the
+// SIMD's 512 registers per lane.  The 64 left are what a pack wave may take to start beside both, so the
+// bound asks for eight waves per SIMD (512 / 8 = 64 registers; 47 used); no LDS, for the same reason
+// (sdf_mlp's two workgroups fill the CU's).
+constexpr int PACK_WAVES_PER_SIMD = 8;
+
+__global__ __launch_bounds__(64 * PACK_NODES, PACK_WAVES_PER_SIMD) void rti_qp_pack_kernel(QpArgs A) {
     const int N = A.N, N1 = N + 1;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int node = blockIdx.x * PACK_NODES + wv;
