@@ -35,6 +35,14 @@
  *                                      solve_for_x0 (ocp.py:169) -> _step + _wait.  It owns the device
  *                                      workspace of B instances, so a controller needs no tensor library
  *
+ *   sdfnmpc_plant_step                 (no reference interface: the reference's plant is the simulator it is run against)
+ *                                      x_next = RK4^substeps of the 'att' / 'att_tau' f_expl (model/
+ *                                      quad_rollpitchyawrate.py:19-55, quad_rollpitchyawrate_tau.py:19-58) per
+ *                                      instance, optionally with a disturbance acceleration and a thrust-gain error
+ *   sdfnmpc_solver_rollout             K iterations of the loop a user of Nmpc writes around it (controller.py:
+ *                                      65-81 set_x0 + solve, with RefGen before and the simulator after), enqueued
+ *                                      without a host round trip: references from x0, shift, RTI step, plant
+ *
  *   sdfnmpc_colcheck                   ColChecker.check_image_points (utils/collision_checker.py:23-125)
  *   sdfnmpc_udf / sdfnmpc_sdf_truth    DfComputer.get_udf / get_sdf (utils/df_computer.py:85-221): the distance
  *                                      field the image itself implies, to label data and to score a network
@@ -52,7 +60,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 8
+#define SDFNMPC_ABI_VERSION 9
 
 enum {
     SDFNMPC_OK = 0,
@@ -282,7 +290,7 @@ long long sdfnmpc_qp_capacity_for(const sdfnmpc_ctx* ctx, int N, const sdfnmpc_q
 int sdfnmpc_ctx_set_tile_rows(sdfnmpc_ctx* ctx, int rows);
 /* per-kernel HIP-event timing on the context stream (off by default) */
 int sdfnmpc_ctx_enable_timing(sdfnmpc_ctx* ctx, int on);
-/* kernel: "sdf_mlp", "sdf_hoist", "linearize"; synchronizes the stream(s) */
+/* kernel: "sdf_mlp", "sdf_hoist", "linearize", "rti_qp", "plant", ...; synchronizes the stream(s) */
 int sdfnmpc_ctx_kernel_stats(sdfnmpc_ctx* ctx, const char* kernel, double* total_ms, long long* launches);
 int sdfnmpc_ctx_reset_stats(sdfnmpc_ctx* ctx);
 
@@ -470,6 +478,55 @@ int sdfnmpc_solver_shift(sdfnmpc_solver* s, int k);
 int sdfnmpc_solver_step(sdfnmpc_solver* s);
 /* wait for the stream; copy the last step's u0 [B][4], status [B], iters [B] (each may be NULL) */
 int sdfnmpc_solver_wait(sdfnmpc_solver* s, double* u0, int* status, int* iters);
+
+/* ---- the plant of a closed loop (csrc/plant.hip) ----
+ * One control period of the vehicle, integrated with `substeps` RK4 steps of dt / substeps (the Butcher tableau and
+ * accumulation order of the preparation phase: with the controller's kind, substeps = 1, dt = dt_k and no mismatch,
+ * x_next is sdfnmpc_lin_args.xn up to rounding).  The plant may differ from the controller's model: the other kind,
+ * a finer step, and per instance a constant world-frame acceleration added to dv/dt and a factor on the thrust
+ * input.  Inputs are not clipped and the quaternion is not renormalised (both models normalise internally). */
+typedef struct {
+    int kind;                      /* SDFNMPC_MODEL_ATT / _ATT_TAU: the plant's model, may differ from the controller's */
+    double gamma, roll, pitch, wz, g, tau_roll, tau_pitch; /* as sdfnmpc_quad_model (tau_*: kind 1 only, > 0) */
+    double dt;                     /* control period, s (> 0) */
+    int substeps;                  /* RK4 steps per period, 1..64 */
+    const double* acc_dist;        /* device [B][3] or NULL */
+    const double* gamma_scale;     /* device [B] or NULL */
+} sdfnmpc_plant_opts;
+
+/* x_next[B][10] = plant(x[B][10], u[B][4]); device pointers, x_next may alias x.  Asynchronous on the context
+ * stream.  SDFNMPC_E_ARG (nothing is launched, x_next untouched): NULL arguments, B < 0, substeps outside 1..64,
+ * dt <= 0, kind 1 with a tau <= 0; SDFNMPC_E_UNSUPPORTED: an unknown kind.  B == 0 is a no-op. */
+int sdfnmpc_plant_step(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* opts, int B, const double* x, const double* u,
+                       double* x_next);
+
+/* K closed-loop steps of the solver's B instances without a host round trip.  Per step, in the order Nmpc.solve
+ * uses: (1) with ref: sdfnmpc_pack_refs from the current x0 into the solver's p / yref / W / yNref / WN; (2) with
+ * shift > 0: sdfnmpc_solver_shift(shift); (3) the SQP-RTI step of sdfnmpc_solver_step; (4) the plant on the solver's
+ * x0 and u0 fields: x0 <- plant(x0, u0) in place -- the next measured state -- and the log rows.  Everything is
+ * enqueued on the solver's stream as a plain launch sequence; sdfnmpc_solver_wait finishes it and returns the last
+ * step's u0 / status / iters.  The arrays named here (and by ref and plant) must stay alive until then.
+ * An instance whose QP fails (status >= 2) keeps its iterate and is advanced with the u0 sdfnmpc_rti_apply leaves,
+ * the unchanged u[:, 0] (Ocp.solve on the host substitutes the previous call's u instead).
+ * SDFNMPC_E_ARG (nothing is launched): NULL arguments, steps < 1, a missing x_log or u_log, the plant's refusals,
+ * ref->mode outside 0..2 or without its inputs (wrow; mode 0: wp_p, wp_q, 1 <= n_wp <= 32; mode 1: vw);
+ * SDFNMPC_E_UNSUPPORTED: an unknown plant kind. */
+typedef struct {
+    int steps;                     /* K >= 1 */
+    int shift;                     /* sdfnmpc_solver_shift(k) before every step (mpc.shift) */
+    const sdfnmpc_ref_opts* ref;   /* NULL: references and q_d stay as they are; else sdfnmpc_pack_refs from the
+                                      current x0 before every step (modes 0 / 1 / 2), with: */
+    const double *wp_p, *wp_q, *vw, *wrow; /* device, as sdfnmpc_ref_args */
+    int n_wp;
+    sdfnmpc_plant_opts plant;
+    double* x_log;                 /* device [B][K+1][10]; row 0 = the starting x0 */
+    double* u_log;                 /* device [B][K][4] */
+    int *status_log, *iters_log;   /* device [B][K], each may be NULL */
+    float* pts_log;                /* device [B][K+1][3] or NULL: the fp32 camera-frame position W_R_Co^T (x[:3] -
+                                      W_p_Co) of every logged state, the pose from node 0 of the instance's p row */
+} sdfnmpc_rollout_args;
+
+int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args);
 
 /* ---- shooting grid (host, bit-exact numpy.linspace/diff semantics of ocp.py:21-27) ---- */
 int sdfnmpc_shooting_grid(int N, double T, int uniform, int nb_short_nodes, double dt_short, double* nodes,

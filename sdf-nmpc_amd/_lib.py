@@ -35,7 +35,7 @@ SYMBOLS = [
     "sdfnmpc_ctx_device", "sdfnmpc_dev_alloc", "sdfnmpc_dev_free", "sdfnmpc_memcpy",
     "sdfnmpc_solver_create", "sdfnmpc_solver_destroy", "sdfnmpc_solver_field", "sdfnmpc_solver_upload",
     "sdfnmpc_solver_download", "sdfnmpc_solver_init", "sdfnmpc_solver_shift", "sdfnmpc_solver_step",
-    "sdfnmpc_solver_wait",
+    "sdfnmpc_solver_wait", "sdfnmpc_plant_step", "sdfnmpc_solver_rollout",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -121,6 +121,18 @@ class QpArgsC(C.Structure):
     _fields_ = [("B", C.c_int), ("N", C.c_int)] + [(n, C.c_void_p) for n in QP_IN + QP_OUT]
 
 
+class PlantOptsC(C.Structure):
+    _fields_ = [("kind", C.c_int)] + [(n, C.c_double) for n in ("gamma", "roll", "pitch", "wz", "g", "tau_roll",
+                                                                "tau_pitch", "dt")] + [
+        ("substeps", C.c_int), ("acc_dist", C.c_void_p), ("gamma_scale", C.c_void_p)]
+
+
+class RolloutArgsC(C.Structure):
+    _fields_ = [("steps", C.c_int), ("shift", C.c_int), ("ref", C.POINTER(RefOptsC))] + [
+        (n, C.c_void_p) for n in ("wp_p", "wp_q", "vw", "wrow")] + [("n_wp", C.c_int), ("plant", PlantOptsC)] + [
+        (n, C.c_void_p) for n in ("x_log", "u_log", "status_log", "iters_log", "pts_log")]
+
+
 _lib = None
 
 
@@ -196,11 +208,13 @@ def load():
         "sdfnmpc_solver_shift": (i, [vp, i]),
         "sdfnmpc_solver_step": (i, [vp]),
         "sdfnmpc_solver_wait": (i, [vp, vp, vp, vp]),
+        "sdfnmpc_plant_step": (i, [vp, P(PlantOptsC), i, vp, vp, vp]),
+        "sdfnmpc_solver_rollout": (i, [vp, P(RolloutArgsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 8:
+    if lib.sdfnmpc_abi_version() != 9:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -632,6 +646,63 @@ def sdf_truth(ctx: Context, opts: ImgOptsC, min_df: float, max_df: float, grid, 
                                     int(points.shape[0]), _ptr(out_sdf), _ptr(out_grad), _ptr(vox_idx)))
 
 
+# ---- the plant of a closed loop (csrc/plant.hip) ----
+class PlantOpts:
+    """sdfnmpc_plant_opts with its per-instance mismatch arrays (host arrays are uploaded once per context, at
+    the first call that uses them; device arrays are used in place).  Nothing is checked here: the C entry
+    points refuse bad options."""
+
+    def __init__(self, kind, gamma, roll, pitch, wz, g, tau_roll, tau_pitch, dt, substeps=1, acc_dist=None,
+                 gamma_scale=None):
+        self.kind, self.dt, self.substeps = int(kind), float(dt), int(substeps)
+        self.gamma, self.roll, self.pitch, self.wz, self.g = (float(v) for v in (gamma, roll, pitch, wz, g))
+        self.tau_roll, self.tau_pitch = float(tau_roll), float(tau_pitch)
+        self.acc_dist, self.gamma_scale = acc_dist, gamma_scale
+        self._dev = {}
+
+    def _array(self, ctx: "Context", name: str, B: int, cols):
+        a = getattr(self, name)
+        if a is None:
+            return None
+        if hasattr(a, "data_ptr"):
+            if np.dtype(str(a.dtype).replace("torch.", "")) != np.float64:
+                raise TypeError(f"device {name} must be float64, got {a.dtype}")
+            return sync_producer(a)
+        key = (id(ctx), name, B)
+        if key not in self._dev:
+            h = np.broadcast_to(np.asarray(a, dtype=np.float64), (B,) + cols)
+            self._dev[key] = DeviceArray.from_numpy(ctx, h)
+        return self._dev[key]
+
+    def c(self, ctx: "Context", B: int) -> PlantOptsC:
+        """The C struct for B instances on a context (the object keeps the device arrays it names alive)."""
+        return PlantOptsC(self.kind, self.gamma, self.roll, self.pitch, self.wz, self.g, self.tau_roll, self.tau_pitch,
+                          self.dt, self.substeps, _ptr(self._array(ctx, "acc_dist", B, (3,))),
+                          _ptr(self._array(ctx, "gamma_scale", B, ())))
+
+
+def plant_opts(cfg, model=None, dt=None, substeps=1, acc_dist=None, gamma_scale=None) -> PlantOpts:
+    """The plant of a config: model 'att' / 'att_tau' (None: cfg.mpc.model, the controller's own), control period
+    dt in seconds (required), RK4 substeps per period, and the optional per-instance mismatch -- acc_dist [B][3],
+    a constant world-frame acceleration, and gamma_scale [B], a factor on the thrust input (host or device
+    fp64 arrays; a host array broadcasts over the batch)."""
+    if dt is None:
+        raise ValueError("plant_opts: dt (the control period) is required")
+    name = str(cfg.mpc.get("model", "att")) if model is None else str(model)
+    if name not in MODEL_KINDS:
+        raise ValueError(f"plant model '{name}': only {sorted(MODEL_KINDS)} are built")
+    lim = cfg.robot.limits
+    return PlantOpts(MODEL_KINDS[name], lim.gamma, lim.roll, lim.pitch, lim.wz, 9.81, TAU_ROLL, TAU_PITCH, dt, substeps,
+                     acc_dist, gamma_scale)
+
+
+def plant_step(ctx: "Context", opts: PlantOpts, B: int, x, u, x_next):
+    """Enqueue sdfnmpc_plant_step: x_next [B][10] = plant(x [B][10], u [B][4]), device fp64 arrays; x_next may
+    be x."""
+    o = opts.c(ctx, B)
+    _check(load().sdfnmpc_plant_step(ctx.h, C.byref(o), int(B), _ptr(x), _ptr(u), _ptr(x_next)))
+
+
 class DeviceArray:
     """A device buffer on a context, with numpy-style shape / dtype (the tensor-free way to hand device
     inputs to the entry points).  ``data_ptr()`` makes it usable wherever a torch tensor is accepted."""
@@ -765,8 +836,21 @@ class Solver:
     def step(self):
         _check(load().sdfnmpc_solver_step(self.h))
 
+    def rollout(self, steps: int, plant: PlantOpts, x_log, u_log, status_log=None, iters_log=None, pts_log=None,
+                shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0):
+        """Enqueue sdfnmpc_solver_rollout: `steps` closed-loop steps (references from x0 when ref is given,
+        shift, RTI step, plant) from the x0 field, logged into the device arrays x_log [B][K+1][10], u_log
+        [B][K][4], status_log / iters_log [B][K] int32 and pts_log [B][K+1][3] float32.  Asynchronous: `wait`
+        finishes it (the arrays are kept alive until then)."""
+        a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
+                         _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
+                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
+        self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log)
+        _check(load().sdfnmpc_solver_rollout(self.h, C.byref(a)))
+
     def wait(self):
         _check(load().sdfnmpc_solver_wait(self.h, self.u0.ctypes.data, self.status.ctypes.data, self.iters.ctypes.data))
+        self._rollout_keep = None  # the stream has drained: a rollout's arrays may go
         return self.u0
 
     def close(self):

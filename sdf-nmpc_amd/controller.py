@@ -28,6 +28,15 @@ import numpy as np
 from .model import Quad
 
 
+class Rollout:
+    """What ``Nmpc.rollout`` logged (numpy arrays, batch-leading): x [B, K+1, 10] plant states (row 0 the start),
+    u [B, K, 4] applied inputs, status / iters [B, K] of every QP; with images also col [B, K+1] collision labels
+    and pts [B, K+1, 3] the camera-frame positions they were taken at (else None)."""
+
+    def __init__(self, x, u, status, iters, col=None, pts=None):
+        self.x, self.u, self.status, self.iters, self.col, self.pts = x, u, status, iters, col, pts
+
+
 class Nmpc:
     """Wrapper around the NMPC controller with range image-based collision prediction (batched)."""
 
@@ -158,6 +167,107 @@ class Nmpc:
             self.fail_counts = np.where(mask, getattr(self, "fail_counts", 0) + 1, 0)
         return self.fail_count
 
+    def rollout(self, steps, refs=None, wps=None, vw=None, weights=None, plant=None, imgs=None, safe_ball_size=0.0,
+                outside='col'):
+        """``steps`` closed-loop control steps on the device, without a host round trip between them: per
+        step the references from the current state (``refs``), the shift (mpc.shift), one SQP-RTI iteration
+        and the plant advanced by u_0 -- the loop ``set_x0``; ``gen_refs_device``; ``solve``; simulate,
+        enqueued as one launch sequence and waited for once (sdfnmpc_solver_rollout, csrc/plant.hip).
+
+        It starts from the state of the last ``set_x0`` (required).  refs: None keeps the references as they
+        are (host setters are flushed once at the start); 'wps' / 'joystick' / 'hover' regenerate them from the
+        plant state before every step as ``gen_refs_device(mode, wps, vw, weights)`` does.  plant: a
+        ``_lib.plant_opts(...)`` (another model kind, RK4 substeps, a disturbance acceleration, a thrust-gain
+        error); default: the controller's own model over ocp.dt[0] with one RK4 step, the perfect-model plant.
+        imgs: float32 [B, H, W] range images normalised by sensor.dmax (host or device, as
+        ``check_openloop_traj``): every logged plant position is labelled against its instance's image in one
+        launch of the collision-check kernel after the loop, in the camera frame of node 0's pose parameters.
+
+        Returns a ``Rollout`` of numpy arrays, batch-leading also for one instance: x [B, K+1, 10] (row 0 the
+        start), u [B, K, 4], status / iters [B, K]; with imgs also col [B, K+1] bool and pts [B, K+1, 3] float32.
+        Afterwards ``self.x0`` is the final plant state and ``ocp.u`` / ``ocp.status`` / ``ocp.iters`` are the last
+        step's.  An instance whose QP fails (status >= 2) keeps its iterate and is advanced with the u_0 the
+        failed step leaves, its unchanged u[:, 0] (``Ocp.solve`` substitutes the previous call's u instead)."""
+        from . import _lib
+        from .reference import Ref
+        if self.x0 is None:
+            raise ValueError("set_x0 before rollout (the loop starts at the current state)")
+        if len(self.ocp.parts) != 1:
+            raise ValueError("rollout(): the batch is split over several devices; sharded rollouts are not built")
+        if refs not in (None, "wps", "joystick", "hover"):
+            raise ValueError(f"refs {refs!r}: None, 'wps', 'joystick' or 'hover'")
+        assert outside in _lib.OUTSIDE
+        K, Bn, ctx, solver = int(steps), max(self.B, 1), self.ocp.ctx, self.ocp.parts[0].solver
+        if K < 1:
+            raise ValueError(f"rollout of {K} steps: at least one")
+        kw = {}
+        if refs is not None:
+            code = {"wps": 0, "joystick": 1, "hover": 2}[refs]
+            wrow = self.model.weight_row(weights if weights is not None else Ref(self.cfg).W_on)
+            if code == 1:
+                wrow[:3] = 0.0  # ref.Wp = [0, 0, 0] (ref_gen.py:122)
+            kw = {"ref": _lib.ref_opts(self.cfg, code), "wrow": self._dev(wrow)}
+            if code == 0:
+                if isinstance(wps, (list, tuple)) and len(wps) and hasattr(wps[0], "p"):
+                    wps = (np.array([w.p for w in wps])[None], np.array([w.q for w in wps])[None])
+                wp_p = np.reshape(np.asarray(wps[0], float), (Bn, -1, 3))
+                kw.update(wp_p=self._dev(wp_p), wp_q=self._dev(np.reshape(np.asarray(wps[1], float), (Bn, -1, 4))),
+                          n_wp=wp_p.shape[1])
+            elif code == 1:
+                kw["vw"] = self._dev(np.reshape(np.asarray(vw, float), (Bn, 4)))
+        if plant is None:
+            plant = _lib.plant_opts(self.cfg, dt=float(self.ocp.dt[0]))
+        dimg = None
+        if imgs is not None:
+            dimg, ishape = self._dev_imgs(imgs)
+        if refs is not None:  # the references are regenerated on the device before every step: as after
+            self._clean("q_d", "yref", "W", "yNref", "WN")  # gen_refs_device, host-set references are dropped
+        self._flush()  # the other host-set regions, once
+        self.ocp.upload("x0", np.reshape(np.asarray(self.x0, dtype=np.float64), (Bn, 1, 10)))
+        log = {"x_log": _lib.DeviceArray(ctx, (Bn, K + 1, 10)), "u_log": _lib.DeviceArray(ctx, (Bn, max(K, 1), 4)),
+               "status_log": _lib.DeviceArray(ctx, (Bn, max(K, 1)), np.int32),
+               "iters_log": _lib.DeviceArray(ctx, (Bn, max(K, 1)), np.int32)}
+        if dimg is not None:
+            log["pts_log"] = _lib.DeviceArray(ctx, (Bn, K + 1, 3), np.float32)
+        solver.rollout(K, plant, shift=int(self.cfg.mpc.shift), **kw, **log)
+        u0 = solver.wait().copy()
+        out = Rollout(log["x_log"].numpy(), log["u_log"].numpy(), log["status_log"].numpy(), log["iters_log"].numpy())
+        if dimg is not None:
+            s = self.cfg.sensor
+            pts = _lib.FieldView(log["pts_log"].data_ptr(), (Bn * (K + 1), 3), np.float32, ctx)
+            lab = _lib.DeviceArray(ctx, (Bn * (K + 1),), np.uint8)
+            _lib.colcheck(ctx, _lib.img_opts(s.dmax, s.hfov, s.vfov, s.is_depth, s.is_spherical), _lib.OUTSIDE[outside],
+                          safe_ball_size, _lib.FieldView(dimg.data_ptr(), ishape, np.float32, ctx), pts, None, lab)
+            out.col = lab.numpy().astype(bool).reshape(Bn, K + 1)  # point j belongs to image j / (K + 1)
+            out.pts = log["pts_log"].numpy()
+        self.x0 = out.x[:, -1].copy() if self.B > 1 else out.x[0, -1].copy()
+        ocp = self.ocp
+        ocp.status, ocp.iters = solver.status.copy(), solver.iters.copy()
+        ocp.fail_mask = ocp.status >= 2
+        ocp.u = u0[0] if self.B == 1 else u0
+        return out
+
+    def _dev_imgs(self, imgs):
+        """Range images [B, H, W] (or [H, W]) float32 on the device, and their 3-d shape."""
+        from . import _lib
+        Bn = max(self.B, 1)
+        if hasattr(imgs, "data_ptr"):
+            if np.dtype(str(imgs.dtype).replace("torch.", "")) != np.float32:
+                raise TypeError(f"device images must be float32, got {imgs.dtype}")
+            dimg = _lib.sync_producer(imgs)
+            shape = tuple(int(v) for v in imgs.shape)
+        else:
+            a = np.asarray(imgs, dtype=np.float32)
+            shape = a.shape
+            dimg = _lib.DeviceArray.from_numpy(self.ocp.ctx, a)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3:
+            raise AssertionError('input image must have size [B, H, W] or [H, W]')
+        if shape[0] != Bn:
+            raise ValueError(f"expected {Bn} images, got {shape[0]}")
+        return dimg, shape
+
     # ---- getters
     def get_matrices(self):
         """x [.., N+1, nx], u [.., N, nu] of the current iterate (controller.py:87-96)."""
@@ -227,21 +337,7 @@ class Nmpc:
         assert outside in _lib.OUTSIDE
         s, idx, ctx = self.cfg.sensor, self.cfg.mpc.p_idx, self.ocp.ctx
         Bn = max(self.B, 1)
-        if hasattr(imgs, "data_ptr"):
-            if np.dtype(str(imgs.dtype).replace("torch.", "")) != np.float32:
-                raise TypeError(f"device images must be float32, got {imgs.dtype}")
-            dimg = _lib.sync_producer(imgs)
-            shape = tuple(int(v) for v in imgs.shape)
-        else:
-            a = np.asarray(imgs, dtype=np.float32)
-            shape = a.shape
-            dimg = _lib.DeviceArray.from_numpy(ctx, a)
-        if len(shape) == 2:
-            shape = (1,) + shape
-        if len(shape) != 3:
-            raise AssertionError('input image must have size [B, H, W] or [H, W]')
-        if shape[0] != Bn:
-            raise ValueError(f"expected {Bn} images, got {shape[0]}")
+        dimg, shape = self._dev_imgs(imgs)
         x = self.ocp.download("x")
         p = self.p if self.B > 1 else self.p[None]
         W_R_Co = p[..., idx.W_R_Co].reshape(Bn, self.N + 1, 3, 3)

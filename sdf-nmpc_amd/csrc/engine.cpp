@@ -25,6 +25,7 @@
 #include "sdf_kernels.h"
 #include "vae_kernels.h"
 #include "df_kernels.h"
+#include "plant_kernels.h"
 
 using namespace sdfn;
 
@@ -1743,6 +1744,46 @@ extern "C" int sdfnmpc_rti_apply(sdfnmpc_ctx* ctx, int B, int N, double* x, doub
     ScopedDevice sd(ctx->device);
     HIPCHK(timed(ctx, "rti_apply", [&] { return launch_rti_apply(B, N, x, u, dx, du, u0, status, ctx->stream); }));
     return SDFNMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the plant of a closed loop (plant.hip).  sdfnmpc_plant_args_ checks the options and fills the kernel's
+// argument block (nothing is launched); sdfnmpc_plant_launch_ launches a filled block on the context stream,
+// timed as "plant".  Both are shared with sdfnmpc_solver_rollout (solver.hip), which adds the log pointers.
+extern "C" int sdfnmpc_plant_args_(const sdfnmpc_plant_opts* o, int B, const double* x, const double* u, double* x_next,
+                                   PlantArgs* out) {
+    if (!o || !out || B < 0 || (B > 0 && (!x || !u || !x_next)))
+        return fail(SDFNMPC_E_ARG, "plant: NULL argument or B < 0");
+    if (o->kind != SDFNMPC_MODEL_ATT && o->kind != SDFNMPC_MODEL_ATT_TAU)
+        return fail(SDFNMPC_E_UNSUPPORTED, "plant opts: kind: only 0 ('att') and 1 ('att_tau') are built");
+    if (o->substeps < 1 || o->substeps > PLANT_MAX_SUBSTEPS) return fail(SDFNMPC_E_ARG, "plant opts: substeps must be 1..64");
+    if (!(o->dt > 0.0)) return fail(SDFNMPC_E_ARG, "plant opts: dt must be > 0");
+    if (o->kind == SDFNMPC_MODEL_ATT_TAU && (!(o->tau_roll > 0.0) || !(o->tau_pitch > 0.0)))
+        return fail(SDFNMPC_E_ARG, "plant opts: kind 1 ('att_tau') needs tau_roll > 0 and tau_pitch > 0");
+    PlantArgs a{};
+    a.B = B; a.kind = o->kind; a.substeps = o->substeps;
+    a.gamma = o->gamma; a.roll = o->roll; a.pitch = o->pitch; a.wz = o->wz; a.g = o->g; a.dt = o->dt;
+    if (o->kind == SDFNMPC_MODEL_ATT_TAU) {
+        a.itau_roll = 1.0 / o->tau_roll;
+        a.itau_pitch = 1.0 / o->tau_pitch;
+    }
+    a.x = x; a.u = u; a.x_next = x_next; a.acc_dist = o->acc_dist; a.gamma_scale = o->gamma_scale;
+    *out = a;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_plant_launch_(sdfnmpc_ctx* ctx, const PlantArgs* a) {
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "plant", [&] { return launch_plant(*a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_plant_step(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* o, int B, const double* x, const double* u,
+                                  double* x_next) {
+    if (!ctx) return fail(SDFNMPC_E_ARG, "NULL context");
+    PlantArgs a{};
+    if (int rc = sdfnmpc_plant_args_(o, B, x, u, x_next, &a)) return rc;
+    return sdfnmpc_plant_launch_(ctx, &a);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -14,8 +14,14 @@
 #include <vector>
 
 #include "../../include/sdfnmpc.h"
+#include "plant_kernels.h"
+#include "ref_kernels.h"
 
 extern "C" int sdfnmpc_solver_fail_(int code, const char* msg);  // engine.cpp: sets sdfnmpc_last_error
+// engine.cpp: the plant's option check + argument block, and its launch on the context stream (timed as "plant")
+extern "C" int sdfnmpc_plant_args_(const sdfnmpc_plant_opts* o, int B, const double* x, const double* u, double* x_next,
+                                   sdfn::PlantArgs* out);
+extern "C" int sdfnmpc_plant_launch_(sdfnmpc_ctx* ctx, const sdfn::PlantArgs* a);
 
 namespace {
 
@@ -327,9 +333,8 @@ extern "C" int sdfnmpc_solver_shift(sdfnmpc_solver* s, int k) {
     return SDFNMPC_OK;
 }
 
-extern "C" int sdfnmpc_solver_step(sdfnmpc_solver* s) {
-    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
-    SolverDevice sd(s->device);
+// one SQP-RTI iteration on the solver's buffers, enqueued; u0 / status / iters stay on the device
+static int step_enqueue(sdfnmpc_solver* s) {
     const size_t n1 = s->N + 1;
     // x_0 of the iterate = the measured state (Ocp.solve: solver.set(0, 'x', x0), ocp.py:161)
     SCHK(hipMemcpy2DAsync(s->x, n1 * 80, s->x0, 80, 80, s->B, hipMemcpyDeviceToDevice, s->stream));
@@ -350,8 +355,53 @@ extern "C" int sdfnmpc_solver_step(sdfnmpc_solver* s) {
     rc = sdfnmpc_qp_feedback(s->ctx, &s->qp, &qa);                             // feedback
     if (rc) return rc;
     rc = sdfnmpc_rti_apply(s->ctx, s->B, s->N, s->x, s->u, s->dx, s->du, s->u0, s->status);
-    if (rc) return rc;
+    return rc;
+}
+
+extern "C" int sdfnmpc_solver_step(sdfnmpc_solver* s) {
+    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
+    SolverDevice sd(s->device);
+    if (int rc = step_enqueue(s)) return rc;
     SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // u0, status, iters
+    s->pending = true;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a) {
+    if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout");
+    if (a->steps < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
+    if (!a->x_log || !a->u_log) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: x_log and u_log are required");
+    // every refusal before the first launch: the plant's options, then what sdfnmpc_pack_refs would refuse
+    sdfn::PlantArgs pa{};
+    if (int rc = sdfnmpc_plant_args_(&a->plant, s->B, s->x0, s->u0, s->x0, &pa)) return rc;
+    sdfnmpc_ref_args ra{};
+    if (a->ref) {
+        const int mode = a->ref->mode;
+        if (mode < 0 || mode > 2) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref->mode must be 0, 1 or 2");
+        if (!a->wrow) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref needs wrow");
+        if (mode == 0 && (a->n_wp < 1 || a->n_wp > sdfn::RP_MAX_WP || !a->wp_p || !a->wp_q))
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref mode 0 needs 1..32 waypoints (wp_p, wp_q)");
+        if (mode == 1 && !a->vw) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref mode 1 needs vw");
+        ra.B = s->B; ra.N = s->N; ra.np = s->np; ra.ny = s->ny; ra.n_wp = mode == 0 ? a->n_wp : 0;
+        ra.x0 = s->x0; ra.x0_stride = 10;
+        ra.wp_p = a->wp_p; ra.wp_q = a->wp_q; ra.vw = a->vw; ra.wrow = a->wrow;
+        ra.p = s->p; ra.yref = s->yref; ra.W = s->W; ra.yNref = s->yNref; ra.WN = s->WN; ra.nyN = s->nyN;
+    }
+    pa.K = a->steps;
+    pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
+    pa.pts_log = a->pts_log;
+    pa.status = s->status; pa.iters = s->iters;
+    pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
+    SolverDevice sd(s->device);
+    for (int k = 0; k < a->steps; ++k) {
+        if (a->ref)
+            if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
+        if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
+        if (int rc = step_enqueue(s)) return rc;
+        pa.k = k;
+        if (int rc = sdfnmpc_plant_launch_(s->ctx, &pa)) return rc;
+    }
+    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
     s->pending = true;
     return SDFNMPC_OK;
 }
