@@ -47,6 +47,13 @@
  *   sdfnmpc_udf / sdfnmpc_sdf_truth    DfComputer.get_udf / get_sdf (utils/df_computer.py:85-221): the distance
  *                                      field the image itself implies, to label data and to score a network
  *
+ *   sdfnmpc_scene_*                    (no reference interface: the reference's images come from the simulator it is
+ *                                      run against) range / depth images of an analytic scene from a camera pose,
+ *                                      the camera pose of a state (controller.py:52-53), the exact signed distance
+ *   sdfnmpc_solver_rollout_perceive    sdfnmpc_solver_rollout with the perception a user wraps around it every
+ *                                      control period: VaeWrapper.set_img / encode (sdf_nmpc/vae.py:29-40) of a new
+ *                                      image and Nmpc.set_latent (controller.py:50-54) with the pose at image time
+ *
  * The CasADi external-function symbols that acados links (sdf_l4c, jac_sdf_l4c, ...) are in
  * sdf_l4c.h / libsdf_l4c.so.
  */
@@ -60,7 +67,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 9
+#define SDFNMPC_ABI_VERSION 10
 
 enum {
     SDFNMPC_OK = 0,
@@ -290,7 +297,8 @@ long long sdfnmpc_qp_capacity_for(const sdfnmpc_ctx* ctx, int N, const sdfnmpc_q
 int sdfnmpc_ctx_set_tile_rows(sdfnmpc_ctx* ctx, int rows);
 /* per-kernel HIP-event timing on the context stream (off by default) */
 int sdfnmpc_ctx_enable_timing(sdfnmpc_ctx* ctx, int on);
-/* kernel: "sdf_mlp", "sdf_hoist", "linearize", "rti_qp", "plant", ...; synchronizes the stream(s) */
+/* kernel: "sdf_mlp", "sdf_hoist", "linearize", "rti_qp", "plant", "scene_render", "scene_pose", "scene_dist", ...;
+ * synchronizes the stream(s) */
 int sdfnmpc_ctx_kernel_stats(sdfnmpc_ctx* ctx, const char* kernel, double* total_ms, long long* launches);
 int sdfnmpc_ctx_reset_stats(sdfnmpc_ctx* ctx);
 
@@ -527,6 +535,92 @@ typedef struct {
 } sdfnmpc_rollout_args;
 
 int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args);
+
+/* ---- analytic scenes (csrc/scene.hip) ----
+ * A scene is a union of up to SDFNMPC_SCENE_MAX_PRIMS primitives in the world frame (z up, as in the models):
+ *   SDFNMPC_PRIM_SPHERE    a = (cx, cy, cz, r)
+ *   SDFNMPC_PRIM_BOX       a = (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z), axis-aligned
+ *   SDFNMPC_PRIM_CYLINDER  a = (cx, cy, r, z0, z1), capped, along z
+ * sdfnmpc_scene_create copies S scenes to the context's device (host arrays: count [S] primitives per scene, prims
+ * [sum of count] scene after scene; synchronous).  It is where a scene is checked -- SDFNMPC_E_ARG for S < 1, a
+ * count outside 0..32, an unknown kind, a radius <= 0, lo >= hi or z0 >= z1, a non-finite value -- so no launch
+ * ever sees a malformed scene.  A launch names the scene of each instance by scene_of [B] (device int32; NULL: every
+ * instance uses scene 0).  Its entries are the caller's responsibility, as p_to_i above (a kernel clamps them into
+ * [0, S)). */
+#define SDFNMPC_SCENE_MAX_PRIMS 32
+#define SDFNMPC_PRIM_SPHERE 0
+#define SDFNMPC_PRIM_BOX 1
+#define SDFNMPC_PRIM_CYLINDER 2
+typedef struct {
+    int kind;
+    double a[6];
+} sdfnmpc_prim;
+typedef struct sdfnmpc_scene sdfnmpc_scene;
+int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims, sdfnmpc_scene** out);
+void sdfnmpc_scene_free(sdfnmpc_scene* scene);
+
+/* img [B][H][W] (device float32) = the image instance b's camera takes of its scene: per pixel the nearest hit t >= 0
+ * of the ray through the pixel centre of colcheck's pixel grid (collision_checker.py:80-84; camera frame x forward,
+ * y left, z up) -- pinhole d_c ~ (1, tan(hfov) (1 - (2u+1)/W), tan(vfov) (1 - (2v+1)/H)), spherical azimuth hfov (1 -
+ * (2u+1)/W) and elevation vfov (1 - (2v+1)/H) -- written as min(val, dmax) * scale with val = t (range) or, with
+ * opts->is_depth, t d_c.x for unit d_c; a miss gives dmax * scale.  scale = 1 / dmax: the normalised image
+ * sdfnmpc_colcheck / sdfnmpc_udf read; scale = 1000 / mm_resolution: the raw sensor image sdfnmpc_vae_encode expects.
+ * A camera inside a primitive sees t = 0 everywhere: the all-zero image colcheck reads as collision.  The pose
+ * W_p_C [B][3], W_R_C [B][9] (device float64, row-major: world = W_R_C cam + W_p_C) is rounded to fp32 once; the
+ * image is computed in fp32 without atomics, bitwise reproducible and independent of the instance's place in the
+ * batch.  Asynchronous on the context stream; B == 0 is a no-op.  SDFNMPC_E_ARG (nothing is launched, img untouched):
+ * NULL arguments, B < 0 or > 65535, H or W < 1 (or H W beyond 2^31 - 1), non-positive or non-finite dmax / hfov / vfov
+ * / scale, pinhole with hfov or vfov >= pi / 2, a spherical image with H + W > 6144, a scene on another device. */
+int sdfnmpc_scene_render(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const int* scene_of, const sdfnmpc_img_opts* opts,
+                         int H, int W, float scale, int B, const double* W_p_C, const double* W_R_C, float* img);
+/* The poses of B states x [B][10] (device float64; position x[0..2], quaternion x[3..6] = (w, x, y, z), not
+ * necessarily normalised): W_p_Bo [B][3] = x[0..2], W_R_Bo [B][9] = quat2rot(q / |q|) (utils/math.py:7-23), and the
+ * camera pose W_p_C = W_R_Bo B_p_C + W_p_Bo, W_R_C = W_R_Bo B_R_C (controller.py:52-53; B_p_C [3], B_R_C [9] host,
+ * row-major).  fp64, asynchronous; B == 0 is a no-op.  SDFNMPC_E_ARG: NULL arguments, B < 0. */
+int sdfnmpc_scene_pose(sdfnmpc_ctx* ctx, const double* B_p_C, const double* B_R_C, int B, const double* x, double* W_p_Bo,
+                       double* W_R_Bo, double* W_p_C, double* W_R_C);
+/* out [n] (device float64) = the signed distance from world point points [n][3] (device float64) to its scene: the
+ * minimum over the primitives of the closed-form sphere, box and capped-cylinder distances, negative inside (exact
+ * outside the union).  p_to_scene [n] (device int32) names each point's scene; NULL: the default ordering of
+ * sdfnmpc_colcheck's p_to_i, point j -> scene j / (n / S) (n must then be a multiple of S).  A scene without
+ * primitives gives +inf.  fp64, asynchronous; n == 0 is a no-op.  SDFNMPC_E_ARG: NULL arguments, n < 0 or beyond
+ * 2^31 - 1, NULL p_to_scene with n % S != 0. */
+int sdfnmpc_scene_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const double* points, const int* p_to_scene,
+                           long long n, double* out);
+
+/* sdfnmpc_solver_rollout with perception inside the loop.  Before step k with (k + phase) % every == 0 it enqueues, on the
+ * solver's stream and in this order: (a) sdfnmpc_scene_pose from the solver's x0 field; (b) sdfnmpc_scene_render of
+ * every instance's scene from that camera pose; (c) sdfnmpc_vae_encode of the images; (d) sdfnmpc_pack_refs in mode -1
+ * with that latent and body pose (Nmpc.set_latent on the device; the sdf flag is untouched).  Then the step's
+ * sequence of sdfnmpc_solver_rollout.  Still a plain launch sequence: no graph, no host synchronisation and no copy
+ * inside the loop.  perc == NULL is sdfnmpc_solver_rollout.  The workspaces are the caller's and hold the last
+ * perception afterwards.  pts_log keeps its meaning, the camera frame of node 0's pose parameters at the time of
+ * logging: with perception that is the frame of the latest image (row k + 1 is logged after step k, in the frame of
+ * the image taken at or before step k).
+ * SDFNMPC_E_ARG, all before the first launch: what sdfnmpc_solver_rollout, sdfnmpc_scene_render, sdfnmpc_scene_pose,
+ * sdfnmpc_vae_encode and sdfnmpc_pack_refs refuse, every < 1, phase < 0, a NULL workspace, an encoder or a scene that does not
+ * live on the solver's context, a latent size that does not fit the solver's parameter row (17 + L > np). */
+typedef struct {
+    const sdfnmpc_scene* scene;
+    const int* scene_of;           /* device [B] or NULL */
+    sdfnmpc_img_opts img;          /* the sensor */
+    int h, w;                      /* rendered image size (the encoder resizes when its own differs) */
+    float scale;                   /* as sdfnmpc_scene_render: the raw sensor image, 1000 / mm_resolution */
+    double B_p_C[3], B_R_C[9];     /* sensor extrinsics */
+    sdfnmpc_vae* vae;              /* loaded on the solver's context */
+    sdfnmpc_vae_opts vae_opts;     /* clip and yz; B, in_h, in_w and dtype are set by the rollout (B, h, w, float32) */
+    int every;                     /* >= 1: a new image before every `every`-th step, starting with step 0 */
+    int phase;                     /* >= 0: steps already taken since the schedule began -- a new image before step k
+                                      when (k + phase) % every == 0, so that a rollout cut into chunks perceives
+                                      where the uncut one does (0: before step 0) */
+    float* images;                 /* device workspaces: [B][h][w] */
+    float* latent;                 /* [B][L] */
+    double* latent64;              /* [B][L] */
+    double *W_p_Bo, *W_R_Bo, *W_p_C, *W_R_C; /* [B][3], [B][9], [B][3], [B][9] */
+} sdfnmpc_perceive_args;
+
+int sdfnmpc_solver_rollout_perceive(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
+                                    const sdfnmpc_perceive_args* perc);
 
 /* ---- shooting grid (host, bit-exact numpy.linspace/diff semantics of ocp.py:21-27) ---- */
 int sdfnmpc_shooting_grid(int N, double T, int uniform, int nb_short_nodes, double dt_short, double* nodes,

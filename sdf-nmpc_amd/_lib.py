@@ -36,6 +36,8 @@ SYMBOLS = [
     "sdfnmpc_solver_create", "sdfnmpc_solver_destroy", "sdfnmpc_solver_field", "sdfnmpc_solver_upload",
     "sdfnmpc_solver_download", "sdfnmpc_solver_init", "sdfnmpc_solver_shift", "sdfnmpc_solver_step",
     "sdfnmpc_solver_wait", "sdfnmpc_plant_step", "sdfnmpc_solver_rollout",
+    "sdfnmpc_scene_create", "sdfnmpc_scene_free", "sdfnmpc_scene_render", "sdfnmpc_scene_pose",
+    "sdfnmpc_scene_distance", "sdfnmpc_solver_rollout_perceive",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -133,6 +135,21 @@ class RolloutArgsC(C.Structure):
         (n, C.c_void_p) for n in ("x_log", "u_log", "status_log", "iters_log", "pts_log")]
 
 
+SCENE_MAX_PRIMS = 32  # SDFNMPC_SCENE_MAX_PRIMS
+PRIM_KINDS = {"sphere": 0, "box": 1, "cylinder": 2}  # SDFNMPC_PRIM_*
+
+
+class PrimC(C.Structure):
+    _fields_ = [("kind", C.c_int), ("a", C.c_double * 6)]
+
+
+class PerceiveArgsC(C.Structure):
+    _fields_ = [("scene", C.c_void_p), ("scene_of", C.c_void_p), ("img", ImgOptsC), ("h", C.c_int), ("w", C.c_int),
+                ("scale", C.c_float), ("B_p_C", C.c_double * 3), ("B_R_C", C.c_double * 9), ("vae", C.c_void_p),
+                ("vae_opts", VaeOptsC), ("every", C.c_int), ("phase", C.c_int)] + [
+        (n, C.c_void_p) for n in ("images", "latent", "latent64", "W_p_Bo", "W_R_Bo", "W_p_C", "W_R_C")]
+
+
 _lib = None
 
 
@@ -210,11 +227,17 @@ def load():
         "sdfnmpc_solver_wait": (i, [vp, vp, vp, vp]),
         "sdfnmpc_plant_step": (i, [vp, P(PlantOptsC), i, vp, vp, vp]),
         "sdfnmpc_solver_rollout": (i, [vp, P(RolloutArgsC)]),
+        "sdfnmpc_scene_create": (i, [vp, i, P(i), P(PrimC), P(vp)]),
+        "sdfnmpc_scene_free": (None, [vp]),
+        "sdfnmpc_scene_render": (i, [vp, vp, vp, P(ImgOptsC), i, i, f, i, vp, vp, vp]),
+        "sdfnmpc_scene_pose": (i, [vp, P(d), P(d), i, vp, vp, vp, vp, vp]),
+        "sdfnmpc_scene_distance": (i, [vp, vp, vp, vp, ll, vp]),
+        "sdfnmpc_solver_rollout_perceive": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 9:
+    if lib.sdfnmpc_abi_version() != 10:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -646,6 +669,41 @@ def sdf_truth(ctx: Context, opts: ImgOptsC, min_df: float, max_df: float, grid, 
                                     int(points.shape[0]), _ptr(out_sdf), _ptr(out_grad), _ptr(vox_idx)))
 
 
+# ---- analytic scenes (csrc/scene.hip); the user-facing object is sdf_nmpc_amd.scene.Scene ----
+def scene_create(ctx: "Context", counts, prims):
+    """sdfnmpc_scene_create: counts [S] primitives per scene, prims a flat list of (kind, values) scene after
+    scene.  Returns the handle; the C entry point refuses malformed scenes."""
+    cn = (C.c_int * len(counts))(*[int(c) for c in counts])
+    pr = (PrimC * max(len(prims), 1))()
+    for k, (kind, vals) in enumerate(prims):
+        pr[k].kind = int(kind)
+        for j, v in enumerate(vals):
+            pr[k].a[j] = float(v)
+    h = C.c_void_p()
+    _check(load().sdfnmpc_scene_create(ctx.h, len(counts), cn, pr, C.byref(h)))
+    return h
+
+
+def scene_render(ctx: "Context", scene_h, scene_of, opts: ImgOptsC, H: int, W: int, scale: float, B: int, W_p_C, W_R_C,
+                 img):
+    """Enqueue sdfnmpc_scene_render: W_p_C [B][3], W_R_C [B][9] device float64 -> img [B][H][W] device float32."""
+    _check(load().sdfnmpc_scene_render(ctx.h, scene_h, _ptr(scene_of), C.byref(opts), int(H), int(W), float(scale),
+                                       int(B), _ptr(W_p_C), _ptr(W_R_C), _ptr(img)))
+
+
+def scene_pose(ctx: "Context", B_p_C, B_R_C, B: int, x, W_p_Bo, W_R_Bo, W_p_C, W_R_C):
+    """Enqueue sdfnmpc_scene_pose: x [B][10] device float64 -> body and camera poses (device float64)."""
+    pv = (C.c_double * 3)(*[float(v) for v in np.asarray(B_p_C, dtype=float).ravel()])
+    rv = (C.c_double * 9)(*[float(v) for v in np.asarray(B_R_C, dtype=float).ravel()])
+    _check(load().sdfnmpc_scene_pose(ctx.h, pv, rv, int(B), _ptr(x), _ptr(W_p_Bo), _ptr(W_R_Bo),
+                                     _ptr(W_p_C), _ptr(W_R_C)))
+
+
+def scene_distance(ctx: "Context", scene_h, points, p_to_scene, n: int, out):
+    """Enqueue sdfnmpc_scene_distance: points [n][3] device float64 -> out [n] device float64."""
+    _check(load().sdfnmpc_scene_distance(ctx.h, scene_h, _ptr(points), _ptr(p_to_scene), int(n), _ptr(out)))
+
+
 # ---- the plant of a closed loop (csrc/plant.hip) ----
 class PlantOpts:
     """sdfnmpc_plant_opts with its per-instance mismatch arrays (host arrays are uploaded once per context, at
@@ -837,16 +895,22 @@ class Solver:
         _check(load().sdfnmpc_solver_step(self.h))
 
     def rollout(self, steps: int, plant: PlantOpts, x_log, u_log, status_log=None, iters_log=None, pts_log=None,
-                shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0):
+                shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0,
+                perceive: "PerceiveArgsC" = None):
         """Enqueue sdfnmpc_solver_rollout: `steps` closed-loop steps (references from x0 when ref is given,
         shift, RTI step, plant) from the x0 field, logged into the device arrays x_log [B][K+1][10], u_log
         [B][K][4], status_log / iters_log [B][K] int32 and pts_log [B][K+1][3] float32.  Asynchronous: `wait`
-        finishes it (the arrays are kept alive until then)."""
+        finishes it (the arrays are kept alive until then).  perceive: a PerceiveArgsC -- a new image, latent and
+        pose before every `every`-th step (sdfnmpc_solver_rollout_perceive); the caller keeps what it names alive."""
         a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
                          _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
                          _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
         self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log)
-        _check(load().sdfnmpc_solver_rollout(self.h, C.byref(a)))
+        if perceive is None:
+            _check(load().sdfnmpc_solver_rollout(self.h, C.byref(a)))
+        else:
+            self._rollout_keep += (perceive,)
+            _check(load().sdfnmpc_solver_rollout_perceive(self.h, C.byref(a), C.byref(perceive)))
 
     def wait(self):
         _check(load().sdfnmpc_solver_wait(self.h, self.u0.ctypes.data, self.status.ctypes.data, self.iters.ctypes.data))

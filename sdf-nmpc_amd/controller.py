@@ -31,10 +31,13 @@ from .model import Quad
 class Rollout:
     """What ``Nmpc.rollout`` logged (numpy arrays, batch-leading): x [B, K+1, 10] plant states (row 0 the start),
     u [B, K, 4] applied inputs, status / iters [B, K] of every QP; with images also col [B, K+1] collision labels
-    and pts [B, K+1, 3] the camera-frame positions they were taken at (else None)."""
+    and pts [B, K+1, 3] the camera-frame positions they were taken at (else None); with a scene clearance [B, K+1],
+    the exact signed distance of every logged position to the instance's scene, and with keep_img img [B, h, w]
+    float32, the last images rendered (raw sensor values)."""
 
-    def __init__(self, x, u, status, iters, col=None, pts=None):
+    def __init__(self, x, u, status, iters, col=None, pts=None, clearance=None, img=None):
         self.x, self.u, self.status, self.iters, self.col, self.pts = x, u, status, iters, col, pts
+        self.clearance, self.img = clearance, img
 
 
 class Nmpc:
@@ -168,7 +171,8 @@ class Nmpc:
         return self.fail_count
 
     def rollout(self, steps, refs=None, wps=None, vw=None, weights=None, plant=None, imgs=None, safe_ball_size=0.0,
-                outside='col'):
+                outside='col', scene=None, vae=None, perceive_every=1, img_shape=None, keep_img=False,
+                perceive_phase=0):
         """``steps`` closed-loop control steps on the device, without a host round trip between them: per
         step the references from the current state (``refs``), the shift (mpc.shift), one SQP-RTI iteration
         and the plant advanced by u_0 -- the loop ``set_x0``; ``gen_refs_device``; ``solve``; simulate,
@@ -182,6 +186,18 @@ class Nmpc:
         imgs: float32 [B, H, W] range images normalised by sensor.dmax (host or device, as
         ``check_openloop_traj``): every logged plant position is labelled against its instance's image in one
         launch of the collision-check kernel after the loop, in the camera frame of node 0's pose parameters.
+
+        scene: a ``scene.Scene`` on the controller's context -- perception inside the loop.  Before every
+        ``perceive_every``-th step (starting with the first) each instance's camera pose is taken from its plant
+        state, its scene is rendered from there as a raw sensor image of ``img_shape`` (h, w; default
+        sensor.shape_imgs[-2:]), ``vae`` (a ``VaeWrapper`` built with ``ctx=nmpc.ocp.ctx`` and ``batch=B``) encodes
+        it and the latent and the body pose go into p as ``set_latent`` writes them (the sdf flag stays): the loop
+        ``render_from_state``; ``set_img``; ``encode_to`` a user writes in front of each step, without leaving the
+        device (sdfnmpc_solver_rollout_perceive, csrc/scene.hip).  The result gains ``clearance`` [B, K+1], the
+        exact signed distance of every logged position to the scene (one launch after the loop), and with
+        ``keep_img`` the last rendered images.  ``perceive_phase``: steps already taken since the schedule began
+        (an image before step k when (k + phase) % perceive_every == 0), so that a rollout cut into chunks
+        perceives where the uncut one does.  ``scene`` excludes ``imgs`` (the image changes inside the loop).
 
         Returns a ``Rollout`` of numpy arrays, batch-leading also for one instance: x [B, K+1, 10] (row 0 the
         start), u [B, K, 4], status / iters [B, K]; with imgs also col [B, K+1] bool and pts [B, K+1, 3] float32.
@@ -200,6 +216,22 @@ class Nmpc:
         K, Bn, ctx, solver = int(steps), max(self.B, 1), self.ocp.ctx, self.ocp.parts[0].solver
         if K < 1:
             raise ValueError(f"rollout of {K} steps: at least one")
+        if scene is None:
+            if vae is not None:
+                raise ValueError("rollout(): vae is the encoder of a scene's images; give scene too")
+        else:  # every refusal before anything is uploaded or enqueued
+            if vae is None:
+                raise ValueError("rollout(): scene needs vae (a VaeWrapper on the controller's context)")
+            if imgs is not None:
+                raise ValueError("rollout(): scene and imgs exclude each other (the image changes inside the loop)")
+            if vae.ctx is not ctx or scene.ctx is not ctx:
+                raise ValueError("rollout(): the scene and the VaeWrapper must be built on the controller's context "
+                                 "(ctx=nmpc.ocp.ctx)")
+            if vae.B != Bn:
+                raise ValueError(f"rollout(): the VaeWrapper encodes {vae.B} images, the batch has {Bn}")
+            if int(perceive_every) < 1 or int(perceive_phase) < 0:
+                raise ValueError(f"perceive_every {perceive_every} / perceive_phase {perceive_phase}: at least 1 / 0")
+            scene._batch(Bn)
         kw = {}
         if refs is not None:
             code = {"wps": 0, "joystick": 1, "hover": 2}[refs]
@@ -217,6 +249,22 @@ class Nmpc:
                 kw["vw"] = self._dev(np.reshape(np.asarray(vw, float), (Bn, 4)))
         if plant is None:
             plant = _lib.plant_opts(self.cfg, dt=float(self.ocp.dt[0]))
+        perc = None
+        if scene is not None:
+            ih, iw = (int(v) for v in (img_shape if img_shape is not None else self.cfg.sensor.shape_imgs[-2:]))
+            ws = {"images": _lib.DeviceArray(ctx, (Bn, ih, iw), np.float32)}
+            ws.update({k: _lib.DeviceArray(ctx, (Bn, n)) for k, n in (("W_p_Bo", 3), ("W_R_Bo", 9), ("W_p_C", 3),
+                                                                     ("W_R_C", 9))})
+            sens = self.cfg.sensor
+            vo = _lib.VaeOptsC(Bn, ih, iw, 0, float(vae.opts.clip), _lib._ptr(vae.yz) if vae.depth2range else None)
+            perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(self.cfg), ih, iw,
+                                      scene.scale(self.cfg, normalized=False),
+                                      (_lib.C.c_double * 3)(*[float(v) for v in np.asarray(sens.B_p_C, float).ravel()]),
+                                      (_lib.C.c_double * 9)(*[float(v) for v in np.asarray(sens.B_R_C, float).ravel()]),
+                                      vae.vae.h, vo, int(perceive_every), int(perceive_phase), ws["images"].data_ptr(), vae.latent.data_ptr(),
+                                      vae.latent64.data_ptr(), *[ws[k].data_ptr() for k in ("W_p_Bo", "W_R_Bo", "W_p_C",
+                                                                                            "W_R_C")])
+            kw["perceive"] = perc
         dimg = None
         if imgs is not None:
             dimg, ishape = self._dev_imgs(imgs)
@@ -240,6 +288,12 @@ class Nmpc:
                           safe_ball_size, _lib.FieldView(dimg.data_ptr(), ishape, np.float32, ctx), pts, None, lab)
             out.col = lab.numpy().astype(bool).reshape(Bn, K + 1)  # point j belongs to image j / (K + 1)
             out.pts = log["pts_log"].numpy()
+        if perc is not None:  # one launch over the logged positions; point j belongs to instance j // (K + 1)
+            p2s = None if scene.S == 1 else np.repeat(scene.scene_of if scene.scene_of is not None else
+                                                      np.zeros(Bn, np.int32), K + 1)
+            out.clearance = scene.distance(np.ascontiguousarray(out.x[:, :, :3]).reshape(-1, 3), p2s).reshape(Bn, K + 1)
+            if keep_img:
+                out.img = ws["images"].numpy()
         self.x0 = out.x[:, -1].copy() if self.B > 1 else out.x[0, -1].copy()
         ocp = self.ocp
         ocp.status, ocp.iters = solver.status.copy(), solver.iters.copy()

@@ -26,6 +26,7 @@
 #include "vae_kernels.h"
 #include "df_kernels.h"
 #include "plant_kernels.h"
+#include "scene_kernels.h"
 
 using namespace sdfn;
 
@@ -1826,6 +1827,7 @@ struct VaeLayer {
 
 struct sdfnmpc_vae {
     int device = 0;
+    const sdfnmpc_ctx* ctx = nullptr;  // the context it was loaded on (sdfnmpc_solver_rollout_perceive asks)
     int L = 0, H = 0, W = 0;
     int Hc = 0, Wc = 0, Hp = 0, Wp = 0;
     int bh[4] = {0}, bw[4] = {0};  // block output maps
@@ -1856,6 +1858,7 @@ extern "C" int sdfnmpc_vae_load(sdfnmpc_ctx* ctx, const void* blob, size_t bytes
     const float* src = (const float*)((const char*)blob + sizeof(Hdr));
     auto* v = new sdfnmpc_vae();
     v->device = ctx->device;
+    v->ctx = ctx;
     v->L = (int)h.L; v->H = (int)h.H; v->W = (int)h.W;
     v->Hc = (v->H - 1) / 2 + 1; v->Wc = (v->W - 1) / 2 + 1;
     v->Hp = (v->Hc - 1) / 2 + 1; v->Wp = (v->Wc - 1) / 2 + 1;
@@ -2131,5 +2134,173 @@ extern "C" int sdfnmpc_sdf_truth(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* o, fl
     a.vox_idx = vox_idx;
     ScopedDevice sd(ctx->device);
     HIPCHK(timed(ctx, "sdf_grid", [&] { return launch_sdf_grid(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// analytic scenes (scene.hip)
+struct sdfnmpc_scene {
+    int device = 0;
+    const sdfnmpc_ctx* ctx = nullptr;
+    int S = 0;
+    void* dmem = nullptr;  // count [S] | ScenePrimD [S][32] | ScenePrimF [S][32]
+    SceneDev dev{};
+};
+
+extern "C" int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
+                                    sdfnmpc_scene** out) {
+    if (!ctx || !count || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create");
+    *out = nullptr;
+    if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "scene: S must be 1..2^20");
+    long long total = 0;
+    for (int s = 0; s < S; ++s) {
+        if (count[s] < 0 || count[s] > SCENE_MAX_PRIMS)
+            return fail(SDFNMPC_E_ARG, "scene: at most 32 primitives per scene (and no negative count)");
+        total += count[s];
+    }
+    if (total > 0 && !prims) return fail(SDFNMPC_E_ARG, "scene: NULL primitives");
+    // the device image: counts padded to 16 bytes, then the fp64 and the fp32 primitives at a fixed stride of 32
+    const size_t cnt_bytes = ((size_t)S * sizeof(int) + 15) & ~(size_t)15;
+    const size_t n = (size_t)S * SCENE_MAX_PRIMS;
+    std::vector<char> host(cnt_bytes + n * (sizeof(ScenePrimD) + sizeof(ScenePrimF)), 0);
+    int* hc = (int*)host.data();
+    ScenePrimD* hd = (ScenePrimD*)(host.data() + cnt_bytes);
+    ScenePrimF* hf = (ScenePrimF*)(host.data() + cnt_bytes + n * sizeof(ScenePrimD));
+    const sdfnmpc_prim* p = prims;
+    for (int s = 0; s < S; ++s) {
+        hc[s] = count[s];
+        for (int i = 0; i < count[s]; ++i, ++p) {
+            const double* a = p->a;
+            int na = 0;
+            bool ok = false;
+            if (p->kind == SDFNMPC_PRIM_SPHERE) { na = 4; ok = a[3] > 0.0; }
+            else if (p->kind == SDFNMPC_PRIM_BOX) { na = 6; ok = a[0] < a[3] && a[1] < a[4] && a[2] < a[5]; }
+            else if (p->kind == SDFNMPC_PRIM_CYLINDER) { na = 5; ok = a[2] > 0.0 && a[3] < a[4]; }
+            else return fail(SDFNMPC_E_ARG, "scene: unknown primitive kind (0 sphere, 1 box, 2 cylinder)");
+            for (int k = 0; k < na; ++k) ok = ok && std::isfinite(a[k]);
+            if (!ok) return fail(SDFNMPC_E_ARG, "scene: a primitive needs finite values, a radius > 0 and lo < hi");
+            ScenePrimD& d = hd[(size_t)s * SCENE_MAX_PRIMS + i];
+            ScenePrimF& f = hf[(size_t)s * SCENE_MAX_PRIMS + i];
+            d.kind = f.kind = p->kind;
+            for (int k = 0; k < na; ++k) {
+                d.a[k] = a[k];
+                f.a[k] = (float)a[k];
+            }
+        }
+    }
+    ScopedDevice sd(ctx->device);
+    auto* sc = new sdfnmpc_scene();
+    sc->device = ctx->device; sc->ctx = ctx; sc->S = S;
+    hipError_t e = hipMalloc(&sc->dmem, host.size());
+    if (e == hipSuccess) e = hipMemcpy(sc->dmem, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (sc->dmem) (void)hipFree(sc->dmem);
+        delete sc;
+        return fail(SDFNMPC_E_HIP, std::string("scene upload: ") + hipGetErrorString(e));
+    }
+    char* d = (char*)sc->dmem;
+    sc->dev = SceneDev{S, (const int*)d, (const ScenePrimF*)(d + cnt_bytes + n * sizeof(ScenePrimD)),
+                       (const ScenePrimD*)(d + cnt_bytes)};
+    *out = sc;
+    return SDFNMPC_OK;
+}
+
+extern "C" void sdfnmpc_scene_free(sdfnmpc_scene* sc) {
+    if (!sc) return;
+    ScopedDevice sd(sc->device);
+    if (sc->dmem) (void)hipFree(sc->dmem);
+    delete sc;
+}
+
+// whether an encoder / a scene lives on this very context (sdfnmpc_solver_rollout_perceive, solver.hip)
+extern "C" int sdfnmpc_vae_on_ctx_(const sdfnmpc_vae* v, const sdfnmpc_ctx* ctx) { return v && v->ctx == ctx; }
+extern "C" int sdfnmpc_scene_on_ctx_(const sdfnmpc_scene* sc, const sdfnmpc_ctx* ctx) { return sc && sc->ctx == ctx; }
+
+// the option checks of the two launches a rollout repeats, split from the launches as the plant's are: _args_
+// refuses or fills the kernel's argument block (nothing is launched), _launch_ enqueues a filled block
+extern "C" int sdfnmpc_scene_render_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of,
+                                          const sdfnmpc_img_opts* o, int H, int W, float scale, int B,
+                                          const double* W_p_C, const double* W_R_C, float* img, SceneRenderArgs* out) {
+    if (!ctx || !sc || !o || !out) return fail(SDFNMPC_E_ARG, "scene_render: NULL context, scene or options");
+    if (sc->device != ctx->device) return fail(SDFNMPC_E_ARG, "scene_render: the scene lives on another device");
+    if (B < 0 || B > 65535) return fail(SDFNMPC_E_ARG, "scene_render: B must be 0..65535");
+    if (H < 1 || W < 1 || (long long)H * W > 2147483647LL) return fail(SDFNMPC_E_ARG, "scene_render: bad image size");
+    auto pos = [](float v) { return v > 0.f && std::isfinite(v); };
+    if (!pos(o->dmax) || !pos(o->hfov) || !pos(o->vfov) || !pos(scale))
+        return fail(SDFNMPC_E_ARG, "scene_render: dmax, hfov, vfov and scale must be positive and finite");
+    const double half_pi = 1.5707963267948966;
+    if (!o->is_spherical && ((double)o->hfov >= half_pi || (double)o->vfov >= half_pi))
+        return fail(SDFNMPC_E_ARG, "scene_render: a pinhole image needs hfov and vfov below pi / 2");
+    if (scene_render_lds_bytes(H, W, o->is_spherical != 0) > SCENE_LDS_MAX)
+        return fail(SDFNMPC_E_ARG, "scene_render: spherical image too large (H + W <= 6144)");
+    if (B > 0 && (!W_p_C || !W_R_C || !img)) return fail(SDFNMPC_E_ARG, "scene_render: NULL pose or image");
+    SceneRenderArgs a{};
+    a.sc = sc->dev; a.scene_of = scene_of; a.B = B; a.H = H; a.W = W; a.W_p_C = W_p_C; a.W_R_C = W_R_C;
+    a.dmax = o->dmax; a.scale = scale; a.hfov = o->hfov; a.vfov = o->vfov;
+    a.is_depth = o->is_depth != 0; a.is_spherical = o->is_spherical != 0;
+    if (!a.is_spherical) {  // tangent coordinates of the pixel centres: t (1 - (2 i + 1) / n) = t (1 - 1 / n) - (2 t / n) i
+        const double th = std::tan((double)o->hfov), tv = std::tan((double)o->vfov);
+        a.ty0 = (float)(th * (1.0 - 1.0 / W)); a.ty1 = (float)(-2.0 * th / W);
+        a.tz0 = (float)(tv * (1.0 - 1.0 / H)); a.tz1 = (float)(-2.0 * tv / H);
+    }
+    a.img = img;
+    *out = a;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_render_launch_(sdfnmpc_ctx* ctx, const SceneRenderArgs* a) {
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "scene_render", [&] { return launch_scene_render(*a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_pose_args_(const double* B_p_C, const double* B_R_C, int B, const double* x, double* W_p_Bo,
+                                        double* W_R_Bo, double* W_p_C, double* W_R_C, ScenePoseArgs* out) {
+    if (!B_p_C || !B_R_C || !out) return fail(SDFNMPC_E_ARG, "scene_pose: NULL extrinsics");
+    if (B < 0) return fail(SDFNMPC_E_ARG, "scene_pose: B < 0");
+    if (B > 0 && (!x || !W_p_Bo || !W_R_Bo || !W_p_C || !W_R_C)) return fail(SDFNMPC_E_ARG, "scene_pose: NULL state or output");
+    ScenePoseArgs a{};
+    a.B = B; a.x = x;
+    for (int i = 0; i < 3; ++i) a.B_p_C[i] = B_p_C[i];
+    for (int i = 0; i < 9; ++i) a.B_R_C[i] = B_R_C[i];
+    a.W_p_Bo = W_p_Bo; a.W_R_Bo = W_R_Bo; a.W_p_C = W_p_C; a.W_R_C = W_R_C;
+    *out = a;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_pose_launch_(sdfnmpc_ctx* ctx, const ScenePoseArgs* a) {
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "scene_pose", [&] { return launch_scene_pose(*a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_render(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of,
+                                    const sdfnmpc_img_opts* o, int H, int W, float scale, int B, const double* W_p_C,
+                                    const double* W_R_C, float* img) {
+    SceneRenderArgs a{};
+    if (int rc = sdfnmpc_scene_render_args_(ctx, sc, scene_of, o, H, W, scale, B, W_p_C, W_R_C, img, &a)) return rc;
+    return B == 0 ? SDFNMPC_OK : sdfnmpc_scene_render_launch_(ctx, &a);
+}
+
+extern "C" int sdfnmpc_scene_pose(sdfnmpc_ctx* ctx, const double* B_p_C, const double* B_R_C, int B, const double* x,
+                                  double* W_p_Bo, double* W_R_Bo, double* W_p_C, double* W_R_C) {
+    if (!ctx) return fail(SDFNMPC_E_ARG, "NULL context");
+    ScenePoseArgs a{};
+    if (int rc = sdfnmpc_scene_pose_args_(B_p_C, B_R_C, B, x, W_p_Bo, W_R_Bo, W_p_C, W_R_C, &a)) return rc;
+    return B == 0 ? SDFNMPC_OK : sdfnmpc_scene_pose_launch_(ctx, &a);
+}
+
+extern "C" int sdfnmpc_scene_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const double* points,
+                                      const int* p_to_scene, long long n, double* out) {
+    if (!ctx || !sc) return fail(SDFNMPC_E_ARG, "scene_distance: NULL context or scene");
+    if (sc->device != ctx->device) return fail(SDFNMPC_E_ARG, "scene_distance: the scene lives on another device");
+    if (n < 0 || n > 2147483647LL) return fail(SDFNMPC_E_ARG, "scene_distance: n out of range");
+    if (!p_to_scene && n % sc->S != 0)
+        return fail(SDFNMPC_E_ARG, "scene_distance: without p_to_scene the points must divide evenly among the scenes");
+    if (n == 0) return SDFNMPC_OK;
+    if (!points || !out) return fail(SDFNMPC_E_ARG, "scene_distance: NULL points or output");
+    SceneDistArgs a{sc->dev, points, p_to_scene, n, std::max(1LL, n / sc->S), out};
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "scene_dist", [&] { return launch_scene_distance(a, ctx->stream); }));
     return SDFNMPC_OK;
 }

@@ -1,0 +1,68 @@
+// Analytic scenes (csrc/scene.hip): range / depth images of a known world rendered on the device, the camera
+// pose of a state, and the exact signed distance to the scene.  The producer side of the perception loop whose
+// consumers are vae_enc.hip (images -> latents), ref_pack.hip (latents + pose -> p) and df_truth.hip (labels).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace sdfn {
+
+constexpr int SCENE_MAX_PRIMS = 32;  // SDFNMPC_SCENE_MAX_PRIMS
+constexpr int SCENE_BLOCK = 256;
+constexpr size_t SCENE_LDS_MAX = 48 * 1024;
+
+// kinds (SDFNMPC_PRIM_*): 0 sphere a = (cx, cy, cz, r); 1 axis-aligned box a = (lo xyz, hi xyz);
+// 2 capped cylinder along z a = (cx, cy, r, z0, z1)
+struct ScenePrimF {  // 32 bytes: two 16-byte LDS reads
+    float a[6];
+    int kind, pad;
+};
+struct ScenePrimD {
+    double a[6];
+    int kind, pad;
+};
+
+// S scenes of up to SCENE_MAX_PRIMS primitives each, in both precisions, on the device
+struct SceneDev {
+    int S;
+    const int* count;        // [S]
+    const ScenePrimF* pf;    // [S][SCENE_MAX_PRIMS]
+    const ScenePrimD* pd;    // [S][SCENE_MAX_PRIMS]
+};
+
+struct SceneRenderArgs {
+    SceneDev sc;
+    const int* scene_of;     // [B] or nullptr (scene 0); entries are the caller's to keep in [0, S)
+    int B, H, W;
+    const double* W_p_C;     // [B][3]
+    const double* W_R_C;     // [B][9] row-major
+    float dmax, scale;
+    float hfov, vfov;        // spherical: half fields of view
+    float ty0, ty1, tz0, tz1;  // pinhole: tangent coordinates ty = ty0 + ty1 u, tz = tz0 + tz1 v
+    int is_depth, is_spherical;
+    float* img;              // [B][H][W]
+};
+
+struct ScenePoseArgs {
+    int B;
+    const double* x;         // [B][10]
+    double B_p_C[3], B_R_C[9];
+    double *W_p_Bo, *W_R_Bo, *W_p_C, *W_R_C;  // [B][3], [B][9], [B][3], [B][9]
+};
+
+struct SceneDistArgs {
+    SceneDev sc;
+    const double* points;    // [n][3]
+    const int* p_to_scene;   // [n] or nullptr: point j -> scene j / per_scene
+    long long n, per_scene;
+    double* out;             // [n]
+};
+
+inline size_t scene_render_lds_bytes(int h, int w, int is_spherical) {
+    return is_spherical ? (size_t)2 * ((size_t)h + (size_t)w) * sizeof(float) : 0;
+}
+
+hipError_t launch_scene_render(const SceneRenderArgs& a, hipStream_t s);
+hipError_t launch_scene_pose(const ScenePoseArgs& a, hipStream_t s);
+hipError_t launch_scene_distance(const SceneDistArgs& a, hipStream_t s);
+
+}  // namespace sdfn

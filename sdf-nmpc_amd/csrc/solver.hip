@@ -16,12 +16,25 @@
 #include "../../include/sdfnmpc.h"
 #include "plant_kernels.h"
 #include "ref_kernels.h"
+#include "scene_kernels.h"
 
 extern "C" int sdfnmpc_solver_fail_(int code, const char* msg);  // engine.cpp: sets sdfnmpc_last_error
 // engine.cpp: the plant's option check + argument block, and its launch on the context stream (timed as "plant")
 extern "C" int sdfnmpc_plant_args_(const sdfnmpc_plant_opts* o, int B, const double* x, const double* u, double* x_next,
                                    sdfn::PlantArgs* out);
 extern "C" int sdfnmpc_plant_launch_(sdfnmpc_ctx* ctx, const sdfn::PlantArgs* a);
+// engine.cpp: the same split for the scene kernels a perceiving rollout repeats, and where an encoder / a scene lives
+extern "C" int sdfnmpc_scene_render_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of,
+                                          const sdfnmpc_img_opts* o, int H, int W, float scale, int B,
+                                          const double* W_p_C, const double* W_R_C, float* img,
+                                          sdfn::SceneRenderArgs* out);
+extern "C" int sdfnmpc_scene_render_launch_(sdfnmpc_ctx* ctx, const sdfn::SceneRenderArgs* a);
+extern "C" int sdfnmpc_scene_pose_args_(const double* B_p_C, const double* B_R_C, int B, const double* x, double* W_p_Bo,
+                                        double* W_R_Bo, double* W_p_C, double* W_R_C,
+                                        sdfn::ScenePoseArgs* out);
+extern "C" int sdfnmpc_scene_pose_launch_(sdfnmpc_ctx* ctx, const sdfn::ScenePoseArgs* a);
+extern "C" int sdfnmpc_vae_on_ctx_(const sdfnmpc_vae* v, const sdfnmpc_ctx* ctx);
+extern "C" int sdfnmpc_scene_on_ctx_(const sdfnmpc_scene* sc, const sdfnmpc_ctx* ctx);
 
 namespace {
 
@@ -368,6 +381,11 @@ extern "C" int sdfnmpc_solver_step(sdfnmpc_solver* s) {
 }
 
 extern "C" int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a) {
+    return sdfnmpc_solver_rollout_perceive(s, a, nullptr);
+}
+
+extern "C" int sdfnmpc_solver_rollout_perceive(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
+                                               const sdfnmpc_perceive_args* pc) {
     if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout");
     if (a->steps < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
     if (!a->x_log || !a->u_log) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: x_log and u_log are required");
@@ -387,6 +405,38 @@ extern "C" int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_a
         ra.wp_p = a->wp_p; ra.wp_q = a->wp_q; ra.vw = a->vw; ra.wrow = a->wrow;
         ra.p = s->p; ra.yref = s->yref; ra.W = s->W; ra.yNref = s->yNref; ra.WN = s->WN; ra.nyN = s->nyN;
     }
+    // perception: the pose and render blocks, and what sdfnmpc_vae_encode / sdfnmpc_pack_refs (mode -1) would refuse
+    sdfn::ScenePoseArgs spa{};
+    sdfn::SceneRenderArgs sra{};
+    sdfnmpc_vae_opts vo{};
+    sdfnmpc_ref_opts lo{};
+    sdfnmpc_ref_args lra{};
+    if (pc) {
+        if (pc->every < 1 || pc->phase < 0)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
+        if (!pc->scene || !pc->vae) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perception needs a scene and an encoder");
+        if (!sdfnmpc_scene_on_ctx_(pc->scene, s->ctx) || !sdfnmpc_vae_on_ctx_(pc->vae, s->ctx))
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene and the encoder must live on the solver's context");
+        if (!pc->images || !pc->latent || !pc->latent64 || !pc->W_p_Bo || !pc->W_R_Bo || !pc->W_p_C || !pc->W_R_C)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perception needs its workspaces (images, latents, poses)");
+        const int L = sdfnmpc_vae_size_latent(pc->vae);
+        if (L < 1 || 17 + L > s->np)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the encoder's latent does not fit the parameter row");
+        if (!(pc->vae_opts.clip > 0.f)) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: vae_opts.clip must be > 0");
+        if (int rc = sdfnmpc_scene_pose_args_(pc->B_p_C, pc->B_R_C, s->B, s->x0, pc->W_p_Bo, pc->W_R_Bo, pc->W_p_C,
+                                              pc->W_R_C, &spa))
+            return rc;
+        if (int rc = sdfnmpc_scene_render_args_(s->ctx, pc->scene, pc->scene_of, &pc->img, pc->h, pc->w, pc->scale, s->B,
+                                                pc->W_p_C, pc->W_R_C, pc->images, &sra))
+            return rc;
+        vo = pc->vae_opts;
+        vo.B = s->B; vo.in_h = pc->h; vo.in_w = pc->w; vo.dtype = 0;
+        lo.mode = -1;
+        for (int i = 0; i < 3; ++i) lo.B_p_C[i] = pc->B_p_C[i];
+        for (int i = 0; i < 9; ++i) lo.B_R_C[i] = pc->B_R_C[i];
+        lra.B = s->B; lra.N = s->N; lra.np = s->np; lra.ny = s->ny; lra.L = L; lra.nyN = s->nyN;
+        lra.latent = pc->latent64; lra.W_p_Bo = pc->W_p_Bo; lra.W_R_Bo = pc->W_R_Bo; lra.p = s->p;
+    }
     pa.K = a->steps;
     pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
     pa.pts_log = a->pts_log;
@@ -394,6 +444,12 @@ extern "C" int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_a
     pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
     SolverDevice sd(s->device);
     for (int k = 0; k < a->steps; ++k) {
+        if (pc && (k + pc->phase) % pc->every == 0) {  // a new image from the current state: pose, render, encode, set_latent
+            if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
+            if (int rc = sdfnmpc_scene_render_launch_(s->ctx, &sra)) return rc;
+            if (int rc = sdfnmpc_vae_encode(s->ctx, pc->vae, &vo, pc->images, pc->latent, pc->latent64)) return rc;
+            if (int rc = sdfnmpc_pack_refs(s->ctx, &lo, &lra)) return rc;
+        }
         if (a->ref)
             if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
         if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;

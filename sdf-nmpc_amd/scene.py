@@ -1,0 +1,151 @@
+"""Analytic scenes on the device (csrc/scene.hip through the C ABI, sdfnmpc_scene_*): the range or depth image a
+sensor of the config would take of a known world from a camera pose, the camera pose of a state, and the exact
+signed distance from a point to the world.
+
+The reference has no counterpart -- its images come from the simulator it is run against.  A ``Scene`` is the
+producer in front of what the package already consumes: ``VaeWrapper.set_img`` (raw images), ``ColChecker`` /
+``DfComputer`` (normalised images) and ``Nmpc.rollout(scene=...)``, which takes a new image of the scene from every
+instance's current pose inside the device loop.
+
+    scene = Scene(ctx, [Scene.sphere((2.5, -0.8, 0.3), 0.5), Scene.box((3.5, 0.5, -1), (4.1, 1.5, 1.2)),
+                        Scene.cylinder((3.0, 0.3), 0.4, -1.5, 1.5)])
+    img = scene.render_from_state(x, cfg)            # DeviceArray [B, h, w] float32, normalised by sensor.dmax
+    d = scene.distance(points)                       # numpy [n] float64, negative inside
+
+World frame z up; camera frame x forward, y left, z up, the pixel grid of ``ColChecker``.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+
+
+class Scene:
+    """One scene (a list of primitives) or several (a list of lists) with ``scene_of`` [B], the scene of each
+    instance; without ``scene_of`` every instance sees scene 0.  At most 32 primitives per scene.  The primitives
+    are checked by the library when the scene is created (SdfnmpcError: more than 32, an unknown kind, a radius
+    <= 0, lo >= hi); ``scene_of`` is checked here."""
+
+    @staticmethod
+    def sphere(center, radius):
+        return ("sphere", [float(v) for v in center] + [float(radius)])
+
+    @staticmethod
+    def box(lo, hi):
+        return ("box", [float(v) for v in lo] + [float(v) for v in hi])
+
+    @staticmethod
+    def cylinder(center_xy, radius, z0, z1):
+        """A capped cylinder along z: axis through center_xy, z in [z0, z1]."""
+        return ("cylinder", [float(v) for v in center_xy] + [float(radius), float(z0), float(z1)])
+
+    def __init__(self, ctx: "_lib.Context", prims, scene_of=None):
+        is_prim = lambda p: isinstance(p, tuple) and len(p) == 2 and isinstance(p[0], (str, int))
+        scenes = [list(prims)] if all(is_prim(p) for p in prims) else [list(s) for s in prims]
+        flat = []
+        for s in scenes:
+            for kind, vals in s:
+                vals = list(vals)
+                if len(vals) > 6:
+                    raise ValueError(f"primitive {kind!r}: at most 6 values, got {len(vals)}")
+                # an unknown kind goes to the library as it is (it refuses it)
+                flat.append((_lib.PRIM_KINDS.get(kind, kind if isinstance(kind, int) else -1), vals))
+        self.ctx, self.S = ctx, len(scenes)
+        self.h = _lib.scene_create(ctx, [len(s) for s in scenes], flat)
+        self.scene_of = self._scene_of = None
+        if scene_of is not None:
+            so = np.ascontiguousarray(scene_of, dtype=np.int32).ravel()
+            if so.size and (so.min() < 0 or so.max() >= self.S):
+                raise ValueError(f"scene_of entries must lie in [0, {self.S})")
+            self.scene_of = so
+            self._scene_of = _lib.DeviceArray.from_numpy(ctx, so)
+
+    # ---- helpers
+    def _f64(self, a, shape):
+        """Host array -> device fp64 of `shape`; a device fp64 array of that many elements passes through."""
+        if hasattr(a, "data_ptr"):
+            if np.dtype(str(a.dtype).replace("torch.", "")) != np.float64:
+                raise TypeError(f"device input must be float64, got {a.dtype}")
+            if int(np.prod(a.shape)) != int(np.prod(shape)):
+                raise ValueError(f"expected a device array of shape {shape}, got {tuple(a.shape)}")
+            return _lib.sync_producer(a)
+        return _lib.DeviceArray.from_numpy(self.ctx, np.reshape(np.asarray(a, dtype=np.float64), shape))
+
+    def _batch(self, B):
+        if self.scene_of is not None and self.scene_of.size != B:
+            raise ValueError(f"scene_of names {self.scene_of.size} instances, the call has {B}")
+
+    @staticmethod
+    def img_opts(cfg):
+        s = cfg.sensor
+        return _lib.img_opts(s.dmax, s.hfov, s.vfov, s.is_depth, s.is_spherical)
+
+    @staticmethod
+    def scale(cfg, normalized=True) -> float:
+        """Pixel value per metre: 1 / dmax (the images ColChecker / DfComputer read) or 1000 / mm_resolution (the
+        raw sensor images VaeWrapper.set_img expects)."""
+        return 1.0 / float(cfg.sensor.dmax) if normalized else 1000.0 / float(cfg.sensor.mm_resolution)
+
+    # ---- the three kernels
+    def render(self, W_p_C, W_R_C, cfg, shape=None, normalized=True, out=None):
+        """Images [B, h, w] float32 (a DeviceArray; asynchronous on the context stream) of the camera poses W_p_C
+        [B, 3], W_R_C [B, 3, 3] (host or device fp64) with the sensor of cfg: range, or depth with
+        sensor.is_depth; pinhole or spherical pixels; clipped at sensor.dmax.  shape (h, w) defaults to
+        sensor.shape_imgs[-2:].  out: a float32 DeviceArray [B, h, w] to write instead of a new one."""
+        h, w = (int(v) for v in (shape if shape is not None else cfg.sensor.shape_imgs[-2:]))
+        B = int(np.prod(W_p_C.shape)) // 3 if hasattr(W_p_C, "data_ptr") else np.asarray(W_p_C).reshape(-1, 3).shape[0]
+        self._batch(B)
+        p, R = self._f64(W_p_C, (B, 3)), self._f64(W_R_C, (B, 9))
+        if out is None:
+            out = _lib.DeviceArray(self.ctx, (B, h, w), np.float32)
+        elif tuple(out.shape) != (B, h, w) or np.dtype(out.dtype) != np.float32:
+            raise ValueError(f"out must be float32 [{B}, {h}, {w}]")
+        _lib.scene_render(self.ctx, self.h, self._scene_of, self.img_opts(cfg), h, w, self.scale(cfg, normalized), B, p, R,
+                          out)
+        out._inputs = (p, R)  # temporaries of an asynchronous launch stay alive with its result
+        return out
+
+    def pose(self, x, cfg):
+        """States x [B, 10] (host or device fp64) -> dict of DeviceArrays W_p_Bo [B, 3], W_R_Bo [B, 9],
+        W_p_C [B, 3], W_R_C [B, 9]: the body pose quat2rot(q / |q|) and the camera pose with the extrinsics of cfg
+        (what Nmpc.set_latent forms from the body pose)."""
+        B = int(np.prod(x.shape)) // 10 if hasattr(x, "data_ptr") else np.asarray(x).reshape(-1, 10).shape[0]
+        dx = self._f64(x, (B, 10))
+        out = {k: _lib.DeviceArray(self.ctx, (B, n)) for k, n in (("W_p_Bo", 3), ("W_R_Bo", 9), ("W_p_C", 3), ("W_R_C", 9))}
+        _lib.scene_pose(self.ctx, cfg.sensor.B_p_C, cfg.sensor.B_R_C, B, dx, *out.values())
+        out["W_p_Bo"]._inputs = dx
+        return out
+
+    def render_from_state(self, x, cfg, shape=None, normalized=True, out=None):
+        """``render`` from the camera poses of the states x (``pose``); the result carries them as ``.pose``."""
+        ps = self.pose(x, cfg)
+        img = self.render(ps["W_p_C"], ps["W_R_C"], cfg, shape, normalized, out)
+        img.pose = ps  # the poses the images were taken from (device arrays, as ``pose`` returns them)
+        return img
+
+    def distance(self, points, p_to_scene=None):
+        """Signed distance [n] (numpy fp64) from world points [n, 3] to their scene, negative inside.  p_to_scene
+        [n]: the scene of each point; None: the default ordering, point j -> scene j // (n / S)."""
+        pts = self._f64(points, (-1, 3) if not hasattr(points, "data_ptr") else tuple(points.shape))
+        n = int(np.prod(pts.shape)) // 3
+        p2s = None
+        if p_to_scene is not None:
+            a = np.ascontiguousarray(p_to_scene, dtype=np.int32).ravel()
+            if a.size != n or (n and (a.min() < 0 or a.max() >= self.S)):
+                raise ValueError(f"p_to_scene needs one entry in [0, {self.S}) per point")
+            p2s = _lib.DeviceArray.from_numpy(self.ctx, a)
+        out = _lib.DeviceArray(self.ctx, (n,), np.float64)
+        _lib.scene_distance(self.ctx, self.h, pts, p2s, n, out)
+        return out.numpy()  # the copy waits for the launch
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib.load().sdfnmpc_scene_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

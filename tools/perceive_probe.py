@@ -1,0 +1,164 @@
+"""What does perceiving inside the device loop buy?  The same K-step closed loop with a new image of an analytic
+scene every `--every`-th step, run two ways on one controller configuration: as Nmpc.rollout(scene=, vae=) (one
+launch sequence, one wait), and as the host-driven loop built from the public pieces (render_from_state -> set_img ->
+encode_to -> set_x0 -> gen_refs_device -> solve -> plant_step -> download the state).  Both use the same kernels, so
+the loops compute the same bits (checked) and the difference is the host's.  Also the three scene kernels' own times
+(HIP events): scene_render at 270 x 480 with 16 primitives next to its floors, scene_pose, scene_dist.
+
+One configuration per run (give every run its own time limit):
+    timeout 600 python tools/perceive_probe.py --B 1024 --N 40 --every 1
+    timeout 600 python tools/perceive_probe.py --B 1024 --N 40 --every 5
+    timeout 200 python tools/perceive_probe.py --B 1 --N 40 --every 1
+Prints ms per control step of both loops (best of --reps repetitions after a warm-up) and a JSON line.  Diagnostic."""
+import argparse
+import json
+import os
+import sys
+import time
+import warnings
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from sdf_nmpc_amd import _lib
+from sdf_nmpc_amd.config import Config
+from sdf_nmpc_amd.scene import Scene
+from sdf_nmpc_amd.vae import VaeWrapper
+from rollout_probe import controller
+
+# vector instructions executed per ray-primitive test, from the loop body in the -save-temps assembly: 38 (box), 39
+# (sphere), 51 (cylinder); the probe's forest is one box, ten cylinders and five spheres
+INSTR_PER_TEST = (38 + 10 * 51 + 5 * 39) / 16
+LANE_INSTR_PER_S = 39e12  # 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz: one wave per SIMD
+LANE_INSTR_PER_S_2 = 2 * LANE_INSTR_PER_S  # two or more waves per SIMD: a wave64 instruction issues in 2 cycles, not 4
+HBM_BYTES_PER_S = 8e12
+
+
+def forest(n_prims, seed=3):
+    """A floor and n_prims - 1 pillars and balls ahead of the start box of rollout_probe.controller."""
+    rng = np.random.default_rng(seed)
+    prims = [Scene.box((-20, -20, -2.1), (20, 20, -2.0))]
+    while len(prims) < n_prims:
+        c = rng.uniform([2.0, -4.0], [7.0, 4.0])
+        prims.append(Scene.cylinder(c, rng.uniform(0.15, 0.4), -2.0, 2.5) if len(prims) % 3 else
+                     Scene.sphere((c[0], c[1], rng.uniform(-1, 1)), rng.uniform(0.2, 0.5)))
+    return prims
+
+
+def host_loop(n, vae, scene, x0, wps, K, every, plant):
+    B, ctx = max(n.B, 1), n.ocp.ctx
+    dx = _lib.DeviceArray(ctx, (B, 10))
+    x, xs = np.reshape(x0, (B, 10)).copy(), []
+    sq = (lambda a: a) if n.B > 1 else (lambda a: a[0])
+    for k in range(K):
+        n.set_x0(sq(x))
+        if k % every == 0:
+            img = scene.render_from_state(x, n.cfg, normalized=False)
+            vae.set_img(img)
+            vae.encode_to(n, img.pose["W_p_Bo"], img.pose["W_R_Bo"])
+        n.gen_refs_device("wps", wps=wps)
+        n.solve()
+        dx.upload(x)
+        _lib.plant_step(ctx, plant, B, dx, n.ocp.field("u0"), dx)
+        x = dx.numpy()
+        xs.append(x)
+    return np.stack(xs, 1)
+
+
+def kernel_times(ctx, cfg, B, res):
+    """HIP events around each launch of the three scene kernels (16 primitives, the sensor's 270 x 480 image)."""
+    scene = Scene(ctx, forest(16))
+    rng = np.random.default_rng(0)
+    x = np.zeros((B, 10))
+    x[:, :3] = rng.uniform(-1, 1, (B, 3))
+    x[:, 3] = 1.0
+    x[:, 6] = rng.uniform(-0.3, 0.3, B)
+    dx = _lib.DeviceArray.from_numpy(ctx, x)
+    h, w = (int(v) for v in cfg.sensor.shape_imgs[-2:])
+    out = _lib.DeviceArray(ctx, (B, h, w), np.float32)
+    ps = scene.pose(dx, cfg)
+    pts = _lib.DeviceArray.from_numpy(ctx, np.tile(x[:, None, :3], (1, 51, 1)).reshape(-1, 3))
+    dist = _lib.DeviceArray(ctx, (B * 51,))
+    calls = {"scene_render": lambda: scene.render(ps["W_p_C"], ps["W_R_C"], cfg, out=out),
+             "scene_pose": lambda: _lib.scene_pose(ctx, cfg.sensor.B_p_C, cfg.sensor.B_R_C, B, dx, *ps.values()),
+             "scene_dist": lambda: _lib.scene_distance(ctx, scene.h, pts, None, B * 51, dist)}
+    for name, fn in calls.items():
+        for _ in range(5):
+            fn()
+        ctx.synchronize()
+        ctx.reset_stats()
+        ctx.enable_timing(True)
+        for _ in range(20):
+            fn()
+        ms, cnt = ctx.kernel_stats(name)
+        ctx.enable_timing(False)
+        ctx.reset_stats()
+        res[f"{name}_us"] = ms / cnt * 1e3
+    rays = B * h * w
+    res["render_rays"] = rays
+    res["render_floor_store_us"] = rays * 4 / HBM_BYTES_PER_S * 1e6
+    res["render_floor_valu_us"] = rays * 16 * INSTR_PER_TEST / LANE_INSTR_PER_S * 1e6
+    res["render_floor_valu_2cycle_us"] = rays * 16 * INSTR_PER_TEST / LANE_INSTR_PER_S_2 * 1e6
+    res["render_hit_share"] = float((out.numpy() < 1.0).mean())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=1024)
+    ap.add_argument("--N", type=int, default=40)
+    ap.add_argument("--K", type=int, default=50)
+    ap.add_argument("--every", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    warnings.simplefilter("ignore")
+    cfg = Config(mpc__N=a.N)
+    res = {"B": a.B, "N": a.N, "K": a.K, "every": a.every}
+    t_roll, t_host, xr, xh = [], [], None, None
+    for rep in range(a.reps + 1):  # repetition 0 warms up (workspaces, code objects) and is not timed
+        n, x0, wps = controller(cfg, a.B, 1)
+        ctx = n.ocp.ctx
+        scene, vae = Scene(ctx, forest(16)), VaeWrapper(cfg, batch=a.B, ctx=ctx)
+        plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]))
+        n.set_x0(x0)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        r = n.rollout(a.K, refs="wps", wps=wps, plant=plant, scene=scene, vae=vae, perceive_every=a.every)
+        t1 = time.perf_counter()
+        vae.vae.close()
+        n.ocp.close()
+        n, x0, wps = controller(cfg, a.B, 1)
+        ctx = n.ocp.ctx
+        scene, vae = Scene(ctx, forest(16)), VaeWrapper(cfg, batch=a.B, ctx=ctx)
+        plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]))
+        ctx.synchronize()
+        t2 = time.perf_counter()
+        xh = host_loop(n, vae, scene, x0, wps, a.K, a.every, plant)
+        t3 = time.perf_counter()
+        xr = r.x[:, 1:]
+        if rep:
+            t_roll.append((t1 - t0) / a.K * 1e3)
+            t_host.append((t3 - t2) / a.K * 1e3)
+        vae.vae.close()
+        if rep < a.reps:
+            n.ocp.close()
+    res["same_bits"] = bool(np.array_equal(xr, xh))
+    res["rollout_ms_per_step"], res["host_loop_ms_per_step"] = min(t_roll), min(t_host)
+    res["rollout_ms_all"], res["host_loop_ms_all"] = [round(t, 3) for t in t_roll], [round(t, 3) for t in t_host]  # the spread
+    res["qp_iters_mean"] = float(r.iters.mean())
+    res["min_clearance"] = float(r.clearance.min())
+    kernel_times(n.ocp.ctx, cfg, max(n.B, 1), res)
+    n.ocp.close()
+    print(f"B={a.B} N={a.N} K={a.K} every={a.every}: rollout with perception {res['rollout_ms_per_step']:.3f} ms/step, "
+          f"host-driven loop {res['host_loop_ms_per_step']:.3f} ms/step (same bits: {res['same_bits']}); scene_render "
+          f"{res['scene_render_us']:.1f} us (floors: store {res['render_floor_store_us']:.1f} us, vector ALU "
+          f"{res['render_floor_valu_us']:.1f} us at 39 T lane-instructions/s, {res['render_floor_valu_2cycle_us']:.1f} us "
+          f"at twice that), scene_pose {res['scene_pose_us']:.1f} us, scene_dist "
+          f"{res['scene_dist_us']:.1f} us")
+    print(json.dumps(res))
+    if res["rollout_ms_per_step"] > res["host_loop_ms_per_step"]:
+        print("NOTE: the rollout was not faster than the host-driven loop in this run")
+
+
+if __name__ == "__main__":
+    main()
