@@ -49,7 +49,9 @@
  *
  *   sdfnmpc_scene_*                    (no reference interface: the reference's images come from the simulator it is
  *                                      run against) range / depth images of an analytic scene from a camera pose,
- *                                      the camera pose of a state (controller.py:52-53), the exact signed distance
+ *                                      the camera pose of a state (controller.py:52-53), the exact signed distance;
+ *                                      primitives may be oriented and may move (_create_moving, _render_at,
+ *                                      _distance_at, sdfnmpc_solver_rollout_perceive_at)
  *   sdfnmpc_solver_rollout_perceive    sdfnmpc_solver_rollout with the perception a user wraps around it every
  *                                      control period: VaeWrapper.set_img / encode (sdf_nmpc/vae.py:29-40) of a new
  *                                      image and Nmpc.set_latent (controller.py:50-54) with the pose at image time
@@ -297,8 +299,8 @@ long long sdfnmpc_qp_capacity_for(const sdfnmpc_ctx* ctx, int N, const sdfnmpc_q
 int sdfnmpc_ctx_set_tile_rows(sdfnmpc_ctx* ctx, int rows);
 /* per-kernel HIP-event timing on the context stream (off by default) */
 int sdfnmpc_ctx_enable_timing(sdfnmpc_ctx* ctx, int on);
-/* kernel: "sdf_mlp", "sdf_hoist", "linearize", "rti_qp", "plant", "scene_render", "scene_pose", "scene_dist", ...;
- * synchronizes the stream(s) */
+/* kernel: "sdf_mlp", "sdf_hoist", "linearize", "rti_qp", "plant", "scene_render", "scene_pose", "scene_dist",
+ * "scene_render_dyn", "scene_dist_dyn", ...; synchronizes the stream(s) */
 int sdfnmpc_ctx_kernel_stats(sdfnmpc_ctx* ctx, const char* kernel, double* total_ms, long long* launches);
 int sdfnmpc_ctx_reset_stats(sdfnmpc_ctx* ctx);
 
@@ -588,6 +590,44 @@ int sdfnmpc_scene_pose(sdfnmpc_ctx* ctx, const double* B_p_C, const double* B_R_
 int sdfnmpc_scene_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const double* points, const int* p_to_scene,
                            long long n, double* out);
 
+/* ---- moving and oriented primitives ----
+ * Every primitive has a reference point c0 -- sphere: its centre; box: (lo + hi) / 2; cylinder: (cx, cy, (z0 + z1) /
+ * 2) -- and an optional motion record that gives its rigid frame at time t:
+ *   c(t) = c0 + v t + amp sin(omega t + phase)      (amp component-wise)
+ *   R(t) = Rz(yaw_rate t) R(q)                      q = (w, x, y, z) of any non-zero norm, normalised at creation
+ * The primitive is its canonical shape (centred, axes as given) placed at (R(t), c(t)): a box with q != identity is
+ * an oriented box, a cylinder with q != identity a tilted capped cylinder.  R(q) is formed once in fp64 when the
+ * scene is created and kept on the device beside the primitives.
+ * sdfnmpc_scene_create_moving is sdfnmpc_scene_create with motion [sum of count] beside prims; motion == NULL gives
+ * exactly what sdfnmpc_scene_create gives.  In addition to that function's checks it refuses (SDFNMPC_E_ARG, before
+ * anything is allocated) a non-finite motion value and a zero quaternion.
+ * A scene set is dynamic (sdfnmpc_scene_is_dynamic: 1, else 0) when some primitive of it has a q that is not the
+ * identity rotation or a non-zero yaw_rate, v or amp.  A set that is not dynamic is rendered and measured by the
+ * static kernels whatever time is given: the same bits as sdfnmpc_scene_render / sdfnmpc_scene_distance.  A dynamic
+ * set takes the dynamic kernels ("scene_render_dyn", "scene_dist_dyn" in sdfnmpc_ctx_kernel_stats) for every scene
+ * of it; a primitive without motion is the case R = I, v = 0 of the same path. */
+typedef struct {
+    double q[4];                   /* orientation (w, x, y, z); (1, 0, 0, 0): none */
+    double yaw_rate;               /* rad / s about the world z axis */
+    double v[3];                   /* m / s */
+    double amp[3];                 /* m, harmonic term */
+    double omega, phase;           /* rad / s, rad */
+} sdfnmpc_prim_motion;
+int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
+                                const sdfnmpc_prim_motion* motion, sdfnmpc_scene** out);
+int sdfnmpc_scene_is_dynamic(const sdfnmpc_scene* scene);
+/* sdfnmpc_scene_render of the scene at time t (sdfnmpc_scene_render is t = 0).  For a dynamic set each block forms
+ * its primitives' frames at t in fp64 -- the camera origin and axes in the primitive's frame -- rounds them to fp32
+ * once and runs the interval tests of sdfnmpc_scene_render on the canonical shapes; hit rule, depth / range,
+ * clipping and scale are the same.  Also refused (SDFNMPC_E_ARG, nothing launched): a non-finite t. */
+int sdfnmpc_scene_render_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const int* scene_of,
+                            const sdfnmpc_img_opts* opts, int H, int W, float scale, int B, const double* W_p_C,
+                            const double* W_R_C, double t, float* img);
+/* sdfnmpc_scene_distance with point j measured against the scene at times [j] (device float64 [n]; NULL: t = 0).
+ * The times are the caller's to keep finite, as the points are. */
+int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const double* points, const int* p_to_scene,
+                              const double* times, long long n, double* out);
+
 /* sdfnmpc_solver_rollout with perception inside the loop.  Before step k with (k + phase) % every == 0 it enqueues, on the
  * solver's stream and in this order: (a) sdfnmpc_scene_pose from the solver's x0 field; (b) sdfnmpc_scene_render of
  * every instance's scene from that camera pose; (c) sdfnmpc_vae_encode of the images; (d) sdfnmpc_pack_refs in mode -1
@@ -621,6 +661,13 @@ typedef struct {
 
 int sdfnmpc_solver_rollout_perceive(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
                                     const sdfnmpc_perceive_args* perc);
+/* sdfnmpc_solver_rollout_perceive of a scene that moves: the image before step k is rendered at the time
+ * t = t0 + (double)(perc->phase + k) * dt, one multiplication and one addition in fp64 (never a fused multiply-add),
+ * so that a host loop that calls sdfnmpc_scene_render_at with the same expression gets the same bits.
+ * sdfnmpc_solver_rollout_perceive is _at(..., 0, 0).  Also refused, before the first launch: a non-finite t0 or dt,
+ * dt < 0. */
+int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
+                                       const sdfnmpc_perceive_args* perc, double t0, double dt);
 
 /* ---- shooting grid (host, bit-exact numpy.linspace/diff semantics of ocp.py:21-27) ---- */
 int sdfnmpc_shooting_grid(int N, double T, int uniform, int nb_short_nodes, double dt_short, double* nodes,

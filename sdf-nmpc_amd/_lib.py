@@ -38,6 +38,8 @@ SYMBOLS = [
     "sdfnmpc_solver_wait", "sdfnmpc_plant_step", "sdfnmpc_solver_rollout",
     "sdfnmpc_scene_create", "sdfnmpc_scene_free", "sdfnmpc_scene_render", "sdfnmpc_scene_pose",
     "sdfnmpc_scene_distance", "sdfnmpc_solver_rollout_perceive",
+    "sdfnmpc_scene_create_moving", "sdfnmpc_scene_is_dynamic", "sdfnmpc_scene_render_at", "sdfnmpc_scene_distance_at",
+    "sdfnmpc_solver_rollout_perceive_at",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -143,6 +145,11 @@ class PrimC(C.Structure):
     _fields_ = [("kind", C.c_int), ("a", C.c_double * 6)]
 
 
+class PrimMotionC(C.Structure):
+    _fields_ = [("q", C.c_double * 4), ("yaw_rate", C.c_double), ("v", C.c_double * 3), ("amp", C.c_double * 3),
+                ("omega", C.c_double), ("phase", C.c_double)]
+
+
 class PerceiveArgsC(C.Structure):
     _fields_ = [("scene", C.c_void_p), ("scene_of", C.c_void_p), ("img", ImgOptsC), ("h", C.c_int), ("w", C.c_int),
                 ("scale", C.c_float), ("B_p_C", C.c_double * 3), ("B_R_C", C.c_double * 9), ("vae", C.c_void_p),
@@ -233,6 +240,11 @@ def load():
         "sdfnmpc_scene_pose": (i, [vp, P(d), P(d), i, vp, vp, vp, vp, vp]),
         "sdfnmpc_scene_distance": (i, [vp, vp, vp, vp, ll, vp]),
         "sdfnmpc_solver_rollout_perceive": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC)]),
+        "sdfnmpc_scene_create_moving": (i, [vp, i, P(i), P(PrimC), P(PrimMotionC), P(vp)]),
+        "sdfnmpc_scene_is_dynamic": (i, [vp]),
+        "sdfnmpc_scene_render_at": (i, [vp, vp, vp, P(ImgOptsC), i, i, f, i, vp, vp, d, vp]),
+        "sdfnmpc_scene_distance_at": (i, [vp, vp, vp, vp, vp, ll, vp]),
+        "sdfnmpc_solver_rollout_perceive_at": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -670,9 +682,10 @@ def sdf_truth(ctx: Context, opts: ImgOptsC, min_df: float, max_df: float, grid, 
 
 
 # ---- analytic scenes (csrc/scene.hip); the user-facing object is sdf_nmpc_amd.scene.Scene ----
-def scene_create(ctx: "Context", counts, prims):
+def scene_create(ctx: "Context", counts, prims, motion=None):
     """sdfnmpc_scene_create: counts [S] primitives per scene, prims a flat list of (kind, values) scene after
-    scene.  Returns the handle; the C entry point refuses malformed scenes."""
+    scene.  Returns the handle; the C entry point refuses malformed scenes.  motion: one dict per primitive (keys
+    q, yaw_rate, v, amp, omega, phase; None: no motion) -- sdfnmpc_scene_create_moving."""
     cn = (C.c_int * len(counts))(*[int(c) for c in counts])
     pr = (PrimC * max(len(prims), 1))()
     for k, (kind, vals) in enumerate(prims):
@@ -680,7 +693,17 @@ def scene_create(ctx: "Context", counts, prims):
         for j, v in enumerate(vals):
             pr[k].a[j] = float(v)
     h = C.c_void_p()
-    _check(load().sdfnmpc_scene_create(ctx.h, len(counts), cn, pr, C.byref(h)))
+    if motion is None:
+        _check(load().sdfnmpc_scene_create(ctx.h, len(counts), cn, pr, C.byref(h)))
+        return h
+    mo = (PrimMotionC * max(len(prims), 1))()
+    for k, m in enumerate(motion):
+        m = m or {}
+        mo[k].q[:] = [float(v) for v in m.get("q", (1.0, 0.0, 0.0, 0.0))]
+        mo[k].v[:] = [float(v) for v in m.get("v", (0.0, 0.0, 0.0))]
+        mo[k].amp[:] = [float(v) for v in m.get("amp", (0.0, 0.0, 0.0))]
+        mo[k].yaw_rate, mo[k].omega, mo[k].phase = (float(m.get(n, 0.0)) for n in ("yaw_rate", "omega", "phase"))
+    _check(load().sdfnmpc_scene_create_moving(ctx.h, len(counts), cn, pr, mo, C.byref(h)))
     return h
 
 
@@ -689,6 +712,19 @@ def scene_render(ctx: "Context", scene_h, scene_of, opts: ImgOptsC, H: int, W: i
     """Enqueue sdfnmpc_scene_render: W_p_C [B][3], W_R_C [B][9] device float64 -> img [B][H][W] device float32."""
     _check(load().sdfnmpc_scene_render(ctx.h, scene_h, _ptr(scene_of), C.byref(opts), int(H), int(W), float(scale),
                                        int(B), _ptr(W_p_C), _ptr(W_R_C), _ptr(img)))
+
+
+def scene_render_at(ctx: "Context", scene_h, scene_of, opts: ImgOptsC, H: int, W: int, scale: float, B: int, W_p_C,
+                    W_R_C, t: float, img):
+    """Enqueue sdfnmpc_scene_render_at: scene_render of the scene at time t."""
+    _check(load().sdfnmpc_scene_render_at(ctx.h, scene_h, _ptr(scene_of), C.byref(opts), int(H), int(W), float(scale),
+                                          int(B), _ptr(W_p_C), _ptr(W_R_C), float(t), _ptr(img)))
+
+
+def scene_distance_at(ctx: "Context", scene_h, points, p_to_scene, times, n: int, out):
+    """Enqueue sdfnmpc_scene_distance_at: times [n] device float64 (None: t = 0), the time of every point."""
+    _check(load().sdfnmpc_scene_distance_at(ctx.h, scene_h, _ptr(points), _ptr(p_to_scene), _ptr(times), int(n),
+                                            _ptr(out)))
 
 
 def scene_pose(ctx: "Context", B_p_C, B_R_C, B: int, x, W_p_Bo, W_R_Bo, W_p_C, W_R_C):
@@ -896,21 +932,27 @@ class Solver:
 
     def rollout(self, steps: int, plant: PlantOpts, x_log, u_log, status_log=None, iters_log=None, pts_log=None,
                 shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0,
-                perceive: "PerceiveArgsC" = None):
+                perceive: "PerceiveArgsC" = None, scene_clock=None):
         """Enqueue sdfnmpc_solver_rollout: `steps` closed-loop steps (references from x0 when ref is given,
         shift, RTI step, plant) from the x0 field, logged into the device arrays x_log [B][K+1][10], u_log
         [B][K][4], status_log / iters_log [B][K] int32 and pts_log [B][K+1][3] float32.  Asynchronous: `wait`
         finishes it (the arrays are kept alive until then).  perceive: a PerceiveArgsC -- a new image, latent and
-        pose before every `every`-th step (sdfnmpc_solver_rollout_perceive); the caller keeps what it names alive."""
+        pose before every `every`-th step (sdfnmpc_solver_rollout_perceive); the caller keeps what it names alive.
+        scene_clock: (t0, dt) -- the image before step k shows the scene at t0 + (phase + k) dt
+        (sdfnmpc_solver_rollout_perceive_at)."""
         a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
                          _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
                          _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
         self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log)
         if perceive is None:
             _check(load().sdfnmpc_solver_rollout(self.h, C.byref(a)))
-        else:
+        elif scene_clock is None:
             self._rollout_keep += (perceive,)
             _check(load().sdfnmpc_solver_rollout_perceive(self.h, C.byref(a), C.byref(perceive)))
+        else:
+            self._rollout_keep += (perceive,)
+            _check(load().sdfnmpc_solver_rollout_perceive_at(self.h, C.byref(a), C.byref(perceive),
+                                                             float(scene_clock[0]), float(scene_clock[1])))
 
     def wait(self):
         _check(load().sdfnmpc_solver_wait(self.h, self.u0.ctypes.data, self.status.ctypes.data, self.iters.ctypes.data))

@@ -32,12 +32,13 @@ class Rollout:
     """What ``Nmpc.rollout`` logged (numpy arrays, batch-leading): x [B, K+1, 10] plant states (row 0 the start),
     u [B, K, 4] applied inputs, status / iters [B, K] of every QP; with images also col [B, K+1] collision labels
     and pts [B, K+1, 3] the camera-frame positions they were taken at (else None); with a scene clearance [B, K+1],
-    the exact signed distance of every logged position to the instance's scene, and with keep_img img [B, h, w]
-    float32, the last images rendered (raw sensor values)."""
+    the exact signed distance of every logged position to the instance's scene at the time of that row, t [K+1]
+    (the scene's clock at every log row), and with keep_img img [B, h, w] float32, the last images rendered (raw
+    sensor values)."""
 
-    def __init__(self, x, u, status, iters, col=None, pts=None, clearance=None, img=None):
+    def __init__(self, x, u, status, iters, col=None, pts=None, clearance=None, img=None, t=None):
         self.x, self.u, self.status, self.iters, self.col, self.pts = x, u, status, iters, col, pts
-        self.clearance, self.img = clearance, img
+        self.clearance, self.img, self.t = clearance, img, t
 
 
 class Nmpc:
@@ -172,7 +173,7 @@ class Nmpc:
 
     def rollout(self, steps, refs=None, wps=None, vw=None, weights=None, plant=None, imgs=None, safe_ball_size=0.0,
                 outside='col', scene=None, vae=None, perceive_every=1, img_shape=None, keep_img=False,
-                perceive_phase=0):
+                perceive_phase=0, scene_t0=0.0, scene_dt=None):
         """``steps`` closed-loop control steps on the device, without a host round trip between them: per
         step the references from the current state (``refs``), the shift (mpc.shift), one SQP-RTI iteration
         and the plant advanced by u_0 -- the loop ``set_x0``; ``gen_refs_device``; ``solve``; simulate,
@@ -198,6 +199,10 @@ class Nmpc:
         ``keep_img`` the last rendered images.  ``perceive_phase``: steps already taken since the schedule began
         (an image before step k when (k + phase) % perceive_every == 0), so that a rollout cut into chunks
         perceives where the uncut one does.  ``scene`` excludes ``imgs`` (the image changes inside the loop).
+        A scene with moving primitives (``Scene.moving``) has a clock: the image before step k shows it at
+        ``scene_t0 + (perceive_phase + k) * scene_dt`` (``scene_dt``: default the plant's control period), the result
+        carries ``t`` [K+1], that time for every log row, and ``clearance[b, j]`` is the distance of row j to the
+        scene at ``t[j]``.  The controller treats every image as a static world.
 
         Returns a ``Rollout`` of numpy arrays, batch-leading also for one instance: x [B, K+1, 10] (row 0 the
         start), u [B, K, 4], status / iters [B, K]; with imgs also col [B, K+1] bool and pts [B, K+1, 3] float32.
@@ -231,6 +236,10 @@ class Nmpc:
                 raise ValueError(f"rollout(): the VaeWrapper encodes {vae.B} images, the batch has {Bn}")
             if int(perceive_every) < 1 or int(perceive_phase) < 0:
                 raise ValueError(f"perceive_every {perceive_every} / perceive_phase {perceive_phase}: at least 1 / 0")
+            if not np.isfinite(float(scene_t0)):
+                raise ValueError(f"scene_t0 {scene_t0}: a finite time")
+            if scene_dt is not None and not (np.isfinite(float(scene_dt)) and float(scene_dt) >= 0.0):
+                raise ValueError(f"scene_dt {scene_dt}: finite and not negative")
             scene._batch(Bn)
         kw = {}
         if refs is not None:
@@ -265,6 +274,9 @@ class Nmpc:
                                       vae.latent64.data_ptr(), *[ws[k].data_ptr() for k in ("W_p_Bo", "W_R_Bo", "W_p_C",
                                                                                             "W_R_C")])
             kw["perceive"] = perc
+            t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)
+            if scene.is_dynamic:  # a static scene has no use for the clock: the call the method has always made
+                kw["scene_clock"] = (t0, dts)
         dimg = None
         if imgs is not None:
             dimg, ishape = self._dev_imgs(imgs)
@@ -291,7 +303,12 @@ class Nmpc:
         if perc is not None:  # one launch over the logged positions; point j belongs to instance j // (K + 1)
             p2s = None if scene.S == 1 else np.repeat(scene.scene_of if scene.scene_of is not None else
                                                       np.zeros(Bn, np.int32), K + 1)
-            out.clearance = scene.distance(np.ascontiguousarray(out.x[:, :, :3]).reshape(-1, 3), p2s).reshape(Bn, K + 1)
+            rows = np.ascontiguousarray(out.x[:, :, :3]).reshape(-1, 3)
+            out.t = t0 + (int(perceive_phase) + np.arange(K + 1)) * dts
+            if scene.is_dynamic:
+                out.clearance = scene.distance(rows, p2s, t=np.tile(out.t, Bn)).reshape(Bn, K + 1)
+            else:
+                out.clearance = scene.distance(rows, p2s).reshape(Bn, K + 1)
             if keep_img:
                 out.img = ws["images"].numpy()
         self.x0 = out.x[:, -1].copy() if self.B > 1 else out.x[0, -1].copy()

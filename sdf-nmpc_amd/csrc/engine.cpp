@@ -2143,12 +2143,18 @@ struct sdfnmpc_scene {
     int device = 0;
     const sdfnmpc_ctx* ctx = nullptr;
     int S = 0;
-    void* dmem = nullptr;  // count [S] | ScenePrimD [S][32] | ScenePrimF [S][32]
+    void* dmem = nullptr;  // count [S] | ScenePrimD [S][32] | ScenePrimF [S][32] | dynamic: ScenePrimDyn [S][32]
     SceneDev dev{};
+    const ScenePrimDyn* dyn = nullptr;  // non-NULL: a dynamic set (some primitive is oriented or moves)
 };
 
 extern "C" int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
                                     sdfnmpc_scene** out) {
+    return sdfnmpc_scene_create_moving(ctx, S, count, prims, nullptr, out);
+}
+
+extern "C" int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
+                                           const sdfnmpc_prim_motion* motion, sdfnmpc_scene** out) {
     if (!ctx || !count || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create");
     *out = nullptr;
     if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "scene: S must be 1..2^20");
@@ -2162,7 +2168,23 @@ extern "C" int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, c
     // the device image: counts padded to 16 bytes, then the fp64 and the fp32 primitives at a fixed stride of 32
     const size_t cnt_bytes = ((size_t)S * sizeof(int) + 15) & ~(size_t)15;
     const size_t n = (size_t)S * SCENE_MAX_PRIMS;
-    std::vector<char> host(cnt_bytes + n * (sizeof(ScenePrimD) + sizeof(ScenePrimF)), 0);
+    // a set is dynamic when some primitive has a rotation other than the identity or a non-zero yaw_rate, v or amp
+    bool dynamic = false;
+    for (long long i = 0; motion && i < total; ++i) {
+        const sdfnmpc_prim_motion& m = motion[i];
+        bool fin = std::isfinite(m.yaw_rate) && std::isfinite(m.omega) && std::isfinite(m.phase);
+        for (int k = 0; k < 4; ++k) fin = fin && std::isfinite(m.q[k]);
+        for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(m.v[k]) && std::isfinite(m.amp[k]);
+        if (!fin) return fail(SDFNMPC_E_ARG, "scene: a motion record needs finite values");
+        if (m.q[0] == 0.0 && m.q[1] == 0.0 && m.q[2] == 0.0 && m.q[3] == 0.0)
+            return fail(SDFNMPC_E_ARG, "scene: a motion record needs a non-zero quaternion");
+        dynamic = dynamic || m.q[1] != 0.0 || m.q[2] != 0.0 || m.q[3] != 0.0 || m.yaw_rate != 0.0;
+        for (int k = 0; k < 3; ++k) dynamic = dynamic || m.v[k] != 0.0 || m.amp[k] != 0.0;
+    }
+    const size_t static_bytes = cnt_bytes + n * (sizeof(ScenePrimD) + sizeof(ScenePrimF));
+    std::vector<char> host(static_bytes + (dynamic ? n * sizeof(ScenePrimDyn) : 0), 0);
+    ScenePrimDyn* hm = dynamic ? (ScenePrimDyn*)(host.data() + static_bytes) : nullptr;
+    static_assert((sizeof(ScenePrimD) + sizeof(ScenePrimF)) * SCENE_MAX_PRIMS % 16 == 0, "fp64 alignment of the motion block");
     int* hc = (int*)host.data();
     ScenePrimD* hd = (ScenePrimD*)(host.data() + cnt_bytes);
     ScenePrimF* hf = (ScenePrimF*)(host.data() + cnt_bytes + n * sizeof(ScenePrimD));
@@ -2186,6 +2208,36 @@ extern "C" int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, c
                 d.a[k] = a[k];
                 f.a[k] = (float)a[k];
             }
+            if (!hm) continue;
+            // the canonical centred shape and its frame at t = 0: R(q / |q|) of utils/math.py:7-23 in fp64
+            ScenePrimDyn& y = hm[(size_t)s * SCENE_MAX_PRIMS + i];
+            const sdfnmpc_prim_motion& m = motion[p - prims];
+            y.kind = p->kind;
+            if (p->kind == SDFNMPC_PRIM_SPHERE) {
+                for (int k = 0; k < 3; ++k) { y.c0[k] = a[k]; y.h[k] = a[3]; }
+            } else if (p->kind == SDFNMPC_PRIM_BOX) {
+                for (int k = 0; k < 3; ++k) { y.c0[k] = 0.5 * (a[k] + a[3 + k]); y.h[k] = 0.5 * (a[3 + k] - a[k]); }
+            } else {
+                y.c0[0] = a[0]; y.c0[1] = a[1]; y.c0[2] = 0.5 * (a[3] + a[4]);
+                y.h[0] = y.h[1] = a[2]; y.h[2] = 0.5 * (a[4] - a[3]);
+            }
+            const double qs = std::max(std::max(std::fabs(m.q[0]), std::fabs(m.q[1])),
+                                       std::max(std::fabs(m.q[2]), std::fabs(m.q[3])));  // no overflow in the norm
+            double q[4];
+            for (int k = 0; k < 4; ++k) q[k] = m.q[k] / qs;
+            const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+            const double q0 = q[0] / qn, q1 = q[1] / qn, q2 = q[2] / qn, q3 = q[3] / qn;
+            y.R0[0] = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3;
+            y.R0[1] = 2 * (q1 * q2 - q0 * q3);
+            y.R0[2] = 2 * (q1 * q3 + q0 * q2);
+            y.R0[3] = 2 * (q1 * q2 + q0 * q3);
+            y.R0[4] = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3;
+            y.R0[5] = 2 * (q2 * q3 - q0 * q1);
+            y.R0[6] = 2 * (q1 * q3 - q0 * q2);
+            y.R0[7] = 2 * (q2 * q3 + q0 * q1);
+            y.R0[8] = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3;
+            for (int k = 0; k < 3; ++k) { y.v[k] = m.v[k]; y.amp[k] = m.amp[k]; }
+            y.yaw_rate = m.yaw_rate; y.omega = m.omega; y.phase = m.phase;
         }
     }
     ScopedDevice sd(ctx->device);
@@ -2201,6 +2253,7 @@ extern "C" int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, c
     char* d = (char*)sc->dmem;
     sc->dev = SceneDev{S, (const int*)d, (const ScenePrimF*)(d + cnt_bytes + n * sizeof(ScenePrimD)),
                        (const ScenePrimD*)(d + cnt_bytes)};
+    if (dynamic) sc->dyn = (const ScenePrimDyn*)(d + static_bytes);
     *out = sc;
     return SDFNMPC_OK;
 }
@@ -2215,6 +2268,7 @@ extern "C" void sdfnmpc_scene_free(sdfnmpc_scene* sc) {
 // whether an encoder / a scene lives on this very context (sdfnmpc_solver_rollout_perceive, solver.hip)
 extern "C" int sdfnmpc_vae_on_ctx_(const sdfnmpc_vae* v, const sdfnmpc_ctx* ctx) { return v && v->ctx == ctx; }
 extern "C" int sdfnmpc_scene_on_ctx_(const sdfnmpc_scene* sc, const sdfnmpc_ctx* ctx) { return sc && sc->ctx == ctx; }
+extern "C" int sdfnmpc_scene_is_dynamic(const sdfnmpc_scene* sc) { return sc && sc->dyn; }
 
 // the option checks of the two launches a rollout repeats, split from the launches as the plant's are: _args_
 // refuses or fills the kernel's argument block (nothing is launched), _launch_ enqueues a filled block
@@ -2254,6 +2308,16 @@ extern "C" int sdfnmpc_scene_render_launch_(sdfnmpc_ctx* ctx, const SceneRenderA
     return SDFNMPC_OK;
 }
 
+// the scene at time t: a static set takes the launch above whatever t is, a dynamic one its own kernel
+extern "C" int sdfnmpc_scene_render_launch_at_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const SceneRenderArgs* a,
+                                               double t) {
+    if (!sc->dyn) return sdfnmpc_scene_render_launch_(ctx, a);
+    const SceneRenderDynArgs da{*a, sc->dyn, t};
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "scene_render_dyn", [&] { return launch_scene_render_dyn(da, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
 extern "C" int sdfnmpc_scene_pose_args_(const double* B_p_C, const double* B_R_C, int B, const double* x, double* W_p_Bo,
                                         double* W_R_Bo, double* W_p_C, double* W_R_C, ScenePoseArgs* out) {
     if (!B_p_C || !B_R_C || !out) return fail(SDFNMPC_E_ARG, "scene_pose: NULL extrinsics");
@@ -2279,7 +2343,16 @@ extern "C" int sdfnmpc_scene_render(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, c
                                     const double* W_R_C, float* img) {
     SceneRenderArgs a{};
     if (int rc = sdfnmpc_scene_render_args_(ctx, sc, scene_of, o, H, W, scale, B, W_p_C, W_R_C, img, &a)) return rc;
-    return B == 0 ? SDFNMPC_OK : sdfnmpc_scene_render_launch_(ctx, &a);
+    return B == 0 ? SDFNMPC_OK : sdfnmpc_scene_render_launch_at_(ctx, sc, &a, 0.0);  // a dynamic set at t = 0
+}
+
+extern "C" int sdfnmpc_scene_render_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of,
+                                       const sdfnmpc_img_opts* o, int H, int W, float scale, int B, const double* W_p_C,
+                                       const double* W_R_C, double t, float* img) {
+    SceneRenderArgs a{};
+    if (int rc = sdfnmpc_scene_render_args_(ctx, sc, scene_of, o, H, W, scale, B, W_p_C, W_R_C, img, &a)) return rc;
+    if (!std::isfinite(t)) return fail(SDFNMPC_E_ARG, "scene_render: the time must be finite");
+    return B == 0 ? SDFNMPC_OK : sdfnmpc_scene_render_launch_at_(ctx, sc, &a, t);
 }
 
 extern "C" int sdfnmpc_scene_pose(sdfnmpc_ctx* ctx, const double* B_p_C, const double* B_R_C, int B, const double* x,
@@ -2292,6 +2365,11 @@ extern "C" int sdfnmpc_scene_pose(sdfnmpc_ctx* ctx, const double* B_p_C, const d
 
 extern "C" int sdfnmpc_scene_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const double* points,
                                       const int* p_to_scene, long long n, double* out) {
+    return sdfnmpc_scene_distance_at(ctx, sc, points, p_to_scene, nullptr, n, out);
+}
+
+extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const double* points,
+                                         const int* p_to_scene, const double* times, long long n, double* out) {
     if (!ctx || !sc) return fail(SDFNMPC_E_ARG, "scene_distance: NULL context or scene");
     if (sc->device != ctx->device) return fail(SDFNMPC_E_ARG, "scene_distance: the scene lives on another device");
     if (n < 0 || n > 2147483647LL) return fail(SDFNMPC_E_ARG, "scene_distance: n out of range");
@@ -2301,6 +2379,11 @@ extern "C" int sdfnmpc_scene_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc,
     if (!points || !out) return fail(SDFNMPC_E_ARG, "scene_distance: NULL points or output");
     SceneDistArgs a{sc->dev, points, p_to_scene, n, std::max(1LL, n / sc->S), out};
     ScopedDevice sd(ctx->device);
+    if (sc->dyn) {
+        const SceneDistDynArgs da{a, sc->dyn, times};
+        HIPCHK(timed(ctx, "scene_dist_dyn", [&] { return launch_scene_distance_dyn(da, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     HIPCHK(timed(ctx, "scene_dist", [&] { return launch_scene_distance(a, ctx->stream); }));
     return SDFNMPC_OK;
 }

@@ -11,6 +11,9 @@
 //                          with quat2rot(q / |q|) of utils/math.py:7-23)
 //   scene_distance_kernel  fp64, one point per lane: the closed-form signed distance to every primitive, the
 //                          minimum over the scene (negative inside)
+//   scene_render_dyn_kernel, scene_distance_dyn_kernel
+//                          the same two for a scene set whose primitives carry a rigid frame (R(t), c(t)): oriented
+//                          boxes, tilted cylinders, moving obstacles.  Static sets never reach them.
 //
 // Every primitive is convex, so a ray meets it in one parameter interval [tn, tf]: the intersection of the
 // slab intervals (box), of the quadratic's root interval (sphere), or of both (cylinder: side wall and caps).
@@ -194,7 +197,174 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_distance_kernel(SceneDistAr
     A.out[j] = best;
 }
 
+// ---- primitives with a frame that is a function of time (oriented and moving obstacles)
+// c(t) = c0 + v t + amp sin(omega t + phase), R(t) = Rz(yaw_rate t) R0 (row-major), in fp64: the one place both
+// dynamic kernels take a primitive's frame from
+__device__ __forceinline__ void prim_frame(const ScenePrimDyn& P, double t, double* c, double* R) {
+    const double ay = P.yaw_rate * t, ah = P.omega * t + P.phase;
+    const double sy = sin(ay), cy = cos(ay), sh = sin(ah);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        c[j] = P.c0[j] + P.v[j] * t + P.amp[j] * sh;
+        R[j] = cy * P.R0[j] - sy * P.R0[3 + j];
+        R[3 + j] = sy * P.R0[j] + cy * P.R0[3 + j];
+        R[6 + j] = P.R0[6 + j];
+    }
+}
+
+// scene_render_kernel for a dynamic scene set: the same launch geometry, rays, hit rule and output.  Lane i < cnt
+// of a block forms primitive i's frame at time t in fp64 and stores the camera in that frame, o' = R(t)^T (W_p_C -
+// c(t)) and M = R(t)^T W_R_C, rounded to fp32 once (world-scale coordinates cancel in fp64, before the rounding).
+// Every lane then takes its camera-frame direction into the primitive's frame, d' = M d_cam, and runs the interval
+// tests of scene_render_kernel on the canonical centred shape.  A primitive without motion is R = I, v = 0 here.
+__global__ __launch_bounds__(SCENE_BLOCK) void scene_render_dyn_kernel(SceneRenderDynArgs D) {
+    extern __shared__ float tab[];  // spherical: col [2 W] | row [2 H], as in scene_render_kernel
+    __shared__ __attribute__((aligned(16))) ScenePrimFrame fr[SCENE_MAX_PRIMS];
+    static_assert(sizeof(ScenePrimFrame) == 64, "four 16-byte reads");
+    const SceneRenderArgs& A = D.r;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int s = A.scene_of ? min(max(A.scene_of[b], 0), A.sc.S - 1) : 0;
+    const int cnt = min(A.sc.count[s], SCENE_MAX_PRIMS);
+    if (tid < cnt) {
+        const ScenePrimDyn& P = D.dyn[(size_t)s * SCENE_MAX_PRIMS + tid];
+        double c[3], R[9], e[3];
+        prim_frame(P, D.t, c, R);
+        const double* Wp = A.W_p_C + (size_t)b * 3;
+        const double* WR = A.W_R_C + (size_t)b * 9;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) e[j] = Wp[j] - c[j];
+        ScenePrimFrame F;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            F.o[j] = (float)(R[j] * e[0] + R[3 + j] * e[1] + R[6 + j] * e[2]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) F.M[j * 3 + k] = (float)(R[j] * WR[k] + R[3 + j] * WR[3 + k] + R[6 + j] * WR[6 + k]);
+        }
+        F.h0 = (float)P.h[0];
+        F.h1 = (float)P.h[1];
+        F.hz = (float)P.h[2];
+        F.kind = P.kind;
+        fr[tid] = F;
+    }
+    const int w = A.W, h = A.H;
+    if (A.is_spherical) {
+        for (int t = tid; t < w + h; t += SCENE_BLOCK) {
+            const bool is_col = t < w;
+            const int i = is_col ? t : t - w;
+            const float f = 1.f - (float)(2 * i + 1) / (float)(is_col ? w : h);
+            const float ang = (is_col ? A.hfov : A.vfov) * f;
+            float* dst = is_col ? tab + 2 * t : tab + 2 * w + 2 * i;
+            dst[0] = cosf(ang);
+            dst[1] = sinf(ang);
+        }
+    }
+    __syncthreads();
+    const long long pix = (long long)blockIdx.x * SCENE_BLOCK + tid;
+    if (pix >= (long long)h * w) return;
+    const int v = (int)(pix / w), u = (int)(pix - (long long)v * w);
+
+    float cx, cy, cz;  // unit ray direction in the camera frame
+    if (A.is_spherical) {
+        const float ca = tab[2 * u], sa = tab[2 * u + 1], ce = tab[2 * w + 2 * v], se = tab[2 * w + 2 * v + 1];
+        cx = ce * ca;
+        cy = ce * sa;
+        cz = se;
+    } else {
+        const float ty = fmaf(A.ty1, (float)u, A.ty0), tz = fmaf(A.tz1, (float)v, A.tz0);
+        cx = __builtin_amdgcn_rsqf(fmaf(ty, ty, fmaf(tz, tz, 1.f)));
+        cy = ty * cx;
+        cz = tz * cx;
+    }
+
+    float best = INFINITY;
+    for (int i = 0; i < cnt; ++i) {  // wave-uniform: one scene per block
+        const float4* q = (const float4*)&fr[i];
+        const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+        const float ox = q0.x, oy = q0.y, oz = q0.z, h0 = q0.w, h2z = q3.z, h1 = q3.w;
+        const float dx = fmaf(q1.x, cx, fmaf(q1.y, cy, q1.z * cz));  // d' = M d_cam
+        const float dy = fmaf(q1.w, cx, fmaf(q2.x, cy, q2.y * cz));
+        const float dz = fmaf(q2.z, cx, fmaf(q2.w, cy, q3.x * cz));
+        const int kind = __builtin_amdgcn_readfirstlane(__float_as_int(q3.y));  // one scene per block: uniform
+        float tn = -INFINITY, tf = INFINITY;
+        if (kind == 0) {  // sphere of radius h0 about the origin
+            const float ex = -ox, ey = -oy, ez = -oz;
+            const float bb = fmaf(ex, dx, fmaf(ey, dy, ez * dz));
+            const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey), wz = fmaf(-bb, dz, ez);
+            const float hh = fmaf(h0, h0, -fmaf(wx, wx, fmaf(wy, wy, wz * wz)));  // r^2 - |w|^2
+            const float cc = fmaf(ex, ex, fmaf(ey, ey, ez * ez)) - h0 * h0;
+            if (hh >= 0.f) root_interval(bb, cc, fsqrt(hh), tn, tf);
+            else tf = -INFINITY;
+        } else if (kind == 1) {  // box of half extents h0, h1, h2z
+            slab(-h0, h0, ox, frcp(dx), tn, tf);
+            slab(-h1, h1, oy, frcp(dy), tn, tf);
+            slab(-h2z, h2z, oz, frcp(dz), tn, tf);
+        } else {  // capped cylinder along its own z: radius h0, half height h2z
+            const float ex = -ox, ey = -oy;
+            const float aa = fmaf(dx, dx, dy * dy), e2 = fmaf(ex, ex, ey * ey);
+            if (aa > 1e-12f) {
+                const float k = frcp(aa);
+                const float bb = fmaf(ex, dx, ey * dy) * k;
+                const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey);
+                const float hh = fmaf(h0, h0, -fmaf(wx, wx, wy * wy));
+                if (hh >= 0.f) root_interval(bb, (e2 - h0 * h0) * k, fsqrt(hh * k), tn, tf);
+                else tf = -INFINITY;
+            } else if (e2 > h0 * h0) {
+                tf = -INFINITY;
+            }
+            slab(-h2z, h2z, oz, frcp(dz), tn, tf);  // the caps
+        }
+        if (tn <= tf && tf >= 0.f) best = fminf(best, fmaxf(tn, 0.f));
+    }
+    float val = A.dmax;  // a miss
+    if (best < INFINITY) val = fminf(A.is_depth ? best * cx : best, A.dmax);
+    A.img[((size_t)b * h + v) * w + u] = val * A.scale;
+}
+
+// scene_distance_kernel for a dynamic scene set: the point is taken into every primitive's frame at the point's own
+// time, q = R(t)^T (p - c(t)), then the same closed forms on the canonical shape
+__global__ __launch_bounds__(SCENE_BLOCK) void scene_distance_dyn_kernel(SceneDistDynArgs D) {
+    const SceneDistArgs& A = D.d;
+    const long long j = (long long)blockIdx.x * SCENE_BLOCK + threadIdx.x;
+    if (j >= A.n) return;
+    const long long s = A.p_to_scene ? (long long)min(max(A.p_to_scene[j], 0), A.sc.S - 1) : j / A.per_scene;
+    const ScenePrimDyn* P = D.dyn + s * SCENE_MAX_PRIMS;
+    const int cnt = min(A.sc.count[s], SCENE_MAX_PRIMS);
+    const double t = D.times ? D.times[j] : 0.0;
+    const double px = A.points[j * 3], py = A.points[j * 3 + 1], pz = A.points[j * 3 + 2];
+    double best = INFINITY;
+    for (int i = 0; i < cnt; ++i) {
+        double c[3], R[9];
+        prim_frame(P[i], t, c, R);
+        const double ex = px - c[0], ey = py - c[1], ez = pz - c[2];
+        const double qx = R[0] * ex + R[3] * ey + R[6] * ez;
+        const double qy = R[1] * ex + R[4] * ey + R[7] * ez;
+        const double qz = R[2] * ex + R[5] * ey + R[8] * ez;
+        const double* h = P[i].h;
+        double d;
+        if (P[i].kind == 0) d = sqrt(qx * qx + qy * qy + qz * qz) - h[0];
+        else if (P[i].kind == 1) d = sd_excess3(fabs(qx) - h[0], fabs(qy) - h[1], fabs(qz) - h[2]);
+        else d = sd_excess3(sqrt(qx * qx + qy * qy) - h[0], fabs(qz) - h[2], -INFINITY);
+        best = fmin(best, d);
+    }
+    A.out[j] = best;
+}
+
 }  // namespace
+
+hipError_t launch_scene_render_dyn(const SceneRenderDynArgs& a, hipStream_t s) {
+    if (a.r.B <= 0) return hipSuccess;
+    const long long tiles = ((long long)a.r.H * a.r.W + SCENE_BLOCK - 1) / SCENE_BLOCK;
+    hipLaunchKernelGGL(scene_render_dyn_kernel, dim3((unsigned)tiles, (unsigned)a.r.B), dim3(SCENE_BLOCK),
+                       scene_render_lds_bytes(a.r.H, a.r.W, a.r.is_spherical), s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_scene_distance_dyn(const SceneDistDynArgs& a, hipStream_t s) {
+    if (a.d.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scene_distance_dyn_kernel, dim3((unsigned)((a.d.n + SCENE_BLOCK - 1) / SCENE_BLOCK)),
+                       dim3(SCENE_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_scene_render(const SceneRenderArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;

@@ -1,5 +1,6 @@
 // Analytic scenes (csrc/scene.hip): range / depth images of a known world rendered on the device, the camera
-// pose of a state, and the exact signed distance to the scene.  The producer side of the perception loop whose
+// pose of a state, and the exact signed distance to the scene; static scenes, and scenes whose primitives carry a
+// rigid frame that is a function of time (oriented and moving obstacles).  The producer side of the perception loop whose
 // consumers are vae_enc.hip (images -> latents), ref_pack.hip (latents + pose -> p) and df_truth.hip (labels).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +20,24 @@ struct ScenePrimF {  // 32 bytes: two 16-byte LDS reads
 struct ScenePrimD {
     double a[6];
     int kind, pad;
+};
+
+// A primitive of a dynamic scene set: the canonical shape (centred: sphere h = (r, -, -), box h = half extents,
+// cylinder h = (r, r, half height)) with its frame at time t, c(t) = c0 + v t + amp sin(omega t + phase),
+// R(t) = Rz(yaw_rate t) R0 (R0 row-major, formed from the unit quaternion on the host in fp64)
+struct ScenePrimDyn {  // 200 bytes
+    double c0[3], R0[9], v[3], amp[3];
+    double yaw_rate, omega, phase;
+    double h[3];
+    int kind, pad;
+};
+// what a block of the dynamic render kernel stages per primitive: the camera origin o' = R(t)^T (W_p_C - c(t)) and
+// M = R(t)^T W_R_C, formed in fp64 and rounded once
+struct ScenePrimFrame {  // 64 bytes: four 16-byte LDS reads; what only a box reads comes last
+    float o[3], h0;      // sphere / cylinder: the radius; box: the half extent along x
+    float M[9];
+    int kind;
+    float hz, h1;        // box / cylinder: the half extent along z; box: along y
 };
 
 // S scenes of up to SCENE_MAX_PRIMS primitives each, in both precisions, on the device
@@ -42,6 +61,12 @@ struct SceneRenderArgs {
     float* img;              // [B][H][W]
 };
 
+struct SceneRenderDynArgs {
+    SceneRenderArgs r;
+    const ScenePrimDyn* dyn; // [S][SCENE_MAX_PRIMS]
+    double t;
+};
+
 struct ScenePoseArgs {
     int B;
     const double* x;         // [B][10]
@@ -57,6 +82,12 @@ struct SceneDistArgs {
     double* out;             // [n]
 };
 
+struct SceneDistDynArgs {
+    SceneDistArgs d;
+    const ScenePrimDyn* dyn; // [S][SCENE_MAX_PRIMS]
+    const double* times;     // [n] or nullptr (t = 0)
+};
+
 inline size_t scene_render_lds_bytes(int h, int w, int is_spherical) {
     return is_spherical ? (size_t)2 * ((size_t)h + (size_t)w) * sizeof(float) : 0;
 }
@@ -64,5 +95,7 @@ inline size_t scene_render_lds_bytes(int h, int w, int is_spherical) {
 hipError_t launch_scene_render(const SceneRenderArgs& a, hipStream_t s);
 hipError_t launch_scene_pose(const ScenePoseArgs& a, hipStream_t s);
 hipError_t launch_scene_distance(const SceneDistArgs& a, hipStream_t s);
+hipError_t launch_scene_render_dyn(const SceneRenderDynArgs& a, hipStream_t s);
+hipError_t launch_scene_distance_dyn(const SceneDistDynArgs& a, hipStream_t s);
 
 }  // namespace sdfn

@@ -9,6 +9,7 @@
 // arena, and the asynchronous step / wait split that lets one host thread keep several devices busy.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -28,7 +29,8 @@ extern "C" int sdfnmpc_scene_render_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene*
                                           const sdfnmpc_img_opts* o, int H, int W, float scale, int B,
                                           const double* W_p_C, const double* W_R_C, float* img,
                                           sdfn::SceneRenderArgs* out);
-extern "C" int sdfnmpc_scene_render_launch_(sdfnmpc_ctx* ctx, const sdfn::SceneRenderArgs* a);
+extern "C" int sdfnmpc_scene_render_launch_at_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const sdfn::SceneRenderArgs* a,
+                                               double t);
 extern "C" int sdfnmpc_scene_pose_args_(const double* B_p_C, const double* B_R_C, int B, const double* x, double* W_p_Bo,
                                         double* W_R_Bo, double* W_p_C, double* W_R_C,
                                         sdfn::ScenePoseArgs* out);
@@ -386,7 +388,14 @@ extern "C" int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_a
 
 extern "C" int sdfnmpc_solver_rollout_perceive(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
                                                const sdfnmpc_perceive_args* pc) {
+    return sdfnmpc_solver_rollout_perceive_at(s, a, pc, 0.0, 0.0);
+}
+
+extern "C" int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
+                                                  const sdfnmpc_perceive_args* pc, double t0, double dt) {
     if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout");
+    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
     if (a->steps < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
     if (!a->x_log || !a->u_log) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: x_log and u_log are required");
     // every refusal before the first launch: the plant's options, then what sdfnmpc_pack_refs would refuse
@@ -446,7 +455,11 @@ extern "C" int sdfnmpc_solver_rollout_perceive(sdfnmpc_solver* s, const sdfnmpc_
     for (int k = 0; k < a->steps; ++k) {
         if (pc && (k + pc->phase) % pc->every == 0) {  // a new image from the current state: pose, render, encode, set_latent
             if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
-            if (int rc = sdfnmpc_scene_render_launch_(s->ctx, &sra)) return rc;
+            // the scene's time at step k, t0 + (phase + k) dt: the product is rounded on its own (a volatile
+            // temporary keeps the compiler from contracting it into a fused multiply-add), as a host loop forms it
+            volatile double steps_dt = (double)(pc->phase + k) * dt;
+            const double t = t0 + steps_dt;
+            if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pc->scene, &sra, t)) return rc;
             if (int rc = sdfnmpc_vae_encode(s->ctx, pc->vae, &vo, pc->images, pc->latent, pc->latent64)) return rc;
             if (int rc = sdfnmpc_pack_refs(s->ctx, &lo, &lra)) return rc;
         }

@@ -12,6 +12,12 @@ instance's current pose inside the device loop.
     img = scene.render_from_state(x, cfg)            # DeviceArray [B, h, w] float32, normalised by sensor.dmax
     d = scene.distance(points)                       # numpy [n] float64, negative inside
 
+Primitives may be oriented and may move: ``Scene.moving(prim, v=, q= | rpy=, yaw_rate=, amp=, omega=, phase=)`` gives
+a primitive the rigid frame c(t) = c0 + v t + amp sin(omega t + phase), R(t) = Rz(yaw_rate t) R(q) about its reference
+point c0 (sphere: centre; box: (lo + hi) / 2; cylinder: (cx, cy, (z0 + z1) / 2)) -- a box with a rotation is an
+oriented box, a sphere with v a moving obstacle.  ``render(..., t=)``, ``render_from_state(..., t=)`` and
+``distance(..., t=)`` then show the scene at time t; a scene without such primitives is the static scene whatever t.
+
 World frame z up; camera frame x forward, y left, z up, the pixel grid of ``ColChecker``.  There is no CPU path.
 """
 from __future__ import annotations
@@ -19,6 +25,13 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+
+
+def _three(a, name):
+    a = [float(v) for v in a]
+    if len(a) != 3:
+        raise ValueError(f"Scene.moving: {name} has three components")
+    return a
 
 
 class Scene:
@@ -40,19 +53,41 @@ class Scene:
         """A capped cylinder along z: axis through center_xy, z in [z0, z1]."""
         return ("cylinder", [float(v) for v in center_xy] + [float(radius), float(z0), float(z1)])
 
+    @staticmethod
+    def moving(prim, *, v=(0.0, 0.0, 0.0), q=None, rpy=None, yaw_rate=0.0, amp=(0.0, 0.0, 0.0), omega=0.0, phase=0.0):
+        """The primitive with a frame that depends on time: orientation q = (w, x, y, z) of any non-zero norm or
+        rpy = (roll, pitch, yaw), ZYX (not both), about its reference point; yaw_rate [rad/s] about the world z axis;
+        velocity v [m/s]; a harmonic term amp sin(omega t + phase).  The library checks the values when the scene is
+        created (SdfnmpcError: a non-finite value, a zero quaternion)."""
+        if q is not None and rpy is not None:
+            raise ValueError("Scene.moving: give q or rpy, not both")
+        if rpy is not None:
+            (cr, sr), (cp, sp), (cy, sy) = ((np.cos(0.5 * float(a)), np.sin(0.5 * float(a))) for a in rpy)
+            q = (cr * cp * cy + sr * sp * sy, sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy,
+                 cr * cp * sy - sr * sp * cy)
+        m = dict(q=[float(a) for a in (q if q is not None else (1.0, 0.0, 0.0, 0.0))], v=_three(v, "v"),
+                 amp=_three(amp, "amp"), yaw_rate=float(yaw_rate), omega=float(omega), phase=float(phase))
+        if len(m["q"]) != 4:
+            raise ValueError("Scene.moving: q = (w, x, y, z)")
+        return (prim[0], list(prim[1]), m)
+
     def __init__(self, ctx: "_lib.Context", prims, scene_of=None):
-        is_prim = lambda p: isinstance(p, tuple) and len(p) == 2 and isinstance(p[0], (str, int))
+        is_prim = lambda p: isinstance(p, tuple) and len(p) in (2, 3) and isinstance(p[0], (str, int))
         scenes = [list(prims)] if all(is_prim(p) for p in prims) else [list(s) for s in prims]
-        flat = []
+        flat, motion = [], []
         for s in scenes:
-            for kind, vals in s:
+            for kind, vals, *mo in s:
                 vals = list(vals)
                 if len(vals) > 6:
                     raise ValueError(f"primitive {kind!r}: at most 6 values, got {len(vals)}")
                 # an unknown kind goes to the library as it is (it refuses it)
                 flat.append((_lib.PRIM_KINDS.get(kind, kind if isinstance(kind, int) else -1), vals))
+                motion.append(mo[0] if mo else None)
         self.ctx, self.S = ctx, len(scenes)
-        self.h = _lib.scene_create(ctx, [len(s) for s in scenes], flat)
+        # plain primitives only: the call a scene has always made
+        self.h = _lib.scene_create(ctx, [len(s) for s in scenes], flat,
+                                   motion if any(m is not None for m in motion) else None)
+        self.is_dynamic = bool(_lib.load().sdfnmpc_scene_is_dynamic(self.h))
         self.scene_of = self._scene_of = None
         if scene_of is not None:
             so = np.ascontiguousarray(scene_of, dtype=np.int32).ravel()
@@ -88,11 +123,12 @@ class Scene:
         return 1.0 / float(cfg.sensor.dmax) if normalized else 1000.0 / float(cfg.sensor.mm_resolution)
 
     # ---- the three kernels
-    def render(self, W_p_C, W_R_C, cfg, shape=None, normalized=True, out=None):
+    def render(self, W_p_C, W_R_C, cfg, shape=None, normalized=True, out=None, t=0.0):
         """Images [B, h, w] float32 (a DeviceArray; asynchronous on the context stream) of the camera poses W_p_C
         [B, 3], W_R_C [B, 3, 3] (host or device fp64) with the sensor of cfg: range, or depth with
         sensor.is_depth; pinhole or spherical pixels; clipped at sensor.dmax.  shape (h, w) defaults to
-        sensor.shape_imgs[-2:].  out: a float32 DeviceArray [B, h, w] to write instead of a new one."""
+        sensor.shape_imgs[-2:].  out: a float32 DeviceArray [B, h, w] to write instead of a new one.  t: the time the
+        scene is shown at (finite; a scene without moving or oriented primitives looks the same at every t)."""
         h, w = (int(v) for v in (shape if shape is not None else cfg.sensor.shape_imgs[-2:]))
         B = int(np.prod(W_p_C.shape)) // 3 if hasattr(W_p_C, "data_ptr") else np.asarray(W_p_C).reshape(-1, 3).shape[0]
         self._batch(B)
@@ -101,8 +137,12 @@ class Scene:
             out = _lib.DeviceArray(self.ctx, (B, h, w), np.float32)
         elif tuple(out.shape) != (B, h, w) or np.dtype(out.dtype) != np.float32:
             raise ValueError(f"out must be float32 [{B}, {h}, {w}]")
-        _lib.scene_render(self.ctx, self.h, self._scene_of, self.img_opts(cfg), h, w, self.scale(cfg, normalized), B, p, R,
-                          out)
+        if isinstance(t, float) and t == 0.0:
+            _lib.scene_render(self.ctx, self.h, self._scene_of, self.img_opts(cfg), h, w, self.scale(cfg, normalized), B,
+                              p, R, out)
+        else:
+            _lib.scene_render_at(self.ctx, self.h, self._scene_of, self.img_opts(cfg), h, w, self.scale(cfg, normalized),
+                                 B, p, R, float(t), out)
         out._inputs = (p, R)  # temporaries of an asynchronous launch stay alive with its result
         return out
 
@@ -117,16 +157,17 @@ class Scene:
         out["W_p_Bo"]._inputs = dx
         return out
 
-    def render_from_state(self, x, cfg, shape=None, normalized=True, out=None):
+    def render_from_state(self, x, cfg, shape=None, normalized=True, out=None, t=0.0):
         """``render`` from the camera poses of the states x (``pose``); the result carries them as ``.pose``."""
         ps = self.pose(x, cfg)
-        img = self.render(ps["W_p_C"], ps["W_R_C"], cfg, shape, normalized, out)
+        img = self.render(ps["W_p_C"], ps["W_R_C"], cfg, shape, normalized, out, t)
         img.pose = ps  # the poses the images were taken from (device arrays, as ``pose`` returns them)
         return img
 
-    def distance(self, points, p_to_scene=None):
+    def distance(self, points, p_to_scene=None, t=None):
         """Signed distance [n] (numpy fp64) from world points [n, 3] to their scene, negative inside.  p_to_scene
-        [n]: the scene of each point; None: the default ordering, point j -> scene j // (n / S)."""
+        [n]: the scene of each point; None: the default ordering, point j -> scene j // (n / S).  t: the time each
+        point is measured at, a scalar or [n] (finite); None: t = 0."""
         pts = self._f64(points, (-1, 3) if not hasattr(points, "data_ptr") else tuple(points.shape))
         n = int(np.prod(pts.shape)) // 3
         p2s = None
@@ -135,8 +176,18 @@ class Scene:
             if a.size != n or (n and (a.min() < 0 or a.max() >= self.S)):
                 raise ValueError(f"p_to_scene needs one entry in [0, {self.S}) per point")
             p2s = _lib.DeviceArray.from_numpy(self.ctx, a)
+        times = None
+        if t is not None:
+            a = np.asarray(t, dtype=np.float64)
+            a = np.full(n, float(a)) if a.ndim == 0 else np.ascontiguousarray(a).ravel()
+            if a.size != n or not np.isfinite(a).all():
+                raise ValueError(f"t needs one finite time per point ({n}) or a scalar")
+            times = _lib.DeviceArray.from_numpy(self.ctx, a)
         out = _lib.DeviceArray(self.ctx, (n,), np.float64)
-        _lib.scene_distance(self.ctx, self.h, pts, p2s, n, out)
+        if times is None:
+            _lib.scene_distance(self.ctx, self.h, pts, p2s, n, out)
+        else:
+            _lib.scene_distance_at(self.ctx, self.h, pts, p2s, times, n, out)
         return out.numpy()  # the copy waits for the launch
 
     def close(self):

@@ -3,7 +3,10 @@ scene every `--every`-th step, run two ways on one controller configuration: as 
 launch sequence, one wait), and as the host-driven loop built from the public pieces (render_from_state -> set_img ->
 encode_to -> set_x0 -> gen_refs_device -> solve -> plant_step -> download the state).  Both use the same kernels, so
 the loops compute the same bits (checked) and the difference is the host's.  Also the three scene kernels' own times
-(HIP events): scene_render at 270 x 480 with 16 primitives next to its floors, scene_pose, scene_dist.
+(HIP events): scene_render at 270 x 480 with 16 primitives next to its floors, scene_pose, scene_dist -- and the
+dynamic kernels on the same scene with every primitive moving, from the same run.  --moving gives the loops' scene
+those motions (the host-driven loop renders at t = k * dt, the device loop runs the scene's clock);
+--kernels-only skips the loops.
 
 One configuration per run (give every run its own time limit):
     timeout 600 python tools/perceive_probe.py --B 1024 --N 40 --every 1
@@ -46,6 +49,19 @@ def forest(n_prims, seed=3):
     return prims
 
 
+def moving_forest(n_prims, seed=3):
+    """The forest with every primitive moving: the floor slides, the pillars lean, drift and turn, the balls drift and
+    bob."""
+    rng = np.random.default_rng(seed + 100)
+    prims = forest(n_prims, seed)
+    out = [Scene.moving(prims[0], v=(0.1, 0.05, 0.0))]
+    for p in prims[1:]:
+        out.append(Scene.moving(p, v=(*rng.uniform(-0.3, 0.3, 2), 0.0), rpy=(*rng.uniform(-0.3, 0.3, 2), 0.0),
+                                yaw_rate=rng.uniform(-0.5, 0.5), amp=(0.0, 0.0, rng.uniform(0.0, 0.3)), omega=1.5,
+                                phase=rng.uniform(0.0, 6.0)))
+    return out
+
+
 def host_loop(n, vae, scene, x0, wps, K, every, plant):
     B, ctx = max(n.B, 1), n.ocp.ctx
     dx = _lib.DeviceArray(ctx, (B, 10))
@@ -54,7 +70,7 @@ def host_loop(n, vae, scene, x0, wps, K, every, plant):
     for k in range(K):
         n.set_x0(sq(x))
         if k % every == 0:
-            img = scene.render_from_state(x, n.cfg, normalized=False)
+            img = scene.render_from_state(x, n.cfg, normalized=False, t=0.0 + k * plant.dt)
             vae.set_img(img)
             vae.encode_to(n, img.pose["W_p_Bo"], img.pose["W_R_Bo"])
         n.gen_refs_device("wps", wps=wps)
@@ -67,8 +83,9 @@ def host_loop(n, vae, scene, x0, wps, K, every, plant):
 
 
 def kernel_times(ctx, cfg, B, res):
-    """HIP events around each launch of the three scene kernels (16 primitives, the sensor's 270 x 480 image)."""
-    scene = Scene(ctx, forest(16))
+    """HIP events around each launch of the scene kernels (16 primitives, the sensor's 270 x 480 image): the static
+    ones on the static forest, the dynamic ones on the same forest with every primitive moving."""
+    scene, dyn = Scene(ctx, forest(16)), Scene(ctx, moving_forest(16))
     rng = np.random.default_rng(0)
     x = np.zeros((B, 10))
     x[:, :3] = rng.uniform(-1, 1, (B, 3))
@@ -80,9 +97,12 @@ def kernel_times(ctx, cfg, B, res):
     ps = scene.pose(dx, cfg)
     pts = _lib.DeviceArray.from_numpy(ctx, np.tile(x[:, None, :3], (1, 51, 1)).reshape(-1, 3))
     dist = _lib.DeviceArray(ctx, (B * 51,))
+    times = _lib.DeviceArray.from_numpy(ctx, np.tile(np.arange(51) * 0.05, B))
     calls = {"scene_render": lambda: scene.render(ps["W_p_C"], ps["W_R_C"], cfg, out=out),
              "scene_pose": lambda: _lib.scene_pose(ctx, cfg.sensor.B_p_C, cfg.sensor.B_R_C, B, dx, *ps.values()),
-             "scene_dist": lambda: _lib.scene_distance(ctx, scene.h, pts, None, B * 51, dist)}
+             "scene_dist": lambda: _lib.scene_distance(ctx, scene.h, pts, None, B * 51, dist),
+             "scene_render_dyn": lambda: dyn.render(ps["W_p_C"], ps["W_R_C"], cfg, out=out, t=1.3),
+             "scene_dist_dyn": lambda: _lib.scene_distance_at(ctx, dyn.h, pts, None, times, B * 51, dist)}
     for name, fn in calls.items():
         for _ in range(5):
             fn()
@@ -100,6 +120,9 @@ def kernel_times(ctx, cfg, B, res):
     res["render_floor_store_us"] = rays * 4 / HBM_BYTES_PER_S * 1e6
     res["render_floor_valu_us"] = rays * 16 * INSTR_PER_TEST / LANE_INSTR_PER_S * 1e6
     res["render_floor_valu_2cycle_us"] = rays * 16 * INSTR_PER_TEST / LANE_INSTR_PER_S_2 * 1e6
+    res["render_dyn_over_static"] = res["scene_render_dyn_us"] / res["scene_render_us"]
+    res["render_dyn_hit_share"] = float((out.numpy() < 1.0).mean())  # the last launches wrote the moving forest
+    scene.render(ps["W_p_C"], ps["W_R_C"], cfg, out=out)
     res["render_hit_share"] = float((out.numpy() < 1.0).mean())
 
 
@@ -110,15 +133,26 @@ def main():
     ap.add_argument("--K", type=int, default=50)
     ap.add_argument("--every", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--moving", action="store_true", help="the loops' scene moves (moving_forest)")
+    ap.add_argument("--kernels-only", action="store_true", help="only the scene kernels' own times")
     a = ap.parse_args()
     warnings.simplefilter("ignore")
     cfg = Config(mpc__N=a.N)
-    res = {"B": a.B, "N": a.N, "K": a.K, "every": a.every}
+    res = {"B": a.B, "N": a.N, "K": a.K, "every": a.every, "moving": a.moving}
+    if a.kernels_only:
+        ctx = _lib.Context(0)
+        kernel_times(ctx, cfg, a.B, res)
+        print(f"B={a.B}: scene_render {res['scene_render_us']:.1f} us, scene_render_dyn {res['scene_render_dyn_us']:.1f} us "
+              f"({res['render_dyn_over_static']:.2f}x), scene_dist {res['scene_dist_us']:.1f} us, scene_dist_dyn "
+              f"{res['scene_dist_dyn_us']:.1f} us")
+        print(json.dumps(res))
+        return
+    make_forest = moving_forest if a.moving else forest
     t_roll, t_host, xr, xh = [], [], None, None
     for rep in range(a.reps + 1):  # repetition 0 warms up (workspaces, code objects) and is not timed
         n, x0, wps = controller(cfg, a.B, 1)
         ctx = n.ocp.ctx
-        scene, vae = Scene(ctx, forest(16)), VaeWrapper(cfg, batch=a.B, ctx=ctx)
+        scene, vae = Scene(ctx, make_forest(16)), VaeWrapper(cfg, batch=a.B, ctx=ctx)
         plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]))
         n.set_x0(x0)
         ctx.synchronize()
@@ -129,7 +163,7 @@ def main():
         n.ocp.close()
         n, x0, wps = controller(cfg, a.B, 1)
         ctx = n.ocp.ctx
-        scene, vae = Scene(ctx, forest(16)), VaeWrapper(cfg, batch=a.B, ctx=ctx)
+        scene, vae = Scene(ctx, make_forest(16)), VaeWrapper(cfg, batch=a.B, ctx=ctx)
         plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]))
         ctx.synchronize()
         t2 = time.perf_counter()
@@ -154,7 +188,8 @@ def main():
           f"{res['scene_render_us']:.1f} us (floors: store {res['render_floor_store_us']:.1f} us, vector ALU "
           f"{res['render_floor_valu_us']:.1f} us at 39 T lane-instructions/s, {res['render_floor_valu_2cycle_us']:.1f} us "
           f"at twice that), scene_pose {res['scene_pose_us']:.1f} us, scene_dist "
-          f"{res['scene_dist_us']:.1f} us")
+          f"{res['scene_dist_us']:.1f} us; on the moving forest scene_render_dyn {res['scene_render_dyn_us']:.1f} us "
+          f"({res['render_dyn_over_static']:.2f}x), scene_dist_dyn {res['scene_dist_dyn_us']:.1f} us")
     print(json.dumps(res))
     if res["rollout_ms_per_step"] > res["host_loop_ms_per_step"]:
         print("NOTE: the rollout was not faster than the host-driven loop in this run")
