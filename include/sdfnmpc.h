@@ -55,6 +55,10 @@
  *   sdfnmpc_solver_rollout_perceive    sdfnmpc_solver_rollout with the perception a user wraps around it every
  *                                      control period: VaeWrapper.set_img / encode (sdf_nmpc/vae.py:29-40) of a new
  *                                      image and Nmpc.set_latent (controller.py:50-54) with the pose at image time
+ *   sdfnmpc_morph / sdfnmpc_outlier_rm Dilate / Erode (and with them Open / Close) and RemoveCloseOutliers
+ *                                      (utils/preprocessing.py:100-259), batched
+ *   sdfnmpc_sensor_apply               ImageAugmenter's noise and erasing (utils/data.py:11-108) as a reproducible
+ *                                      sensor model, also inside the rollout (sdfnmpc_solver_rollout_perceive_sensor)
  *
  * The CasADi external-function symbols that acados links (sdf_l4c, jac_sdf_l4c, ...) are in
  * sdf_l4c.h / libsdf_l4c.so.
@@ -69,7 +73,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 10
+#define SDFNMPC_ABI_VERSION 11
 
 enum {
     SDFNMPC_OK = 0,
@@ -300,7 +304,7 @@ int sdfnmpc_ctx_set_tile_rows(sdfnmpc_ctx* ctx, int rows);
 /* per-kernel HIP-event timing on the context stream (off by default) */
 int sdfnmpc_ctx_enable_timing(sdfnmpc_ctx* ctx, int on);
 /* kernel: "sdf_mlp", "sdf_hoist", "linearize", "rti_qp", "plant", "scene_render", "scene_pose", "scene_dist",
- * "scene_render_dyn", "scene_dist_dyn", ...; synchronizes the stream(s) */
+ * "scene_render_dyn", "scene_dist_dyn", "morph", "outlier_rm", "sensor_degrade", ...; synchronizes the stream(s) */
 int sdfnmpc_ctx_kernel_stats(sdfnmpc_ctx* ctx, const char* kernel, double* total_ms, long long* launches);
 int sdfnmpc_ctx_reset_stats(sdfnmpc_ctx* ctx);
 
@@ -668,6 +672,81 @@ int sdfnmpc_solver_rollout_perceive(sdfnmpc_solver* s, const sdfnmpc_rollout_arg
  * dt < 0. */
 int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
                                        const sdfnmpc_perceive_args* perc, double t0, double dt);
+
+/* ---- image morphology (csrc/morph.hip) ----
+ * The reference's Dilate / Erode (utils/preprocessing.py:100-199) on images in / out [B][H][W] (device float32, in !=
+ * out) with a structuring element kernel [k_h][k_w] (host bytes, row-major; a tap is included where the byte is not
+ * 0), as the reference writes them: the image is padded by origin = (k_h / 2, k_w / 2) on the top / left and by k -
+ * origin - 1 on the bottom / right with the border value -2 (dilate, op 0) or +2 (erode, op 1); the erosion of a pixel
+ * is the minimum over all k_h k_w taps (i, j) of padded[y + i][x + j] + bias(i, j), the bias 0 where the tap is
+ * included and +2 where it is not; the dilation is the maximum with the bias 0 / -2 of the *flipped* element (tap
+ * (i, j) is included where kernel[k_h-1-i][k_w-1-j] is) on the same, unflipped padding -- for an even-sized or
+ * asymmetric element not a textbook dilation.  While an included tap reads a value of the image (the reference's
+ * modules assume images normalised by dmax, in [0, 1]) the result is the plain min / max over the included taps; where
+ * every included tap reads the border value, an erosion of a non-negative image gives the border value 2 itself and a
+ * dilation the largest excluded value minus 2, as the reference's does.  ignore_zeros: zeros count as the border value
+ * during the scan, and a result equal to the border value becomes 0; the input is not modified (the reference's
+ * module overwrites its input).  The results are the reference's bit for bit.  Asynchronous on the context stream;
+ * B == 0 is a no-op.  SDFNMPC_E_ARG (nothing is launched, out untouched): NULL arguments, in == out, op not 0 / 1, B < 0 or > 65535,
+ * H or W < 1 (or B H W beyond 2^31 - 1), k_h or k_w outside 1..21, an element without a 1. */
+#define SDFNMPC_MORPH_DILATE 0
+#define SDFNMPC_MORPH_ERODE 1
+#define SDFNMPC_MORPH_K_MAX 21
+int sdfnmpc_morph(sdfnmpc_ctx* ctx, int op, const unsigned char* kernel, int k_h, int k_w, int ignore_zeros,
+                  const float* in, int B, int H, int W, float* out);
+/* RemoveCloseOutliers(kernel_size, min_range) (utils/preprocessing.py:241-259): t = in < min_range ? 0 : in, the
+ * opening of t (erosion, then dilation, by a kernel_size x kernel_size element of ones, ignore_zeros off), and the
+ * value of t restored where the opening is > 0.  min_range is in the image's own units.  kernel_size 3 is one fused
+ * launch ("outlier_rm" in sdfnmpc_ctx_kernel_stats) without an intermediate image in device memory; any other size
+ * takes a threshold launch, two sdfnmpc_morph launches and a restore launch through workspaces of the context.  Both
+ * give what the composition of the reference's modules gives.  SDFNMPC_E_ARG (nothing is launched): NULL arguments,
+ * in == out, B < 0 or > 65535, H or W < 1 (or B H W beyond 2^31 - 1), kernel_size outside 1..21, a non-finite min_range. */
+int sdfnmpc_outlier_rm(sdfnmpc_ctx* ctx, int kernel_size, float min_range, const float* in, int B, int H, int W,
+                       float* out);
+
+/* ---- sensor degradation (csrc/sensor.hip) ----
+ * What a real depth camera does to the exact image sdfnmpc_scene_render gives, in place on img [B][H][W] (device
+ * float32) in the image's own units (raw or normalised; vmax is the image's value at dmax).  Per pixel with value v:
+ *   1. miss     with miss_invalid, v >= vmax -> 0 (no return)
+ *   2. noise    v == 0 stays 0 (utils/data.py:67); else v <- clamp(v + (a + b v^2) z, 0, vmax), z ~ N(0, 1)
+ *   3. dropout  with probability p_thresh / 2^32 the pixel becomes 0
+ *   4. boxes    the pixel becomes 0 inside any of the image's erased rectangles
+ * The randomness is counter-based: one Philox4x32-10 call per pixel with the 64-bit seed as the key (low word first)
+ * and the counter (pixel index y W + x, frame, stream, 0), stream = stream_id[b] (device int32 [B]; NULL: b).  Words 0
+ * and 1 give u = ((w >> 8) + 1) 2^-24 in (0, 1] and z = sqrtf(-2 logf(u1)) cosf(2 pi u2); word 2 < p_thresh (unsigned)
+ * is the dropout decision.  No atomics, no state: the result depends on (seed, stream, frame, pixel, v) only, not on
+ * the instance's place in the batch, the launch shape or earlier launches.
+ * boxes: device int16 [n_frames][B][max_boxes][4] = (y0, x0, h, w) per box, h == 0: none; the launch reads the
+ * entries of frame % n_frames and of instance b.  NULL: no boxes (n_frames and max_boxes are then ignored).
+ * outlier_rm: after the degradation, sdfnmpc_outlier_rm(3, min_range) of the image through the caller's workspace
+ * scratch [B][H][W] (required exactly then), and the result copied back into img.
+ * SDFNMPC_E_ARG (nothing is launched, img untouched): NULL ctx / opts / img, B < 0 or > 65535, H or W < 1 (or B H W
+ * beyond 2^31 - 1), a non-finite or negative a or b, vmax not positive and finite, frame < 0, a box table with n_frames
+ * < 1 or max_boxes outside 0..8, outlier_rm without scratch or with a non-finite min_range.  B == 0 is a no-op. */
+typedef struct {
+    uint64_t seed;
+    float a, b;                    /* noise standard deviation a + b v^2, image units */
+    float vmax;
+    uint32_t p_thresh;             /* floor(p 2^32) */
+    int miss_invalid;
+    int outlier_rm;
+    float min_range;               /* image units (outlier_rm) */
+    const int16_t* boxes;
+    int n_frames, max_boxes;
+    const int* stream_id;
+} sdfnmpc_sensor_opts;
+int sdfnmpc_sensor_apply(sdfnmpc_ctx* ctx, const sdfnmpc_sensor_opts* opts, int frame, float* img, int B, int H, int W,
+                         float* scratch);
+
+/* sdfnmpc_solver_rollout_perceive_at with a sensor model between the renderer and the encoder: at a perceiving step k
+ * the sequence is pose, render, sdfnmpc_sensor_apply(sensor, frame = perc->phase + k, perc->images, scratch), encode,
+ * pack -- so a rollout cut into chunks degrades as the uncut one does, and a host loop that calls sdfnmpc_sensor_apply
+ * with that frame between the render and the encoder gets the same bits.  perc->images holds the degraded image
+ * afterwards.  sensor == NULL is exactly sdfnmpc_solver_rollout_perceive_at (scratch is ignored).  Also refused, before
+ * the first launch: a sensor without perc, what sdfnmpc_sensor_apply refuses, phase + steps beyond 2^31 - 1. */
+int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
+                                           const sdfnmpc_perceive_args* perc, double t0, double dt,
+                                           const sdfnmpc_sensor_opts* sensor, float* scratch);
 
 /* ---- shooting grid (host, bit-exact numpy.linspace/diff semantics of ocp.py:21-27) ---- */
 int sdfnmpc_shooting_grid(int N, double T, int uniform, int nb_short_nodes, double dt_short, double* nodes,

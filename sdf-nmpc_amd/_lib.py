@@ -40,6 +40,7 @@ SYMBOLS = [
     "sdfnmpc_scene_distance", "sdfnmpc_solver_rollout_perceive",
     "sdfnmpc_scene_create_moving", "sdfnmpc_scene_is_dynamic", "sdfnmpc_scene_render_at", "sdfnmpc_scene_distance_at",
     "sdfnmpc_solver_rollout_perceive_at",
+    "sdfnmpc_morph", "sdfnmpc_outlier_rm", "sdfnmpc_sensor_apply", "sdfnmpc_solver_rollout_perceive_sensor",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -157,6 +158,16 @@ class PerceiveArgsC(C.Structure):
         (n, C.c_void_p) for n in ("images", "latent", "latent64", "W_p_Bo", "W_R_Bo", "W_p_C", "W_R_C")]
 
 
+class SensorOptsC(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("a", C.c_float), ("b", C.c_float), ("vmax", C.c_float),
+                ("p_thresh", C.c_uint32), ("miss_invalid", C.c_int), ("outlier_rm", C.c_int), ("min_range", C.c_float),
+                ("boxes", C.c_void_p), ("n_frames", C.c_int), ("max_boxes", C.c_int), ("stream_id", C.c_void_p)]
+
+
+MORPH_OPS = {"dilate": 0, "erode": 1}  # SDFNMPC_MORPH_*
+MORPH_TILE = 16  # output pixels per block edge of csrc/morph.hip (tests cross its seams)
+SENSOR_MAX_BOXES = 8
+
 _lib = None
 
 
@@ -245,11 +256,15 @@ def load():
         "sdfnmpc_scene_render_at": (i, [vp, vp, vp, P(ImgOptsC), i, i, f, i, vp, vp, d, vp]),
         "sdfnmpc_scene_distance_at": (i, [vp, vp, vp, vp, vp, ll, vp]),
         "sdfnmpc_solver_rollout_perceive_at": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d]),
+        "sdfnmpc_morph": (i, [vp, i, vp, i, i, i, vp, i, i, i, vp]),
+        "sdfnmpc_outlier_rm": (i, [vp, i, f, vp, i, i, i, vp]),
+        "sdfnmpc_sensor_apply": (i, [vp, P(SensorOptsC), i, vp, i, i, i, vp]),
+        "sdfnmpc_solver_rollout_perceive_sensor": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d, P(SensorOptsC), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 10:
+    if lib.sdfnmpc_abi_version() != 11:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -740,6 +755,26 @@ def scene_distance(ctx: "Context", scene_h, points, p_to_scene, n: int, out):
     _check(load().sdfnmpc_scene_distance(ctx.h, scene_h, _ptr(points), _ptr(p_to_scene), int(n), _ptr(out)))
 
 
+# ---- image morphology and the sensor stage (csrc/morph.hip, csrc/sensor.hip); the user-facing objects are
+# sdf_nmpc_amd.preprocessing.* and sdf_nmpc_amd.sensor.SensorModel ----
+def morph(ctx: "Context", op: int, kernel, ignore_zeros: bool, img, out):
+    """Enqueue sdfnmpc_morph: kernel a host uint8 array [k_h][k_w]; img / out device float32 [B][H][W]."""
+    k = np.ascontiguousarray(kernel, dtype=np.uint8)
+    _check(load().sdfnmpc_morph(ctx.h, int(op), k.ctypes.data, int(k.shape[0]), int(k.shape[1]), int(bool(ignore_zeros)),
+                                *_img_dims(img), _ptr(out)))
+
+
+def outlier_rm(ctx: "Context", kernel_size: int, min_range: float, img, out):
+    """Enqueue sdfnmpc_outlier_rm: img / out device float32 [B][H][W]; min_range in the image's units."""
+    _check(load().sdfnmpc_outlier_rm(ctx.h, int(kernel_size), float(min_range), *_img_dims(img), _ptr(out)))
+
+
+def sensor_apply(ctx: "Context", opts: SensorOptsC, frame: int, img, scratch=None):
+    """Enqueue sdfnmpc_sensor_apply in place on img, device float32 [B][H][W]; scratch: the same shape, needed with
+    opts.outlier_rm."""
+    _check(load().sdfnmpc_sensor_apply(ctx.h, C.byref(opts), int(frame), *_img_dims(img), _ptr(scratch)))
+
+
 # ---- the plant of a closed loop (csrc/plant.hip) ----
 class PlantOpts:
     """sdfnmpc_plant_opts with its per-instance mismatch arrays (host arrays are uploaded once per context, at
@@ -932,19 +967,26 @@ class Solver:
 
     def rollout(self, steps: int, plant: PlantOpts, x_log, u_log, status_log=None, iters_log=None, pts_log=None,
                 shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0,
-                perceive: "PerceiveArgsC" = None, scene_clock=None):
+                perceive: "PerceiveArgsC" = None, scene_clock=None, sensor=None):
         """Enqueue sdfnmpc_solver_rollout: `steps` closed-loop steps (references from x0 when ref is given,
         shift, RTI step, plant) from the x0 field, logged into the device arrays x_log [B][K+1][10], u_log
         [B][K][4], status_log / iters_log [B][K] int32 and pts_log [B][K+1][3] float32.  Asynchronous: `wait`
         finishes it (the arrays are kept alive until then).  perceive: a PerceiveArgsC -- a new image, latent and
         pose before every `every`-th step (sdfnmpc_solver_rollout_perceive); the caller keeps what it names alive.
         scene_clock: (t0, dt) -- the image before step k shows the scene at t0 + (phase + k) dt
-        (sdfnmpc_solver_rollout_perceive_at)."""
+        (sdfnmpc_solver_rollout_perceive_at).  sensor: (SensorOptsC, scratch [B][h][w] float32 or None) -- the
+        degradation of every new image before it is encoded (sdfnmpc_solver_rollout_perceive_sensor)."""
         a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
                          _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
                          _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
         self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log)
-        if perceive is None:
+        if sensor is not None:
+            self._rollout_keep += (perceive, sensor)
+            t0, dt = (0.0, 0.0) if scene_clock is None else scene_clock
+            _check(load().sdfnmpc_solver_rollout_perceive_sensor(
+                self.h, C.byref(a), None if perceive is None else C.byref(perceive), float(t0), float(dt),
+                C.byref(sensor[0]), _ptr(sensor[1])))
+        elif perceive is None:
             _check(load().sdfnmpc_solver_rollout(self.h, C.byref(a)))
         elif scene_clock is None:
             self._rollout_keep += (perceive,)

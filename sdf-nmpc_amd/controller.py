@@ -173,7 +173,7 @@ class Nmpc:
 
     def rollout(self, steps, refs=None, wps=None, vw=None, weights=None, plant=None, imgs=None, safe_ball_size=0.0,
                 outside='col', scene=None, vae=None, perceive_every=1, img_shape=None, keep_img=False,
-                perceive_phase=0, scene_t0=0.0, scene_dt=None):
+                perceive_phase=0, scene_t0=0.0, scene_dt=None, sensor=None):
         """``steps`` closed-loop control steps on the device, without a host round trip between them: per
         step the references from the current state (``refs``), the shift (mpc.shift), one SQP-RTI iteration
         and the plant advanced by u_0 -- the loop ``set_x0``; ``gen_refs_device``; ``solve``; simulate,
@@ -203,6 +203,11 @@ class Nmpc:
         ``scene_t0 + (perceive_phase + k) * scene_dt`` (``scene_dt``: default the plant's control period), the result
         carries ``t`` [K+1], that time for every log row, and ``clearance[b, j]`` is the distance of row j to the
         scene at ``t[j]``.  The controller treats every image as a static world.
+        sensor: a ``sensor.SensorModel`` on the controller's context (requires ``scene``) -- every new image is
+        degraded as frame ``perceive_phase + k`` before the encoder sees it (noise, lost pixels, erased boxes, outlier
+        removal; sdfnmpc_solver_rollout_perceive_sensor): the loop ``render_from_state``; ``sensor.apply(img, frame)``;
+        ``set_img``; ``encode_to``.  ``keep_img`` then returns the degraded image the encoder saw; ``clearance`` stays
+        the exact distance to the scene -- the clearance kept under a degraded camera.
 
         Returns a ``Rollout`` of numpy arrays, batch-leading also for one instance: x [B, K+1, 10] (row 0 the
         start), u [B, K, 4], status / iters [B, K]; with imgs also col [B, K+1] bool and pts [B, K+1, 3] float32.
@@ -224,6 +229,8 @@ class Nmpc:
         if scene is None:
             if vae is not None:
                 raise ValueError("rollout(): vae is the encoder of a scene's images; give scene too")
+            if sensor is not None:
+                raise ValueError("rollout(): sensor degrades a scene's images; give scene (and vae) too")
         else:  # every refusal before anything is uploaded or enqueued
             if vae is None:
                 raise ValueError("rollout(): scene needs vae (a VaeWrapper on the controller's context)")
@@ -241,6 +248,8 @@ class Nmpc:
             if scene_dt is not None and not (np.isfinite(float(scene_dt)) and float(scene_dt) >= 0.0):
                 raise ValueError(f"scene_dt {scene_dt}: finite and not negative")
             scene._batch(Bn)
+            if sensor is not None and sensor.ctx is not ctx:
+                raise ValueError("rollout(): the SensorModel must be built on the controller's context (ctx=nmpc.ocp.ctx)")
         kw = {}
         if refs is not None:
             code = {"wps": 0, "joystick": 1, "hover": 2}[refs]
@@ -274,6 +283,8 @@ class Nmpc:
                                       vae.latent64.data_ptr(), *[ws[k].data_ptr() for k in ("W_p_Bo", "W_R_Bo", "W_p_C",
                                                                                             "W_R_C")])
             kw["perceive"] = perc
+            if sensor is not None:  # in the units of the raw image the renderer writes for the encoder
+                kw["sensor"] = sensor.opts(Bn, ih, iw, normalized=False)
             t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)
             if scene.is_dynamic:  # a static scene has no use for the clock: the call the method has always made
                 kw["scene_clock"] = (t0, dts)

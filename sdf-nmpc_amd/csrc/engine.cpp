@@ -27,6 +27,7 @@
 #include "df_kernels.h"
 #include "plant_kernels.h"
 #include "scene_kernels.h"
+#include "sensor_kernels.h"
 
 using namespace sdfn;
 
@@ -89,6 +90,7 @@ struct sdfnmpc_ctx {
     bool timing = false;
     DevBuf c13, sdf4, lat, out4, glat, qpw, qpst, wws;
     DevBuf dfpool;  // sdfnmpc_udf: the 5x5 min-pooled images
+    DevBuf morph_t, morph_e;  // sdfnmpc_outlier_rm with kernel_size != 3: the thresholded image and its erosion
     // host-pointer path (sdf_eval_host, the CasADi external): pinned staging, its own hoist buffer and
     // the latents it was computed for (consecutive acados calls share one latent: the hoist is reused)
     float* h_pin = nullptr;
@@ -2386,4 +2388,133 @@ extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* 
     }
     HIPCHK(timed(ctx, "scene_dist", [&] { return launch_scene_distance(a, ctx->stream); }));
     return SDFNMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// image morphology (morph.hip) and the sensor-degradation stage (sensor.hip)
+static int image_batch_check(const char* who, int B, int H, int W) {
+    const std::string w(who);
+    if (B < 0 || B > 65535) return fail(SDFNMPC_E_ARG, w + ": B must be 0..65535");
+    if (H < 1 || W < 1) return fail(SDFNMPC_E_ARG, w + ": bad image size");
+    if ((long long)H * W > 2147483647LL || (long long)B * H * W > 2147483647LL)
+        return fail(SDFNMPC_E_ARG, w + ": more than 2^31 - 1 pixels");
+    return SDFNMPC_OK;
+}
+
+static int morph_args(int op, const unsigned char* kernel, int k_h, int k_w, int ignore_zeros, const float* in, int B,
+                      int H, int W, float* out, MorphArgs* a) {
+    if (op != MORPH_DILATE && op != MORPH_ERODE) return fail(SDFNMPC_E_ARG, "morph: op must be 0 (dilate) or 1 (erode)");
+    if (!kernel) return fail(SDFNMPC_E_ARG, "morph: NULL structuring element");
+    if (k_h < 1 || k_h > MORPH_K_MAX || k_w < 1 || k_w > MORPH_K_MAX)
+        return fail(SDFNMPC_E_ARG, "morph: the structuring element must be 1..21 x 1..21");
+    if (int rc = image_batch_check("morph", B, H, W)) return rc;
+    if (B > 0 && (!in || !out)) return fail(SDFNMPC_E_ARG, "morph: NULL image");
+    if (B > 0 && in == out) return fail(SDFNMPC_E_ARG, "morph: in and out must differ");
+    a->in = in; a->out = out; a->B = B; a->H = H; a->W = W;
+    a->k_h = k_h; a->k_w = k_w; a->oh = k_h / 2; a->ow = k_w / 2;
+    a->op = op; a->ignore_zeros = ignore_zeros != 0;
+    a->border = op == MORPH_DILATE ? -2.f : 2.f;
+    if (morph_build_taps(op, kernel, k_h, k_w, &a->taps) < 1)
+        return fail(SDFNMPC_E_ARG, "morph: the structuring element has no 1");
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_morph(sdfnmpc_ctx* ctx, int op, const unsigned char* kernel, int k_h, int k_w, int ignore_zeros,
+                             const float* in, int B, int H, int W, float* out) {
+    if (!ctx) return fail(SDFNMPC_E_ARG, "morph: NULL context");
+    MorphArgs a{};
+    if (int rc = morph_args(op, kernel, k_h, k_w, ignore_zeros, in, B, H, W, out, &a)) return rc;
+    if (B == 0) return SDFNMPC_OK;
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "morph", [&] { return launch_morph(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+// the fused launch's option check, split from the launch as the scene kernels' are (the rollout repeats the launch)
+static int outlier_args(float min_range, const float* in, int B, int H, int W, float* out, OutlierArgs* a) {
+    if (int rc = image_batch_check("outlier_rm", B, H, W)) return rc;
+    if (!std::isfinite(min_range)) return fail(SDFNMPC_E_ARG, "outlier_rm: min_range must be finite");
+    if (B > 0 && (!in || !out)) return fail(SDFNMPC_E_ARG, "outlier_rm: NULL image");
+    if (B > 0 && in == out) return fail(SDFNMPC_E_ARG, "outlier_rm: in and out must differ");
+    *a = OutlierArgs{in, out, B, H, W, min_range};
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_outlier_rm(sdfnmpc_ctx* ctx, int kernel_size, float min_range, const float* in, int B, int H,
+                                  int W, float* out) {
+    if (!ctx) return fail(SDFNMPC_E_ARG, "outlier_rm: NULL context");
+    if (kernel_size < 1 || kernel_size > MORPH_K_MAX) return fail(SDFNMPC_E_ARG, "outlier_rm: kernel_size must be 1..21");
+    OutlierArgs oa{};
+    if (int rc = outlier_args(min_range, in, B, H, W, out, &oa)) return rc;
+    if (B == 0) return SDFNMPC_OK;
+    ScopedDevice sd(ctx->device);
+    if (kernel_size == 3) {
+        HIPCHK(timed(ctx, "outlier_rm", [&] { return launch_outlier_rm(oa, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
+    // threshold -> t; erode t -> e; dilate e -> out; out = out > 0 ? t : out
+    const long long n = (long long)B * H * W;
+    HIPCHK(ctx->morph_t.ensure((size_t)n * sizeof(float)));
+    HIPCHK(ctx->morph_e.ensure((size_t)n * sizeof(float)));
+    float *t = (float*)ctx->morph_t.p, *e = (float*)ctx->morph_e.p;
+    unsigned char ones[MORPH_K_MAX * MORPH_K_MAX];
+    memset(ones, 1, sizeof(ones));
+    MorphArgs er{}, di{};
+    if (int rc = morph_args(MORPH_ERODE, ones, kernel_size, kernel_size, 0, t, B, H, W, e, &er)) return rc;
+    if (int rc = morph_args(MORPH_DILATE, ones, kernel_size, kernel_size, 0, e, B, H, W, out, &di)) return rc;
+    HIPCHK(timed(ctx, "morph_threshold", [&] { return launch_morph_threshold(in, t, n, min_range, ctx->stream); }));
+    HIPCHK(timed(ctx, "morph", [&] { return launch_morph(er, ctx->stream); }));
+    HIPCHK(timed(ctx, "morph", [&] { return launch_morph(di, ctx->stream); }));
+    HIPCHK(timed(ctx, "morph_restore", [&] { return launch_morph_restore(out, t, n, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+// sdfnmpc_sensor_apply in two halves (solver.hip repeats the second inside a rollout): _args_ refuses or fills the two
+// kernels' argument blocks, _launch_ enqueues them for a frame
+extern "C" int sdfnmpc_sensor_args_(const sdfnmpc_sensor_opts* o, float* img, int B, int H, int W, float* scratch,
+                                    SensorArgs* sa, OutlierArgs* oa) {
+    if (!o || !sa || !oa) return fail(SDFNMPC_E_ARG, "sensor: NULL options");
+    if (int rc = image_batch_check("sensor", B, H, W)) return rc;
+    if (!(std::isfinite(o->a) && o->a >= 0.f && std::isfinite(o->b) && o->b >= 0.f))
+        return fail(SDFNMPC_E_ARG, "sensor: a and b must be finite and not negative");
+    if (!(o->vmax > 0.f && std::isfinite(o->vmax))) return fail(SDFNMPC_E_ARG, "sensor: vmax must be positive and finite");
+    if (o->boxes && (o->n_frames < 1 || o->max_boxes < 0 || o->max_boxes > SENSOR_MAX_BOXES))
+        return fail(SDFNMPC_E_ARG, "sensor: a box table needs n_frames >= 1 and max_boxes in 0..8");
+    if (B > 0 && !img) return fail(SDFNMPC_E_ARG, "sensor: NULL image");
+    if (o->outlier_rm) {
+        if (B > 0 && !scratch) return fail(SDFNMPC_E_ARG, "sensor: outlier_rm needs the scratch image");
+        if (int rc = outlier_args(o->min_range, img, B, H, W, scratch, oa)) return rc;
+    }
+    SensorArgs a{};
+    a.img = img; a.B = B; a.H = H; a.W = W;
+    a.key0 = (unsigned)(o->seed & 0xffffffffull); a.key1 = (unsigned)(o->seed >> 32);
+    a.a = o->a; a.b = o->b; a.vmax = o->vmax; a.p_thresh = o->p_thresh; a.miss_invalid = o->miss_invalid != 0;
+    a.boxes = (o->boxes && o->max_boxes > 0) ? o->boxes : nullptr;
+    a.n_frames = o->n_frames; a.max_boxes = o->max_boxes; a.stream_id = o->stream_id;
+    *sa = a;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_sensor_launch_(sdfnmpc_ctx* ctx, const SensorArgs* sa, const OutlierArgs* oa, int outlier_rm,
+                                      int frame) {
+    if (sa->B == 0) return SDFNMPC_OK;
+    SensorArgs a = *sa;
+    a.frame = (unsigned)frame;
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "sensor_degrade", [&] { return launch_sensor_degrade(a, ctx->stream); }));
+    if (outlier_rm) {
+        HIPCHK(timed(ctx, "outlier_rm", [&] { return launch_outlier_rm(*oa, ctx->stream); }));
+        HIPCHK(hipMemcpyAsync(a.img, oa->out, (size_t)a.B * a.H * a.W * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_sensor_apply(sdfnmpc_ctx* ctx, const sdfnmpc_sensor_opts* o, int frame, float* img, int B, int H,
+                                    int W, float* scratch) {
+    if (!ctx) return fail(SDFNMPC_E_ARG, "sensor: NULL context");
+    SensorArgs sa{};
+    OutlierArgs oa{};
+    if (int rc = sdfnmpc_sensor_args_(o, img, B, H, W, scratch, &sa, &oa)) return rc;
+    if (frame < 0) return fail(SDFNMPC_E_ARG, "sensor: frame must be >= 0");
+    return sdfnmpc_sensor_launch_(ctx, &sa, &oa, o->outlier_rm != 0, frame);
 }

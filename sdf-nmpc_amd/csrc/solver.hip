@@ -18,6 +18,7 @@
 #include "plant_kernels.h"
 #include "ref_kernels.h"
 #include "scene_kernels.h"
+#include "sensor_kernels.h"
 
 extern "C" int sdfnmpc_solver_fail_(int code, const char* msg);  // engine.cpp: sets sdfnmpc_last_error
 // engine.cpp: the plant's option check + argument block, and its launch on the context stream (timed as "plant")
@@ -36,6 +37,11 @@ extern "C" int sdfnmpc_scene_pose_args_(const double* B_p_C, const double* B_R_C
                                         sdfn::ScenePoseArgs* out);
 extern "C" int sdfnmpc_scene_pose_launch_(sdfnmpc_ctx* ctx, const sdfn::ScenePoseArgs* a);
 extern "C" int sdfnmpc_vae_on_ctx_(const sdfnmpc_vae* v, const sdfnmpc_ctx* ctx);
+// engine.cpp: the same split for the sensor stage of a perceiving rollout (degradation, then the fused outlier removal)
+extern "C" int sdfnmpc_sensor_args_(const sdfnmpc_sensor_opts* o, float* img, int B, int H, int W, float* scratch,
+                                    sdfn::SensorArgs* sa, sdfn::OutlierArgs* oa);
+extern "C" int sdfnmpc_sensor_launch_(sdfnmpc_ctx* ctx, const sdfn::SensorArgs* sa, const sdfn::OutlierArgs* oa,
+                                      int outlier_rm, int frame);
 extern "C" int sdfnmpc_scene_on_ctx_(const sdfnmpc_scene* sc, const sdfnmpc_ctx* ctx);
 
 namespace {
@@ -393,7 +399,14 @@ extern "C" int sdfnmpc_solver_rollout_perceive(sdfnmpc_solver* s, const sdfnmpc_
 
 extern "C" int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
                                                   const sdfnmpc_perceive_args* pc, double t0, double dt) {
+    return sdfnmpc_solver_rollout_perceive_sensor(s, a, pc, t0, dt, nullptr, nullptr);
+}
+
+extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
+                                                      const sdfnmpc_perceive_args* pc, double t0, double dt,
+                                                      const sdfnmpc_sensor_opts* sensor, float* scratch) {
     if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout");
+    if (sensor && !pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: a sensor model needs perception (perc)");
     if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
     if (a->steps < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
@@ -420,6 +433,8 @@ extern "C" int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnm
     sdfnmpc_vae_opts vo{};
     sdfnmpc_ref_opts lo{};
     sdfnmpc_ref_args lra{};
+    sdfn::SensorArgs sna{};
+    sdfn::OutlierArgs ora{};
     if (pc) {
         if (pc->every < 1 || pc->phase < 0)
             return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
@@ -445,6 +460,11 @@ extern "C" int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnm
         for (int i = 0; i < 9; ++i) lo.B_R_C[i] = pc->B_R_C[i];
         lra.B = s->B; lra.N = s->N; lra.np = s->np; lra.ny = s->ny; lra.L = L; lra.nyN = s->nyN;
         lra.latent = pc->latent64; lra.W_p_Bo = pc->W_p_Bo; lra.W_R_Bo = pc->W_R_Bo; lra.p = s->p;
+        if (sensor) {
+            if ((long long)pc->phase + a->steps > 2147483647LL)
+                return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the sensor's frame counter (phase + steps) overflows");
+            if (int rc = sdfnmpc_sensor_args_(sensor, pc->images, s->B, pc->h, pc->w, scratch, &sna, &ora)) return rc;
+        }
     }
     pa.K = a->steps;
     pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
@@ -460,6 +480,8 @@ extern "C" int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnm
             volatile double steps_dt = (double)(pc->phase + k) * dt;
             const double t = t0 + steps_dt;
             if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pc->scene, &sra, t)) return rc;
+            if (sensor)  // what the camera makes of the exact image: frame = phase + k, as a chunked or host loop counts
+                if (int rc = sdfnmpc_sensor_launch_(s->ctx, &sna, &ora, sensor->outlier_rm != 0, pc->phase + k)) return rc;
             if (int rc = sdfnmpc_vae_encode(s->ctx, pc->vae, &vo, pc->images, pc->latent, pc->latent64)) return rc;
             if (int rc = sdfnmpc_pack_refs(s->ctx, &lo, &lra)) return rc;
         }

@@ -6,12 +6,17 @@ the loops compute the same bits (checked) and the difference is the host's.  Als
 (HIP events): scene_render at 270 x 480 with 16 primitives next to its floors, scene_pose, scene_dist -- and the
 dynamic kernels on the same scene with every primitive moving, from the same run.  --moving gives the loops' scene
 those motions (the host-driven loop renders at t = k * dt, the device loop runs the scene's clock);
---kernels-only skips the loops.
+--kernels-only skips the loops.  --sensor runs the loops under the reference's training augmentation as a sensor model
+(SensorModel.reference_augment with the outlier removal behind it): the device loop against the host-driven loop that
+calls SensorModel.apply between the render and the encoder (same bits, checked), the distribution of the minimum
+clearance over the batch with and without the sensor model, and per launch the sensor stage's kernels next to
+scene_render and the encoder's from one timed rollout, plus the general morphology kernel with the radius-10 disc.
 
 One configuration per run (give every run its own time limit):
     timeout 600 python tools/perceive_probe.py --B 1024 --N 40 --every 1
     timeout 600 python tools/perceive_probe.py --B 1024 --N 40 --every 5
     timeout 200 python tools/perceive_probe.py --B 1 --N 40 --every 1
+    timeout 600 python tools/perceive_probe.py --B 256 --N 40 --every 1 --sensor
 Prints ms per control step of both loops (best of --reps repetitions after a warm-up) and a JSON line.  Diagnostic."""
 import argparse
 import json
@@ -27,6 +32,7 @@ sys.path.insert(0, ROOT)
 from sdf_nmpc_amd import _lib
 from sdf_nmpc_amd.config import Config
 from sdf_nmpc_amd.scene import Scene
+from sdf_nmpc_amd.sensor import SensorModel
 from sdf_nmpc_amd.vae import VaeWrapper
 from rollout_probe import controller
 
@@ -62,7 +68,7 @@ def moving_forest(n_prims, seed=3):
     return out
 
 
-def host_loop(n, vae, scene, x0, wps, K, every, plant):
+def host_loop(n, vae, scene, x0, wps, K, every, plant, sensor=None):
     B, ctx = max(n.B, 1), n.ocp.ctx
     dx = _lib.DeviceArray(ctx, (B, 10))
     x, xs = np.reshape(x0, (B, 10)).copy(), []
@@ -71,6 +77,8 @@ def host_loop(n, vae, scene, x0, wps, K, every, plant):
         n.set_x0(sq(x))
         if k % every == 0:
             img = scene.render_from_state(x, n.cfg, normalized=False, t=0.0 + k * plant.dt)
+            if sensor is not None:
+                sensor.apply(img, frame=k, normalized=False)
             vae.set_img(img)
             vae.encode_to(n, img.pose["W_p_Bo"], img.pose["W_R_Bo"])
         n.gen_refs_device("wps", wps=wps)
@@ -126,6 +134,67 @@ def kernel_times(ctx, cfg, B, res):
     res["render_hit_share"] = float((out.numpy() < 1.0).mean())
 
 
+def sensor_probe(cfg, a, res):
+    """The loops under a degraded camera, the clearance it costs, and the sensor stage's own time."""
+    from sdf_nmpc_amd import preprocessing
+    make = lambda ctx: SensorModel.reference_augment(cfg, ctx, 2024, outlier_rm=True, miss_invalid=True)
+    runs = {}
+    for name in ("sensor", "clean", "host"):
+        n, x0, wps = controller(cfg, a.B, 1)
+        ctx = n.ocp.ctx
+        scene, vae = Scene(ctx, forest(16)), VaeWrapper(cfg, batch=a.B, ctx=ctx)
+        plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]))
+        if name == "host":
+            runs[name] = host_loop(n, vae, scene, x0, wps, a.K, a.every, plant, sensor=make(ctx))
+        else:
+            n.set_x0(x0)
+            if name == "sensor":
+                ctx.enable_timing(True)
+                ctx.reset_stats()
+            runs[name] = n.rollout(a.K, refs="wps", wps=wps, plant=plant, scene=scene, vae=vae, perceive_every=a.every,
+                                   sensor=make(ctx) if name == "sensor" else None)
+            if name == "sensor":
+                for k in ("scene_render", "sensor_degrade", "outlier_rm", "vae_pre", "vae_stem", "vae_conv", "vae_head"):
+                    ms, cnt = ctx.kernel_stats(k)
+                    res[f"{k}_us"], res[f"{k}_launches"] = ms / max(cnt, 1) * 1e3, cnt
+                ctx.enable_timing(False)
+                per = max(res["scene_render_launches"], 1)
+                res["sensor_stage_us_per_perception"] = (res["sensor_degrade_us"] * res["sensor_degrade_launches"] +
+                                                         res["outlier_rm_us"] * res["outlier_rm_launches"]) / per
+                res["vae_encode_us_per_perception"] = sum(res[f"{k}_us"] * res[f"{k}_launches"] for k in
+                                                          ("vae_pre", "vae_stem", "vae_conv", "vae_head")) / per
+                # the general kernel with the reference's disc of radius 10 on the batch's images (Erode, ignore_zeros)
+                h, w = (int(v) for v in cfg.sensor.shape_imgs[-2:])
+                img = _lib.DeviceArray.from_numpy(ctx, np.random.default_rng(0).uniform(0, 1, (max(n.B, 1), h, w)).astype(np.float32))
+                r = np.arange(-10, 11)
+                er = preprocessing.Erode((r[:, None] ** 2 + r[None] ** 2 <= 100), True, ctx=ctx)
+                er(img)
+                ctx.reset_stats()
+                ctx.enable_timing(True)
+                for _ in range(5):
+                    er(img)
+                ms, cnt = ctx.kernel_stats("morph")
+                ctx.enable_timing(False)
+                res["morph_disc10_us"] = ms / cnt * 1e3
+        vae.vae.close()
+        n.ocp.close()
+    res["same_bits"] = bool(np.array_equal(runs["sensor"].x[:, 1:], runs["host"]))
+    q = (0, 5, 25, 50, 75, 95, 100)
+    for name in ("sensor", "clean"):
+        mc = runs[name].clearance.min(axis=1)
+        res[f"min_clearance_{name}_percentiles"] = dict(zip(map(str, q), np.percentile(mc, q).round(4).tolist()))
+        res[f"collided_{name}"] = int((mc < 0).sum())
+    print(f"B={a.B} N={a.N} K={a.K} every={a.every} under reference_augment + outlier removal: device loop == host loop: "
+          f"{res['same_bits']}; per perceiving step scene_render {res['scene_render_us']:.1f} us, sensor stage "
+          f"{res['sensor_stage_us_per_perception']:.1f} us (sensor_degrade {res['sensor_degrade_us']:.1f} + outlier_rm "
+          f"{res['outlier_rm_us']:.1f} + a copy), encoder {res['vae_encode_us_per_perception']:.1f} us; Erode with the "
+          f"radius-10 disc {res['morph_disc10_us']:.1f} us")
+    print("min clearance over the batch, percentiles", q)
+    for name in ("clean", "sensor"):
+        print(f"  {name:6s}", list(res[f"min_clearance_{name}_percentiles"].values()), "collided:", res[f"collided_{name}"])
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=1024)
@@ -135,10 +204,14 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--moving", action="store_true", help="the loops' scene moves (moving_forest)")
     ap.add_argument("--kernels-only", action="store_true", help="only the scene kernels' own times")
+    ap.add_argument("--sensor", action="store_true", help="the loops under SensorModel.reference_augment")
     a = ap.parse_args()
     warnings.simplefilter("ignore")
     cfg = Config(mpc__N=a.N)
     res = {"B": a.B, "N": a.N, "K": a.K, "every": a.every, "moving": a.moving}
+    if a.sensor:
+        sensor_probe(cfg, a, res)
+        return
     if a.kernels_only:
         ctx = _lib.Context(0)
         kernel_times(ctx, cfg, a.B, res)
