@@ -55,6 +55,10 @@
  *   sdfnmpc_solver_rollout_perceive    sdfnmpc_solver_rollout with the perception a user wraps around it every
  *                                      control period: VaeWrapper.set_img / encode (sdf_nmpc/vae.py:29-40) of a new
  *                                      image and Nmpc.set_latent (controller.py:50-54) with the pose at image time
+ *   sdfnmpc_scene_sdf_rows             (no reference interface: the reference's SDF is always the network) what the
+ *                                      network's epilogue writes as the sdf row of h / J_h (gen_model.py:46-61),
+ *                                      from the scene's exact distance; sdfnmpc_lin_args.sdf_scene, sdfnmpc_solver_
+ *                                      set_sdf_scene and sdfnmpc_solver_rollout_scene_sdf carry it through the step
  *   sdfnmpc_morph / sdfnmpc_outlier_rm Dilate / Erode (and with them Open / Close) and RemoveCloseOutliers
  *                                      (utils/preprocessing.py:100-259), batched
  *   sdfnmpc_sensor_apply               ImageAugmenter's noise and erasing (utils/data.py:11-108) as a reproducible
@@ -73,7 +77,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 11
+#define SDFNMPC_ABI_VERSION 12
 
 enum {
     SDFNMPC_OK = 0,
@@ -86,6 +90,17 @@ enum {
 
 typedef struct sdfnmpc_ctx sdfnmpc_ctx;
 typedef struct sdfnmpc_net sdfnmpc_net;
+typedef struct sdfnmpc_scene sdfnmpc_scene;
+
+/* An analytic scene as the source of the SDF row (csrc/scene_sdf.hip, sdfnmpc_scene_sdf_rows below): the scene
+ * set, the scene of each instance, the truncation distance and the scene's time at the nodes. */
+typedef struct {
+    const sdfnmpc_scene* scene;  /* on the caller's context */
+    const int* scene_of;         /* device [B] or NULL (scene 0); entries clamped into [0, S) as by every scene kernel */
+    double max_df;               /* > 0, finite: distances are truncated there (df_train.py:50) */
+    double t0;                   /* finite: the scene's time at node 0 */
+    const double* tau;           /* device [N+1] or NULL: node k sees the scene at t0 + tau[k]; NULL: every node at t0 */
+} sdfnmpc_scene_sdf_opts;
 
 #define SDFNMPC_POLY_DEG_MAX 6 /* braking-distance polynomial: degree bound ... */
 #define SDFNMPC_POLY_MAX 84    /* ... and its coefficient count (deg + 3 choose 3) */
@@ -150,6 +165,11 @@ typedef struct {
                          camera-frame point at the braking distance ahead (gen_model.py:98-112); the
                          rec_feas constraint value is h[N][2] + hE[0] (gen_model.py:94-95) */
     double* JhE;      /* [B][10][6]      column-major d hE / d x_N */
+    const sdfnmpc_scene_sdf_opts* sdf_scene; /* NULL: the network.  Else the SDF row h[.][2] / J_h[.][.][2] is the
+                         exact distance of this scene (sdfnmpc_scene_sdf_rows on x, p, h, Jh): net may be NULL and no
+                         network is evaluated; linearize, then the rows kernel, then the record pack, on the context
+                         stream.  Refused together with no_sdf (SDFNMPC_E_ARG), and by sdfnmpc_step_create
+                         (SDFNMPC_E_UNSUPPORTED) */
 } sdfnmpc_lin_args;
 
 /* QP model data and solver options (defaults in sdf-nmpc_amd/model.py / ocp.py) */
@@ -216,7 +236,9 @@ typedef struct {
  * formate_ref (quad_rollpitchyawrate.py:62-65) -> Nmpc.set_ref / set_latent / set_sdf_flag
  * (controller.py:45-54,133-142) for B instances x (N+1) nodes on the device. */
 typedef struct {
-    int mode;              /* 0 gen_ref_list_wps, 1 gen_ref_joystick, 2 from_x0, -1 latent / flag only */
+    int mode;              /* 0 gen_ref_list_wps, 1 gen_ref_joystick, 2 from_x0, -1 latent / flag only, -2 pose only:
+                              p[:, :, 1:13] of every node from W_p_Bo / W_R_Bo (required) and the extrinsics, the
+                              bits mode -1 writes there; flag and latent columns untouched (latent / flag ignored) */
     int yaw_mode;          /* path samples: 0 identity, 1 'ref', 2 'align', 3 x0 quaternion ('curent', sic) */
     int st_enable;         /* ref.stop_and_turn.enable */
     int st_mode;           /* stop-and-turn yaw: 0 current, 1 'topic', 2 'align' */
@@ -561,7 +583,6 @@ typedef struct {
     int kind;
     double a[6];
 } sdfnmpc_prim;
-typedef struct sdfnmpc_scene sdfnmpc_scene;
 int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims, sdfnmpc_scene** out);
 void sdfnmpc_scene_free(sdfnmpc_scene* scene);
 
@@ -672,6 +693,49 @@ int sdfnmpc_solver_rollout_perceive(sdfnmpc_solver* s, const sdfnmpc_rollout_arg
  * dt < 0. */
 int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
                                        const sdfnmpc_perceive_args* perc, double t0, double dt);
+
+/* ---- the scene's exact distance as the controller's SDF (csrc/scene_sdf.hip) ----
+ * sdfnmpc_scene_sdf_rows writes what the network kernels' epilogue writes (gen_model.py:46-61), from the closed forms of
+ * sdfnmpc_scene_distance(_at): for node row r = b (N+1) + k with the world position x[r][0..2], the instance's scene
+ * and the time t0 + tau[k],
+ *   h[r][2] = flag df + (1 - flag) max_df,   Jh[r][j][2] = flag grad_j (j < 3), 0 (j = 3..9),   flag = p[r][0]
+ * where df = d and grad = the world gradient of d where the signed distance d < max_df, else (and for a scene without
+ * primitives) df = max_df and grad = 0.  The gradient is that of the primitive attaining the minimum (the lowest index
+ * on a tie), taken in the primitive's frame and rotated by R(t): sphere q / |q|; box and capped cylinder the normalised
+ * positive excesses outside and the axis of the largest excess inside.  At a kink it is one of the one-sided values,
+ * finite and of norm <= 1.  Columns 0 and 1 of h and Jh are not touched.  A set that is not dynamic takes the static
+ * kernel whatever the time.  fp64, no atomics: a row does not depend on its place in the batch.  "scene_sdf_rows" in
+ * sdfnmpc_ctx_kernel_stats.  x [B][N+1][10], p [B][N+1][np], h [B][N+1][3], Jh [B][N+1][10][3] device float64.
+ * Asynchronous on the context stream; B == 0 is a no-op.  SDFNMPC_E_ARG (nothing is launched, outputs untouched): NULL
+ * arguments, B < 0, N < 1, np < 17, max_df not > 0 or not finite, a non-finite t0, a scene on another context. */
+int sdfnmpc_scene_sdf_rows(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* opts, int B, int N, int np, const double* x,
+                           const double* p, double* h, double* Jh);
+
+/* The solver's SDF source.  scene != NULL: every later step evaluates the scene's exact distance instead of the
+ * network (sdfnmpc_lin_args.sdf_scene), truncated at max_df, for scene_of [B] (device, NULL: scene 0; the caller's to
+ * keep alive), at the solver's scene time; with predict node k sees the scene at that time + tau[k], tau[0] = 0,
+ * tau[k] = tau[k-1] + dt[k-1] of the solver's own grid.  scene == NULL returns to the network.  The solver keeps the
+ * two pointers, not copies: the scene, like scene_of, must stay alive while it is the source -- call this with NULL
+ * before sdfnmpc_scene_free (sdf_nmpc_amd.scene.Scene.close does).  SDFNMPC_E_ARG: no row
+ * or cost of the solver's constraint set reads the SDF, a scene on another context, max_df not > 0 or not finite. */
+int sdfnmpc_solver_set_sdf_scene(sdfnmpc_solver* s, const sdfnmpc_scene* scene, const int* scene_of, double max_df,
+                                 int predict);
+/* The scene time the next steps pass as sdfnmpc_scene_sdf_opts.t0 (0 at creation).  SDFNMPC_E_ARG: a non-finite t. */
+int sdfnmpc_solver_set_scene_time(sdfnmpc_solver* s, double t);
+
+/* sdfnmpc_solver_rollout for a solver with a scene source.  Before step k the solver's scene time is set to
+ * t0 + (double)(phase + k) * dt (the product rounded on its own, as sdfnmpc_solver_rollout_perceive_at forms it), and
+ * with pose != NULL and (k + phase) % pose->every == 0 the camera pose the field-of-view rows read is refreshed:
+ * sdfnmpc_scene_pose from the solver's x0 field into the caller's workspaces, then sdfnmpc_pack_refs in mode -2.  A
+ * plain launch sequence.  SDFNMPC_E_ARG, all before the first launch: what sdfnmpc_solver_rollout refuses, no source
+ * set on the solver, every < 1, phase < 0, a missing workspace, a non-finite t0 or dt, dt < 0. */
+typedef struct {
+    int every;                     /* >= 1 */
+    double B_p_C[3], B_R_C[9];     /* sensor extrinsics */
+    double *W_p_Bo, *W_R_Bo, *W_p_C, *W_R_C; /* device workspaces [B][3], [B][9], [B][3], [B][9] */
+} sdfnmpc_pose_refresh_args;
+int sdfnmpc_solver_rollout_scene_sdf(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
+                                     const sdfnmpc_pose_refresh_args* pose, int phase, double t0, double dt);
 
 /* ---- image morphology (csrc/morph.hip) ----
  * The reference's Dilate / Erode (utils/preprocessing.py:100-199) on images in / out [B][H][W] (device float32, in !=

@@ -41,6 +41,8 @@ SYMBOLS = [
     "sdfnmpc_scene_create_moving", "sdfnmpc_scene_is_dynamic", "sdfnmpc_scene_render_at", "sdfnmpc_scene_distance_at",
     "sdfnmpc_solver_rollout_perceive_at",
     "sdfnmpc_morph", "sdfnmpc_outlier_rm", "sdfnmpc_sensor_apply", "sdfnmpc_solver_rollout_perceive_sensor",
+    "sdfnmpc_scene_sdf_rows", "sdfnmpc_solver_set_sdf_scene", "sdfnmpc_solver_set_scene_time",
+    "sdfnmpc_solver_rollout_scene_sdf",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -71,10 +73,15 @@ TAU_ROLL = TAU_PITCH = 0.12  # quad_rollpitchyawrate_tau.py:19-20
 LIN_PTRS = ("x", "u", "p", "dt", "xn", "AB", "y", "Jy", "yN", "JyN", "h", "Jh", "sdf")
 
 
+class SceneSdfOptsC(C.Structure):
+    _fields_ = [("scene", C.c_void_p), ("scene_of", C.c_void_p), ("max_df", C.c_double), ("t0", C.c_double),
+                ("tau", C.c_void_p)]
+
+
 class LinArgsC(C.Structure):
     _fields_ = [("B", C.c_int), ("N", C.c_int), ("np", C.c_int), ("latent_mode", C.c_int)] + [
         (n, C.c_void_p) for n in LIN_PTRS] + [("nyN", C.c_int), ("no_sdf", C.c_int), ("hE", C.c_void_p),
-                                             ("JhE", C.c_void_p)]
+                                             ("JhE", C.c_void_p), ("sdf_scene", C.POINTER(SceneSdfOptsC))]
 
 
 class QpOptsC(C.Structure):
@@ -156,6 +163,11 @@ class PerceiveArgsC(C.Structure):
                 ("scale", C.c_float), ("B_p_C", C.c_double * 3), ("B_R_C", C.c_double * 9), ("vae", C.c_void_p),
                 ("vae_opts", VaeOptsC), ("every", C.c_int), ("phase", C.c_int)] + [
         (n, C.c_void_p) for n in ("images", "latent", "latent64", "W_p_Bo", "W_R_Bo", "W_p_C", "W_R_C")]
+
+
+class PoseRefreshArgsC(C.Structure):
+    _fields_ = [("every", C.c_int), ("B_p_C", C.c_double * 3), ("B_R_C", C.c_double * 9)] + [
+        (n, C.c_void_p) for n in ("W_p_Bo", "W_R_Bo", "W_p_C", "W_R_C")]
 
 
 class SensorOptsC(C.Structure):
@@ -260,11 +272,15 @@ def load():
         "sdfnmpc_outlier_rm": (i, [vp, i, f, vp, i, i, i, vp]),
         "sdfnmpc_sensor_apply": (i, [vp, P(SensorOptsC), i, vp, i, i, i, vp]),
         "sdfnmpc_solver_rollout_perceive_sensor": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d, P(SensorOptsC), vp]),
+        "sdfnmpc_scene_sdf_rows": (i, [vp, P(SceneSdfOptsC), i, i, i, vp, vp, vp, vp]),
+        "sdfnmpc_solver_set_sdf_scene": (i, [vp, vp, vp, d, i]),
+        "sdfnmpc_solver_set_scene_time": (i, [vp, d]),
+        "sdfnmpc_solver_rollout_scene_sdf": (i, [vp, P(RolloutArgsC), P(PoseRefreshArgsC), i, d, d]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 11:
+    if lib.sdfnmpc_abi_version() != 12:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -484,16 +500,28 @@ def quad_model(cfg, model=None) -> QuadModelC:
     return m
 
 
-def lin_args(B: int, N: int, np_: int, bufs: dict, latent_mode=0, nyN=4, no_sdf=False) -> LinArgsC:
-    return LinArgsC(B, N, np_, latent_mode, *[_ptr(bufs.get(k)) for k in LIN_PTRS], int(nyN), int(bool(no_sdf)),
-                    _ptr(bufs.get("hE")), _ptr(bufs.get("JhE")))
+def scene_sdf_opts(scene_h, max_df: float, scene_of=None, t0: float = 0.0, tau=None) -> SceneSdfOptsC:
+    """sdfnmpc_scene_sdf_opts: a scene handle as the source of the SDF row; scene_of [B] int32 / tau [N+1] float64
+    device arrays or None.  The caller keeps what it names alive."""
+    return SceneSdfOptsC(scene_h.value if isinstance(scene_h, C.c_void_p) else scene_h, _ptr(scene_of), float(max_df),
+                         float(t0), _ptr(tau))
+
+
+def lin_args(B: int, N: int, np_: int, bufs: dict, latent_mode=0, nyN=4, no_sdf=False, sdf_scene=None) -> LinArgsC:
+    """sdf_scene: a SceneSdfOptsC (scene_sdf_opts) -- the scene's exact distance as the SDF row, no network."""
+    a = LinArgsC(B, N, np_, latent_mode, *[_ptr(bufs.get(k)) for k in LIN_PTRS], int(nyN), int(bool(no_sdf)),
+                 _ptr(bufs.get("hE")), _ptr(bufs.get("JhE")))
+    if sdf_scene is not None:
+        a.sdf_scene = C.pointer(sdf_scene)
+        a._keep = sdf_scene
+    return a
 
 
 def linearize(ctx: Context, net, model: QuadModelC, B: int, N: int, np_: int, bufs: dict, latent_mode=0, nyN=4,
-              no_sdf=False):
+              no_sdf=False, sdf_scene=None):
     """Enqueue the batched preparation phase.  bufs: device tensors named as sdfnmpc_lin_args (net may be
-    None with no_sdf)."""
-    a = lin_args(B, N, np_, bufs, latent_mode, nyN, no_sdf)
+    None with no_sdf or sdf_scene)."""
+    a = lin_args(B, N, np_, bufs, latent_mode, nyN, no_sdf, sdf_scene)
     _check(load().sdfnmpc_linearize(ctx.h, None if net is None else net.h, C.byref(model), C.byref(a)))
 
 
@@ -520,10 +548,10 @@ def qp_solve(ctx: Context, opts: QpOptsC, B: int, N: int, bufs: dict):
 
 
 def rti_prepare(ctx: Context, net, model: QuadModelC, opts: QpOptsC, B: int, N: int, np_: int, bufs: dict,
-                latent_mode=0, no_sdf=False):
+                latent_mode=0, no_sdf=False, sdf_scene=None):
     """Enqueue the RTI preparation phase acados-style: linearisation + the QP's stage records (everything
     but x0).  bufs: device tensors named as sdfnmpc_lin_args and sdfnmpc_qp_args."""
-    la = lin_args(B, N, np_, bufs, latent_mode, opts.nyN, no_sdf)
+    la = lin_args(B, N, np_, bufs, latent_mode, opts.nyN, no_sdf, sdf_scene)
     qa = QpArgsC(B, N, *[_ptr(bufs.get(k)) for k in QP_IN + QP_OUT])
     _check(load().sdfnmpc_rti_prepare(ctx.h, None if net is None else net.h, C.byref(model), C.byref(la),
                                       C.byref(opts), C.byref(qa)))
@@ -549,11 +577,11 @@ class RtiStep:
     must stay alive and at the same addresses."""
 
     def __init__(self, ctx: Context, net, model: QuadModelC, opts: QpOptsC, B: int, N: int, np_: int, bufs: dict,
-                 u0=None, latent_mode=0, no_sdf=False, graph=False):
+                 u0=None, latent_mode=0, no_sdf=False, graph=False, sdf_scene=None):
         self._lib = load()
         self._ctx, self._net = ctx.h, None if net is None else net.h
         self._model, self._opts, self._B, self._N = model, opts, B, N
-        self._la = lin_args(B, N, np_, bufs, latent_mode, opts.nyN, no_sdf)
+        self._la = lin_args(B, N, np_, bufs, latent_mode, opts.nyN, no_sdf, sdf_scene)
         self._qa = QpArgsC(B, N, *[_ptr(bufs.get(k)) for k in QP_IN + QP_OUT])
         self._apply = (_ptr(bufs["x"]), _ptr(bufs["u"]), _ptr(bufs["dx"]), _ptr(bufs["du"]), _ptr(u0),
                        _ptr(bufs.get("status")))
@@ -598,7 +626,7 @@ def shooting_grid(N: int, T: float, uniform=True, nb_short_nodes=2, dt_short=0.0
 
 def ref_opts(cfg, mode: int) -> RefOptsC:
     """RefGen knobs of a config (ref_gen.py) for sdfnmpc_pack_refs; mode 0 waypoints, 1 joystick, 2 from_x0,
-    -1 latent / flag only."""
+    -1 latent / flag only, -2 pose only."""
     r = cfg.ref
     ym = str(r.yaw_mode)
     yaw_mode = {"ref": 1, "align": 2, "curent": 3}.get(ym, 0)  # 'current' / 'zero': identity (ref_gen.py:12, sic)
@@ -748,6 +776,15 @@ def scene_pose(ctx: "Context", B_p_C, B_R_C, B: int, x, W_p_Bo, W_R_Bo, W_p_C, W
     rv = (C.c_double * 9)(*[float(v) for v in np.asarray(B_R_C, dtype=float).ravel()])
     _check(load().sdfnmpc_scene_pose(ctx.h, pv, rv, int(B), _ptr(x), _ptr(W_p_Bo), _ptr(W_R_Bo),
                                      _ptr(W_p_C), _ptr(W_R_C)))
+
+
+def scene_sdf_rows(ctx: "Context", scene_h, B: int, N: int, np_: int, x, p, h, Jh, max_df: float, scene_of=None,
+                   t0: float = 0.0, tau=None):
+    """Enqueue sdfnmpc_scene_sdf_rows: the scene's exact distance as the SDF row of h [B][N+1][3] / Jh
+    [B][N+1][10][3] (column 2) at the positions x [B][N+1][10][:3], flag p [B][N+1][np][0]; node k at t0 + tau[k]."""
+    o = scene_sdf_opts(scene_h, max_df, scene_of, t0, tau)
+    _check(load().sdfnmpc_scene_sdf_rows(ctx.h, C.byref(o), int(B), int(N), int(np_), _ptr(x), _ptr(p), _ptr(h),
+                                         _ptr(Jh)))
 
 
 def scene_distance(ctx: "Context", scene_h, points, p_to_scene, n: int, out):
@@ -995,6 +1032,28 @@ class Solver:
             self._rollout_keep += (perceive,)
             _check(load().sdfnmpc_solver_rollout_perceive_at(self.h, C.byref(a), C.byref(perceive),
                                                              float(scene_clock[0]), float(scene_clock[1])))
+
+    def set_sdf_scene(self, scene_h, scene_of=None, max_df: float = 1.0, predict: bool = False):
+        """sdfnmpc_solver_set_sdf_scene: the scene's exact distance instead of the network from the next step on;
+        scene_h None returns to the network.  scene_of: a device int32 [B] array, kept alive here."""
+        _check(load().sdfnmpc_solver_set_sdf_scene(self.h, scene_h, _ptr(scene_of), float(max_df), int(bool(predict))))
+        self._sdf_scene_keep = (scene_h, scene_of)
+
+    def set_scene_time(self, t: float):
+        _check(load().sdfnmpc_solver_set_scene_time(self.h, float(t)))
+
+    def rollout_scene_sdf(self, steps: int, plant: PlantOpts, x_log, u_log, pose: "PoseRefreshArgsC" = None, phase: int = 0,
+                          t0: float = 0.0, dt: float = 0.0, status_log=None, iters_log=None, pts_log=None, shift: int = 0,
+                          ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0):
+        """Enqueue sdfnmpc_solver_rollout_scene_sdf: `rollout` for a solver with a scene source -- before step k the
+        scene time t0 + (phase + k) dt, and with pose (a PoseRefreshArgsC) the camera pose of p refreshed from the
+        plant state before every `every`-th step."""
+        a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
+                         _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
+                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
+        self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, pose)
+        _check(load().sdfnmpc_solver_rollout_scene_sdf(self.h, C.byref(a), None if pose is None else C.byref(pose),
+                                                       int(phase), float(t0), float(dt)))
 
     def wait(self):
         _check(load().sdfnmpc_solver_wait(self.h, self.u0.ctypes.data, self.status.ctypes.data, self.iters.ctypes.data))

@@ -64,6 +64,7 @@ class Nmpc:
         self.cmd_TRPYr_hover = np.array([cfg.robot.mass * self.model.g, 0, 0, 0])
         self.cmd_TRPYr_min = [0, -lim.roll, -lim.pitch, -lim.wz]
         self.cmd_TRPYr_max = [lim.gamma, lim.roll, lim.pitch, lim.wz]
+        self._sdf_scene = None  # the scene whose exact distance replaces the network (set_sdf_scene)
         self.reset()
 
     # ---- state of the controller (host arrays, batch-leading; B == 1 keeps the reference's shapes)
@@ -146,6 +147,46 @@ class Nmpc:
         self._mark("pose")
         self._mark("latent")
 
+    # ---- the exact scene distance as the SDF (csrc/scene_sdf.hip)
+    def set_sdf_scene(self, scene, max_df=None, predict=False):
+        """The SDF row of the constraints (and the sdf cost) from the exact signed distance of ``scene`` (a
+        ``scene.Scene`` on the controller's context) instead of the network, truncated at ``max_df`` (default
+        model.max_df) as the network's training target is: the same controller with a perfect distance, the yardstick
+        a learned one is measured against.  ``solve`` and ``rollout`` use it from the next call on; the scene is seen at
+        the time of ``set_scene_time`` (``rollout`` sets it per step).  predict: node k of the horizon sees a moving
+        scene at that time + the node's own time on the shooting grid, not as a static world.  None restores the
+        network, and so does closing the scene while it is the source.  ValueError, before anything is enqueued: a batch split over several devices, a scene on another
+        context, a ``scene_of`` that does not fit the batch, a model whose flags read no SDF."""
+        if len(self.ocp.parts) != 1:
+            raise ValueError("set_sdf_scene(): the batch is split over several devices; sharded batches are not built")
+        solver = self.ocp.parts[0].solver
+        if scene is None:
+            solver.set_sdf_scene(None)
+            if self._sdf_scene is not None:
+                self._sdf_scene._sdf_users.discard(self)
+            self._sdf_scene = None
+            return
+        if scene.ctx is not self.ocp.ctx:
+            raise ValueError("set_sdf_scene(): the scene must be built on the controller's context (ctx=nmpc.ocp.ctx)")
+        scene._batch(max(self.B, 1))
+        if not self.model.need_sdf:
+            raise ValueError("set_sdf_scene(): no constraint row or cost of this model's flags reads the SDF")
+        md = float(self.model.max_df if max_df is None else max_df)
+        if not (np.isfinite(md) and md > 0.0):
+            raise ValueError(f"max_df {max_df}: positive and finite")
+        solver.set_sdf_scene(scene.h, scene._scene_of, md, bool(predict))
+        if self._sdf_scene is not None:
+            self._sdf_scene._sdf_users.discard(self)
+        self._sdf_scene = scene  # kept alive here; Scene.close() takes itself out of its users first
+        scene._sdf_users.add(self)
+
+    def set_scene_time(self, t):
+        """The time a scene source is seen at by the next ``solve`` (0 at creation)."""
+        if not np.isfinite(float(t)):
+            raise ValueError(f"scene time {t}: a finite time")
+        for part in self.ocp.parts:
+            part.solver.set_scene_time(float(t))
+
     # ---- control iteration
     def set_x0(self, x0):
         """Current state feedback (controller.py:67-71); the first call initialises the OCP iterate."""
@@ -226,7 +267,13 @@ class Nmpc:
         K, Bn, ctx, solver = int(steps), max(self.B, 1), self.ocp.ctx, self.ocp.parts[0].solver
         if K < 1:
             raise ValueError(f"rollout of {K} steps: at least one")
-        if scene is None:
+        src = self._sdf_scene
+        if src is not None:  # a scene source: the exact distance, no perception (every refusal before any upload)
+            if scene is not None or vae is not None or sensor is not None:
+                raise ValueError("rollout(): scene, vae and sensor exclude a scene source (set_sdf_scene): the "
+                                 "controller reads the scene's exact distance, not an image")
+            _check_schedule(perceive_every, perceive_phase, scene_t0, scene_dt)
+        elif scene is None:
             if vae is not None:
                 raise ValueError("rollout(): vae is the encoder of a scene's images; give scene too")
             if sensor is not None:
@@ -241,12 +288,7 @@ class Nmpc:
                                  "(ctx=nmpc.ocp.ctx)")
             if vae.B != Bn:
                 raise ValueError(f"rollout(): the VaeWrapper encodes {vae.B} images, the batch has {Bn}")
-            if int(perceive_every) < 1 or int(perceive_phase) < 0:
-                raise ValueError(f"perceive_every {perceive_every} / perceive_phase {perceive_phase}: at least 1 / 0")
-            if not np.isfinite(float(scene_t0)):
-                raise ValueError(f"scene_t0 {scene_t0}: a finite time")
-            if scene_dt is not None and not (np.isfinite(float(scene_dt)) and float(scene_dt) >= 0.0):
-                raise ValueError(f"scene_dt {scene_dt}: finite and not negative")
+            _check_schedule(perceive_every, perceive_phase, scene_t0, scene_dt)
             scene._batch(Bn)
             if sensor is not None and sensor.ctx is not ctx:
                 raise ValueError("rollout(): the SensorModel must be built on the controller's context (ctx=nmpc.ocp.ctx)")
@@ -270,18 +312,12 @@ class Nmpc:
         perc = None
         if scene is not None:
             ih, iw = (int(v) for v in (img_shape if img_shape is not None else self.cfg.sensor.shape_imgs[-2:]))
-            ws = {"images": _lib.DeviceArray(ctx, (Bn, ih, iw), np.float32)}
-            ws.update({k: _lib.DeviceArray(ctx, (Bn, n)) for k, n in (("W_p_Bo", 3), ("W_R_Bo", 9), ("W_p_C", 3),
-                                                                     ("W_R_C", 9))})
-            sens = self.cfg.sensor
+            ws = dict(_pose_workspaces(ctx, Bn), images=_lib.DeviceArray(ctx, (Bn, ih, iw), np.float32))
             vo = _lib.VaeOptsC(Bn, ih, iw, 0, float(vae.opts.clip), _lib._ptr(vae.yz) if vae.depth2range else None)
             perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(self.cfg), ih, iw,
-                                      scene.scale(self.cfg, normalized=False),
-                                      (_lib.C.c_double * 3)(*[float(v) for v in np.asarray(sens.B_p_C, float).ravel()]),
-                                      (_lib.C.c_double * 9)(*[float(v) for v in np.asarray(sens.B_R_C, float).ravel()]),
+                                      scene.scale(self.cfg, normalized=False), *_extrinsics(self.cfg),
                                       vae.vae.h, vo, int(perceive_every), int(perceive_phase), ws["images"].data_ptr(), vae.latent.data_ptr(),
-                                      vae.latent64.data_ptr(), *[ws[k].data_ptr() for k in ("W_p_Bo", "W_R_Bo", "W_p_C",
-                                                                                            "W_R_C")])
+                                      vae.latent64.data_ptr(), *[ws[k].data_ptr() for k in POSE_WS])
             kw["perceive"] = perc
             if sensor is not None:  # in the units of the raw image the renderer writes for the encoder
                 kw["sensor"] = sensor.opts(Bn, ih, iw, normalized=False)
@@ -300,7 +336,15 @@ class Nmpc:
                "iters_log": _lib.DeviceArray(ctx, (Bn, max(K, 1)), np.int32)}
         if dimg is not None:
             log["pts_log"] = _lib.DeviceArray(ctx, (Bn, K + 1, 3), np.float32)
-        solver.rollout(K, plant, shift=int(self.cfg.mpc.shift), **kw, **log)
+        if src is not None:  # the pose the FOV rows read is refreshed from the plant state, the scene's clock per step
+            ws = _pose_workspaces(ctx, Bn)
+            pose = _lib.PoseRefreshArgsC(int(perceive_every), *_extrinsics(self.cfg), *[ws[k].data_ptr() for k in POSE_WS])
+            t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)
+            solver.rollout_scene_sdf(K, plant, pose=pose, phase=int(perceive_phase), t0=t0, dt=dts,
+                                     shift=int(self.cfg.mpc.shift), **kw, **log)
+            self._clean("pose")  # written on the device, as after set_pose_device
+        else:
+            solver.rollout(K, plant, shift=int(self.cfg.mpc.shift), **kw, **log)
         u0 = solver.wait().copy()
         out = Rollout(log["x_log"].numpy(), log["u_log"].numpy(), log["status_log"].numpy(), log["iters_log"].numpy())
         if dimg is not None:
@@ -311,16 +355,9 @@ class Nmpc:
                           safe_ball_size, _lib.FieldView(dimg.data_ptr(), ishape, np.float32, ctx), pts, None, lab)
             out.col = lab.numpy().astype(bool).reshape(Bn, K + 1)  # point j belongs to image j / (K + 1)
             out.pts = log["pts_log"].numpy()
-        if perc is not None:  # one launch over the logged positions; point j belongs to instance j // (K + 1)
-            p2s = None if scene.S == 1 else np.repeat(scene.scene_of if scene.scene_of is not None else
-                                                      np.zeros(Bn, np.int32), K + 1)
-            rows = np.ascontiguousarray(out.x[:, :, :3]).reshape(-1, 3)
-            out.t = t0 + (int(perceive_phase) + np.arange(K + 1)) * dts
-            if scene.is_dynamic:
-                out.clearance = scene.distance(rows, p2s, t=np.tile(out.t, Bn)).reshape(Bn, K + 1)
-            else:
-                out.clearance = scene.distance(rows, p2s).reshape(Bn, K + 1)
-            if keep_img:
+        if perc is not None or src is not None:  # against the rendered scene, or the source scene
+            _log_clearance(out, scene if perc is not None else src, t0 + (int(perceive_phase) + np.arange(K + 1)) * dts)
+            if perc is not None and keep_img:
                 out.img = ws["images"].numpy()
         self.x0 = out.x[:, -1].copy() if self.B > 1 else out.x[0, -1].copy()
         ocp = self.ocp
@@ -521,6 +558,40 @@ class Nmpc:
             part.ctx.synchronize()
         self._clean("pose", "latent", *(("flag",) if flag is not None else ()))
 
+    def set_pose_device(self, W_p_Bo, W_R_Bo):
+        """``set_latent_device`` without the latent: the camera pose in p (the columns the field-of-view rows read) of
+        every node from the body pose W_p_Bo [B][3], W_R_Bo [B][9] (host or device fp64 arrays), on the device
+        buffers; the flag and the latent stay.  What a loop without an encoder (``set_sdf_scene``) refreshes."""
+        from . import _lib
+        Bn = max(self.B, 1)
+        cols = {"W_p_Bo": 3, "W_R_Bo": 9}
+        given = {"W_p_Bo": W_p_Bo, "W_R_Bo": W_R_Bo}
+        host = {}
+        for k, v in given.items():
+            if not hasattr(v, "data_ptr"):
+                host[k] = np.reshape(np.asarray(v, dtype=np.float64), (Bn, cols[k]))
+            elif np.dtype(str(v.dtype).replace("torch.", "")) != np.float64:
+                raise TypeError(f"device input must be float64, got {v.dtype}")
+        parts = self.ocp.parts
+        synced = set()
+        for part in parts:
+            lo, nb = part.lo, part.hi - part.lo
+            args = {"p": part.solver.field("p")}
+            for k, v in given.items():
+                if k not in host and len(parts) > 1 and _device_of(v) != part.ctx.device:
+                    host[k] = _download(v, Bn, cols[k])  # another device: through the host, once per array
+                if k in host:
+                    args[k] = _lib.DeviceArray.from_numpy(part.ctx, np.ascontiguousarray(host[k][lo:part.hi]))
+                else:
+                    v = given[k] = _producer_done(v, part.ctx, synced)
+                    args[k] = v if len(parts) == 1 else _lib.FieldView(v.data_ptr() + lo * cols[k] * 8, (nb, cols[k]),
+                                                                       np.float64, part.ctx)
+            _lib.pack_refs(part.ctx, _lib.ref_opts(self.cfg, -2), nb, self.N, self.model.np, self.model.ny, args,
+                           nyN=self.model.nyN)
+        for part in parts:
+            part.ctx.synchronize()
+        self._clean("pose")
+
     def set_ref(self, ref, k, b=None):
         """y, W and q_d of node k from a reference object (controller.py:136-142); b selects one instance
         of a batch (None: all)."""
@@ -538,6 +609,45 @@ class Nmpc:
             self.yN[sel] = y[: self.model.nyN]
             self._mark("yNref", b)
             self._mark("WN", b)
+
+
+POSE_WS = ("W_p_Bo", "W_R_Bo", "W_p_C", "W_R_C")  # the pose workspaces of a rollout, [B][3] / [B][9]
+
+
+def _check_schedule(perceive_every, perceive_phase, scene_t0, scene_dt):
+    """The perception / pose-refresh schedule and the scene clock of ``rollout``: ValueError before anything is enqueued."""
+    if int(perceive_every) < 1 or int(perceive_phase) < 0:
+        raise ValueError(f"perceive_every {perceive_every} / perceive_phase {perceive_phase}: at least 1 / 0")
+    if not np.isfinite(float(scene_t0)):
+        raise ValueError(f"scene_t0 {scene_t0}: a finite time")
+    if scene_dt is not None and not (np.isfinite(float(scene_dt)) and float(scene_dt) >= 0.0):
+        raise ValueError(f"scene_dt {scene_dt}: finite and not negative")
+
+
+def _pose_workspaces(ctx, Bn):
+    from . import _lib
+    return {k: _lib.DeviceArray(ctx, (Bn, 3 if "_p_" in k else 9)) for k in POSE_WS}
+
+
+def _extrinsics(cfg):
+    """sensor.B_p_C, sensor.B_R_C (row-major) as the C structures take them"""
+    from . import _lib
+    s = cfg.sensor
+    return ((_lib.C.c_double * 3)(*[float(v) for v in np.asarray(s.B_p_C, float).ravel()]),
+            (_lib.C.c_double * 9)(*[float(v) for v in np.asarray(s.B_R_C, float).ravel()]))
+
+
+def _log_clearance(out, scene, t):
+    """``Rollout.t`` and ``Rollout.clearance``: one distance launch over the logged positions (point j belongs to
+    instance j // (K + 1)), row j of a dynamic set against the scene at t[j]."""
+    Bn, K1 = out.x.shape[:2]
+    p2s = None if scene.S == 1 else np.repeat(scene.scene_of if scene.scene_of is not None else np.zeros(Bn, np.int32), K1)
+    rows = np.ascontiguousarray(out.x[:, :, :3]).reshape(-1, 3)
+    out.t = t
+    if scene.is_dynamic:
+        out.clearance = scene.distance(rows, p2s, t=np.tile(t, Bn)).reshape(Bn, K1)
+    else:
+        out.clearance = scene.distance(rows, p2s).reshape(Bn, K1)
 
 
 def _producer_done(a, ctx, synced: set):

@@ -1296,12 +1296,17 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
     return SDFNMPC_OK;
 }
 
+// the option check + argument block of sdfnmpc_scene_sdf_rows (below, with the scenes): nothing is launched
+extern "C" int sdfnmpc_scene_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int B, int N, int np,
+                                       const double* x, const double* p, double* h, double* Jh, SceneSdfArgs* out);
+
 // ------------------------------------------------------------------------------------------------
 // batched preparation phase
 // pk != NULL (sdfnmpc_rti_prepare): the QP stage records are packed in the same phase.  With ny == 11
 // the pack runs after the linearisation on the aux stream, beside the SDF kernel, and only the sdf row
 // of C^T waits for the join; with the sdf cost (ny == 12) H and g depend on h[2], so the whole pack
-// follows the join.
+// follows the join.  With lin_args.sdf_scene no network runs: linearize, the scene's rows kernel (scene_sdf.hip) and the
+// whole pack follow each other on the main stream.
 static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad_model* mdl,
                     const sdfnmpc_lin_args* a, const QpArgs* pk, bool* split_out = nullptr) {
     if (!ctx || !mdl || !a) return fail(SDFNMPC_E_ARG, "NULL argument");
@@ -1313,8 +1318,10 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
         if (!(mdl->tau_roll > 0.0) || !(mdl->tau_pitch > 0.0))
             return fail(SDFNMPC_E_ARG, "model.kind 1 ('att_tau') needs tau_roll > 0 and tau_pitch > 0");
     }
-    const bool no_sdf = a->no_sdf != 0;
-    if (!net && !no_sdf) return fail(SDFNMPC_E_ARG, "NULL network (only allowed with lin_args.no_sdf)");
+    if (a->no_sdf && a->sdf_scene) return fail(SDFNMPC_E_ARG, "lin_args.sdf_scene together with lin_args.no_sdf");
+    // no network is evaluated: nothing reads the SDF, or the SDF row is the scene's exact distance (sdf_scene)
+    const bool no_sdf = a->no_sdf != 0 || a->sdf_scene;
+    if (!net && !no_sdf) return fail(SDFNMPC_E_ARG, "NULL network (only allowed with lin_args.no_sdf or .sdf_scene)");
     if (a->B < 0 || a->N < 1 || a->np < 17 + (net ? net->host.L : 0) || (a->latent_mode != 0 && a->latent_mode != 1))
         return fail(SDFNMPC_E_ARG, "bad B/N/np/latent_mode");
     const int nyN = a->nyN == 0 ? 4 : a->nyN;
@@ -1329,6 +1336,9 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
         !a->Jh)
         return fail(SDFNMPC_E_ARG, "NULL array in sdfnmpc_lin_args");
     if (net && net->device != ctx->device) return fail(SDFNMPC_E_ARG, "net and ctx are on different devices");
+    SceneSdfArgs ssa{};
+    if (a->sdf_scene)  // refused before the first launch
+        if (int rc_ = sdfnmpc_scene_sdf_args_(ctx, a->sdf_scene, a->B, a->N, a->np, a->x, a->p, a->h, a->Jh, &ssa)) return rc_;
     ScopedDevice sd(ctx->device);
     const long long rows = (long long)a->B * (a->N + 1);
     float4* sdf4 = (float4*)a->sdf;
@@ -1402,6 +1412,8 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
     int rc;
     if (no_sdf) {  // no constraint or cost reads the network: the linearisation alone, then the pack
         HIPCHK(timed(ctx, "linearize", [&] { return launch_linearize(la, ctx->stream); }, ctx->stream));
+        if (a->sdf_scene)  // the SDF row from the scene's closed forms, between the linearisation and the pack
+            HIPCHK(timed(ctx, "scene_sdf_rows", [&] { return launch_scene_sdf_rows(ssa, ctx->stream); }));
         return finish_pack();
     }
     // 2. latent hoisting (latent = p[.][17:] as fp32)
@@ -1646,6 +1658,7 @@ extern "C" int sdfnmpc_step_create(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, con
     if (!ctx || !mdl || !la || !o || !qa || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_step_create");
     *out = nullptr;
     if (qa->B < 1) return fail(SDFNMPC_E_ARG, "step_create: B must be >= 1");
+    if (la->sdf_scene) return fail(SDFNMPC_E_UNSUPPORTED, "step_create: lin_args.sdf_scene (a scene as the SDF source) is not captured");
     // once eagerly: every workspace is allocated and every argument checked before the capture (no
     // allocation may happen inside it)
     if (int rc = step_eager(ctx, net, mdl, la, o, qa, u0, status)) return rc;
@@ -1716,13 +1729,14 @@ extern "C" int sdfnmpc_pack_refs(sdfnmpc_ctx* ctx, const sdfnmpc_ref_opts* o, co
     if (!ctx || !o || !a) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_pack_refs");
     if (a->B < 0 || a->N < 1 || a->np < 17 || (a->ny != 11 && a->ny != 12) || !a->p)
         return fail(SDFNMPC_E_ARG, "pack_refs: bad B / N / np / ny or NULL p");
-    if (o->mode < -1 || o->mode > 2) return fail(SDFNMPC_E_ARG, "pack_refs: mode must be -1..2");
+    if (o->mode < -2 || o->mode > 2) return fail(SDFNMPC_E_ARG, "pack_refs: mode must be -2..2");
+    if (o->mode == -2 && (!a->W_p_Bo || !a->W_R_Bo)) return fail(SDFNMPC_E_ARG, "pack_refs: mode -2 (pose only) needs W_p_Bo and W_R_Bo");
     if (o->mode >= 0 && (!a->x0 || a->x0_stride < 7 || !a->wrow || !a->yref || !a->W || !a->yNref || !a->WN))
         return fail(SDFNMPC_E_ARG, "pack_refs: x0 (stride >= 7), wrow and the reference outputs are required");
     if (o->mode == 0 && (a->n_wp < 1 || a->n_wp > RP_MAX_WP || !a->wp_p || !a->wp_q))
         return fail(SDFNMPC_E_ARG, "pack_refs: mode 0 needs 1..32 waypoints (wp_p, wp_q)");
     if (o->mode == 1 && !a->vw) return fail(SDFNMPC_E_ARG, "pack_refs: mode 1 needs vw");
-    if (a->latent && (!a->W_p_Bo || !a->W_R_Bo || a->L < 1 || 17 + a->L > a->np))
+    if (o->mode != -2 && a->latent && (!a->W_p_Bo || !a->W_R_Bo || a->L < 1 || 17 + a->L > a->np))
         return fail(SDFNMPC_E_ARG, "pack_refs: latent needs W_p_Bo, W_R_Bo and 17 + L <= np");
     ScopedDevice sd(ctx->device);
     RefPackArgs r{};
@@ -1736,6 +1750,7 @@ extern "C" int sdfnmpc_pack_refs(sdfnmpc_ctx* ctx, const sdfnmpc_ref_opts* o, co
     for (int i = 0; i < 9; ++i) r.B_R_C[i] = o->B_R_C[i];
     r.x0 = a->x0; r.x0_stride = a->x0_stride; r.wp_p = a->wp_p; r.wp_q = a->wp_q; r.vw = a->vw; r.wrow = a->wrow;
     r.latent = a->latent; r.W_p_Bo = a->W_p_Bo; r.W_R_Bo = a->W_R_Bo; r.flag = a->flag;
+    if (o->mode == -2) r.latent = r.flag = nullptr;  // pose only: the latent and flag columns stay
     r.p = a->p; r.yref = a->yref; r.W = a->W; r.yNref = a->yNref; r.WN = a->WN;
     HIPCHK(timed(ctx, "ref_pack", [&] { return launch_ref_pack(r, ctx->stream); }));
     return SDFNMPC_OK;
@@ -2387,6 +2402,36 @@ extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* 
         return SDFNMPC_OK;
     }
     HIPCHK(timed(ctx, "scene_dist", [&] { return launch_scene_distance(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+// the scene's exact distance as the SDF row (scene_sdf.hip): the option check and the argument block, split from the
+// launch as the other scene entry points' are, for the preparation phase (lin_args.sdf_scene) and the solver
+extern "C" int sdfnmpc_scene_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int B, int N, int np,
+                                       const double* x, const double* p, double* h, double* Jh, SceneSdfArgs* out) {
+    if (!ctx || !o || !o->scene || !out) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: NULL context, options or scene");
+    if (B < 0 || N < 1 || np < 17) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: B >= 0, N >= 1 and np >= 17 required");
+    if (!(o->max_df > 0.0) || !std::isfinite(o->max_df))
+        return fail(SDFNMPC_E_ARG, "scene_sdf_rows: max_df must be positive and finite");
+    if (!std::isfinite(o->t0)) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: the time t0 must be finite");
+    if (o->scene->ctx != ctx) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: the scene lives on another context");
+    if (B > 0 && (!x || !p || !h || !Jh)) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: NULL x, p, h or Jh");
+    SceneSdfArgs a{};
+    a.sc = o->scene->dev; a.dyn = o->scene->dyn; a.scene_of = o->scene_of;
+    a.rows = (long long)B * (N + 1); a.N1 = N + 1; a.np = np;
+    a.x = x; a.p = p; a.h = h; a.Jh = Jh;
+    a.max_df = o->max_df; a.t0 = o->t0; a.tau = o->tau;
+    *out = a;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_sdf_rows(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int B, int N, int np,
+                                      const double* x, const double* p, double* h, double* Jh) {
+    SceneSdfArgs a{};
+    if (int rc = sdfnmpc_scene_sdf_args_(ctx, o, B, N, np, x, p, h, Jh, &a)) return rc;
+    if (B == 0) return SDFNMPC_OK;
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "scene_sdf_rows", [&] { return launch_scene_sdf_rows(a, ctx->stream); }));
     return SDFNMPC_OK;
 }
 

@@ -47,7 +47,8 @@ __global__ __launch_bounds__(64) void ref_pack_kernel(RefPackArgs A) {
     double* P = A.p + (size_t)b * N1 * np_;
 
     // ---- set_latent / set_sdf_flag (controller.py:45-54): every node
-    if (A.latent) {
+    //      (mode -2: the pose block alone, for a controller without an encoder; the latent and the flag stay)
+    if (A.latent || A.mode == -2) {
         const double* Rb = A.W_R_Bo + (size_t)b * 9;
         const double* pb = A.W_p_Bo + (size_t)b * 3;
         double pc[3], rc[9];
@@ -63,10 +64,12 @@ __global__ __launch_bounds__(64) void ref_pack_kernel(RefPackArgs A) {
             for (int i = 0; i < 3; ++i) pk[1 + i] = pc[i];
             for (int i = 0; i < 9; ++i) pk[4 + i] = rc[i];
         }
-        const double* lat = A.latent + (size_t)b * A.L;
-        for (int e = tid; e < N1 * A.L; e += 64) {
-            const int k = e / A.L, j = e - k * A.L;
-            P[(size_t)k * np_ + 17 + j] = lat[j];
+        if (A.latent) {
+            const double* lat = A.latent + (size_t)b * A.L;
+            for (int e = tid; e < N1 * A.L; e += 64) {
+                const int k = e / A.L, j = e - k * A.L;
+                P[(size_t)k * np_ + 17 + j] = lat[j];
+            }
         }
     } else if (A.flag) {
         for (int k = tid; k < N1; k += 64) P[(size_t)k * np_] = A.flag[b];

@@ -19,7 +19,7 @@
 // slab intervals (box), of the quadratic's root interval (sphere), or of both (cylinder: side wall and caps).
 // The ray hits when tf >= max(tn, 0), at t = max(tn, 0): an origin inside gives t = 0 for every ray.  No
 // atomics, no cross-lane traffic: a pixel depends on its instance's pose and scene only.
-#include "scene_kernels.h"
+#include "scene_dev.h"
 
 namespace sdfn {
 
@@ -197,20 +197,7 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_distance_kernel(SceneDistAr
     A.out[j] = best;
 }
 
-// ---- primitives with a frame that is a function of time (oriented and moving obstacles)
-// c(t) = c0 + v t + amp sin(omega t + phase), R(t) = Rz(yaw_rate t) R0 (row-major), in fp64: the one place both
-// dynamic kernels take a primitive's frame from
-__device__ __forceinline__ void prim_frame(const ScenePrimDyn& P, double t, double* c, double* R) {
-    const double ay = P.yaw_rate * t, ah = P.omega * t + P.phase;
-    const double sy = sin(ay), cy = cos(ay), sh = sin(ah);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        c[j] = P.c0[j] + P.v[j] * t + P.amp[j] * sh;
-        R[j] = cy * P.R0[j] - sy * P.R0[3 + j];
-        R[3 + j] = sy * P.R0[j] + cy * P.R0[3 + j];
-        R[6 + j] = P.R0[6 + j];
-    }
-}
+// ---- primitives with a frame that is a function of time (oriented and moving obstacles): prim_frame, scene_dev.h
 
 // scene_render_kernel for a dynamic scene set: the same launch geometry, rays, hit rule and output.  Lane i < cnt
 // of a block forms primitive i's frame at time t in fp64 and stores the camera in that frame, o' = R(t)^T (W_p_C -

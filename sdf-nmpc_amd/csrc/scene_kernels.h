@@ -88,6 +88,21 @@ struct SceneDistDynArgs {
     const double* times;     // [n] or nullptr (t = 0)
 };
 
+// scene_sdf.hip: the scene's exact distance written as the SDF row of h / J_h for rows = B (N+1) node rows
+struct SceneSdfArgs {
+    SceneDev sc;
+    const ScenePrimDyn* dyn; // [S][SCENE_MAX_PRIMS], or nullptr: a static set
+    const int* scene_of;     // [B] or nullptr (scene 0)
+    long long rows;          // B (N+1)
+    int N1, np;              // nodes per instance, parameters per node
+    const double* x;         // [rows][10]: the world position is x[r][0:3]
+    const double* p;         // [rows][np]: the flag is p[r][0]
+    double* h;               // [rows][3]: column 2 is written
+    double* Jh;              // [rows][10][3]: column 2 is written
+    double max_df, t0;
+    const double* tau;       // [N1] or nullptr: node k at time t0 + tau[k] (dynamic sets)
+};
+
 inline size_t scene_render_lds_bytes(int h, int w, int is_spherical) {
     return is_spherical ? (size_t)2 * ((size_t)h + (size_t)w) * sizeof(float) : 0;
 }
@@ -97,5 +112,6 @@ hipError_t launch_scene_pose(const ScenePoseArgs& a, hipStream_t s);
 hipError_t launch_scene_distance(const SceneDistArgs& a, hipStream_t s);
 hipError_t launch_scene_render_dyn(const SceneRenderDynArgs& a, hipStream_t s);
 hipError_t launch_scene_distance_dyn(const SceneDistDynArgs& a, hipStream_t s);
+hipError_t launch_scene_sdf_rows(const SceneSdfArgs& a, hipStream_t s);
 
 }  // namespace sdfn

@@ -1,0 +1,152 @@
+// The exact signed distance of an analytic scene as the preparation phase's SDF row: what sdf_mlp.hip's epilogue
+// writes from the network (gen_model.py:46-61: h[2] = flag df + (1 - flag) max_df and its position gradient), written
+// from the closed forms of scene.hip instead -- the yardstick controller whose distance constraint describes the
+// world it flies in.  The reference has no counterpart: its SDF is always the network.
+//
+//   scene_sdf_rows_kernel<false>   a static scene set: the world-frame primitives of scene_distance_kernel
+//   scene_sdf_rows_kernel<true>    a dynamic set: every primitive in its own frame (R(t), c(t)) at the node's time
+//                                  t0 + tau[k] (t0 for every node without tau), as scene_distance_dyn_kernel
+//
+// fp64, one node row r = b (N+1) + k per lane.  The distance of every primitive is the formula scene_distance(_dyn)_
+// kernel evaluates; its gradient g in the primitive's frame is taken on the same excesses, and the world gradient is
+// R(t) g of the primitive that attains the minimum (the lowest index on a tie).  Truncated as the network's training
+// target is (df_train.py:50): d >= max_df, and an empty scene, give df = max_df with a zero gradient.  No atomics, no
+// cross-lane traffic: a row depends on its position, its flag, its instance's scene and its time only.
+#include "scene_dev.h"
+
+namespace sdfn {
+
+namespace {
+
+__device__ __forceinline__ double sgn1(double v) { return v < 0.0 ? -1.0 : 1.0; }  // sign(0) = +1
+
+// distance and gradient of the canonical centred shape at the point q of its frame (sphere: radius h0; box: half
+// extents h0, h1, hz; capped cylinder along z: radius h0, half height hz).  The distance is sd_excess3 of scene.hip on
+// the per-axis excesses; at a kink the gradient is one of the one-sided values, finite and of norm <= 1.
+__device__ __forceinline__ double shape_sd(int kind, double qx, double qy, double qz, double h0, double h1, double hz,
+                                           double& gx, double& gy, double& gz) {
+    if (kind == 0) {
+        const double n = sqrt(qx * qx + qy * qy + qz * qz);
+        const bool z = n == 0.0;
+        gx = z ? 0.0 : qx / n;
+        gy = z ? 0.0 : qy / n;
+        gz = z ? 1.0 : qz / n;
+        return n - h0;
+    }
+    if (kind == 1) {
+        const double ax = fabs(qx) - h0, ay = fabs(qy) - h1, az = fabs(qz) - hz;
+        const double px = fmax(ax, 0.0), py = fmax(ay, 0.0), pz = fmax(az, 0.0);
+        const double len = sqrt(px * px + py * py + pz * pz);
+        const double amax = fmax(ax, fmax(ay, az));
+        if (amax > 0.0) {
+            gx = sgn1(qx) * px / len;
+            gy = sgn1(qy) * py / len;
+            gz = sgn1(qz) * pz / len;
+        } else {  // inside: the nearest face, the lowest axis on a tie
+            const bool mx = ax >= ay && ax >= az, my = !mx && ay >= az;
+            gx = mx ? sgn1(qx) : 0.0;
+            gy = my ? sgn1(qy) : 0.0;
+            gz = (!mx && !my) ? sgn1(qz) : 0.0;
+        }
+        return len + fmin(amax, 0.0);
+    }
+    const double rho = sqrt(qx * qx + qy * qy);
+    const bool z = rho == 0.0;
+    const double ex = z ? 1.0 : qx / rho, ey = z ? 0.0 : qy / rho;
+    const double a0 = rho - h0, a1 = fabs(qz) - hz;
+    const double p0 = fmax(a0, 0.0), p1 = fmax(a1, 0.0);
+    const double len = sqrt(p0 * p0 + p1 * p1 + 0.0);  // sd_excess3's third component is -inf: its positive part 0
+    const double amax = fmax(a0, a1);
+    if (amax > 0.0) {
+        gx = p0 * ex / len;
+        gy = p0 * ey / len;
+        gz = p1 * sgn1(qz) / len;
+    } else if (a0 >= a1) {
+        gx = ex; gy = ey; gz = 0.0;
+    } else {
+        gx = 0.0; gy = 0.0; gz = sgn1(qz);
+    }
+    return len + fmin(amax, 0.0);
+}
+
+template <bool DYN>
+__global__ __launch_bounds__(SCENE_BLOCK) void scene_sdf_rows_kernel(SceneSdfArgs A) {
+    const long long r = (long long)blockIdx.x * SCENE_BLOCK + threadIdx.x;
+    if (r >= A.rows) return;
+    const long long b = r / A.N1;
+    const int k = (int)(r - b * A.N1);
+    const long long s = A.scene_of ? (long long)min(max(A.scene_of[b], 0), A.sc.S - 1) : 0;
+    const int cnt = min(A.sc.count[s], SCENE_MAX_PRIMS);
+    const double* xr = A.x + r * 10;
+    const double px = xr[0], py = xr[1], pz = xr[2];
+    double best = INFINITY, bx = 0.0, by = 0.0, bz = 0.0;
+    if (DYN) {
+        const ScenePrimDyn* P = A.dyn + s * SCENE_MAX_PRIMS;
+        const double t = A.tau ? A.t0 + A.tau[k] : A.t0;
+        for (int i = 0; i < cnt; ++i) {
+            double c[3], R[9];
+            prim_frame(P[i], t, c, R);
+            const double ex = px - c[0], ey = py - c[1], ez = pz - c[2];
+            const double qx = R[0] * ex + R[3] * ey + R[6] * ez;
+            const double qy = R[1] * ex + R[4] * ey + R[7] * ez;
+            const double qz = R[2] * ex + R[5] * ey + R[8] * ez;
+            double gx, gy, gz;
+            const double d = shape_sd(P[i].kind, qx, qy, qz, P[i].h[0], P[i].h[1], P[i].h[2], gx, gy, gz);
+            if (d < best) {  // the lowest index on a tie
+                best = d;
+                bx = R[0] * gx + R[1] * gy + R[2] * gz;
+                by = R[3] * gx + R[4] * gy + R[5] * gz;
+                bz = R[6] * gx + R[7] * gy + R[8] * gz;
+            }
+        }
+    } else {
+        const ScenePrimD* P = A.sc.pd + s * SCENE_MAX_PRIMS;
+        for (int i = 0; i < cnt; ++i) {
+            const double* a = P[i].a;
+            const int kind = P[i].kind;
+            double qx, qy, qz, h0, h1 = 0.0, hz = 0.0;
+            if (kind == 0) {
+                qx = px - a[0]; qy = py - a[1]; qz = pz - a[2];
+                h0 = a[3];
+            } else if (kind == 1) {
+                qx = px - 0.5 * (a[0] + a[3]); qy = py - 0.5 * (a[1] + a[4]); qz = pz - 0.5 * (a[2] + a[5]);
+                h0 = 0.5 * (a[3] - a[0]); h1 = 0.5 * (a[4] - a[1]); hz = 0.5 * (a[5] - a[2]);
+            } else {
+                qx = px - a[0]; qy = py - a[1]; qz = pz - 0.5 * (a[3] + a[4]);
+                h0 = a[2]; hz = 0.5 * (a[4] - a[3]);
+            }
+            double gx, gy, gz;
+            const double d = shape_sd(kind, qx, qy, qz, h0, h1, hz, gx, gy, gz);
+            if (d < best) {
+                best = d;
+                bx = gx; by = gy; bz = gz;
+            }
+        }
+    }
+    const bool near = best < A.max_df;  // false for an empty scene (+inf)
+    const double df = near ? best : A.max_df;
+    if (!near) bx = by = bz = 0.0;
+    // the network epilogue's contract (sdf_mlp.hip): column 2 of h and of the ten Jacobian columns, nothing else
+    const double flag = A.p[r * A.np];
+    A.h[r * 3 + 2] = flag * df + (1.0 - flag) * A.max_df;
+    double* J = A.Jh + r * 30 + 2;
+    J[0] = flag * bx;
+    J[3] = flag * by;
+    J[6] = flag * bz;
+#pragma unroll
+    for (int j = 3; j < 10; ++j) J[j * 3] = 0.0;
+}
+
+}  // namespace
+
+hipError_t launch_scene_sdf_rows(const SceneSdfArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((a.rows + SCENE_BLOCK - 1) / SCENE_BLOCK));
+    if (a.dyn)
+        hipLaunchKernelGGL(scene_sdf_rows_kernel<true>, grid, dim3(SCENE_BLOCK), 0, s, a);
+    else
+        hipLaunchKernelGGL(scene_sdf_rows_kernel<false>, grid, dim3(SCENE_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace sdfn

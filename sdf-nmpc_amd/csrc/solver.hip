@@ -108,6 +108,11 @@ struct sdfnmpc_solver {
     hipStream_t stream = nullptr;
     int B = 0, N = 0, np = 0, ny = 0, nyN = 4, latent_mode = 0;
     bool no_sdf = false;  // no constraint row or cost reads the network
+    // the SDF source: a scene's exact distance instead of the network (sdfnmpc_solver_set_sdf_scene); sdf_src.scene ==
+    // NULL is the network.  tau: the node times of `predict`, built once from the solver's own dt grid
+    sdfnmpc_scene_sdf_opts sdf_src{};
+    double* tau = nullptr;
+    std::vector<double> h_dt;
     sdfnmpc_quad_model model{};
     sdfnmpc_qp_opts qp{};
     std::vector<void*> allocs;
@@ -224,6 +229,7 @@ extern "C" int sdfnmpc_solver_create(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, c
     s->no_sdf = !need_sdf;
     s->model = o->model;
     s->qp = o->qp;
+    s->h_dt.assign(o->dt, o->dt + o->N);
     SolverDevice sd(s->device);
     const size_t B = o->B, N = o->N, N1 = N + 1;
     hipError_t e = hipSuccess;
@@ -364,6 +370,7 @@ static int step_enqueue(sdfnmpc_solver* s) {
     la.x = s->x; la.u = s->u; la.p = s->p; la.dt = s->dt;
     la.xn = s->xn; la.AB = s->AB; la.y = s->y; la.Jy = s->Jy; la.yN = s->yN; la.JyN = s->JyN; la.h = s->h; la.Jh = s->Jh;
     la.nyN = s->nyN; la.no_sdf = s->no_sdf ? 1 : 0; la.hE = s->hE; la.JhE = s->JhE;
+    if (s->sdf_src.scene) la.sdf_scene = &s->sdf_src;  // t0: the solver's scene time (sdfnmpc_solver_set_scene_time)
     sdfnmpc_qp_args qa{};
     qa.B = s->B; qa.N = s->N;
     qa.xn = s->xn; qa.AB = s->AB; qa.y = s->y; qa.Jy = s->Jy; qa.yN = s->yN; qa.JyN = s->JyN; qa.h = s->h; qa.Jh = s->Jh;
@@ -388,6 +395,27 @@ extern "C" int sdfnmpc_solver_step(sdfnmpc_solver* s) {
     return SDFNMPC_OK;
 }
 
+// what every rollout refuses before its first launch: the step count and logs, the plant's options (pa is filled),
+// then what sdfnmpc_pack_refs would refuse (ra is filled when args->ref is set)
+static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, sdfn::PlantArgs& pa, sdfnmpc_ref_args& ra) {
+    if (a->steps < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
+    if (!a->x_log || !a->u_log) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: x_log and u_log are required");
+    if (int rc = sdfnmpc_plant_args_(&a->plant, s->B, s->x0, s->u0, s->x0, &pa)) return rc;
+    if (a->ref) {
+        const int mode = a->ref->mode;
+        if (mode < 0 || mode > 2) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref->mode must be 0, 1 or 2");
+        if (!a->wrow) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref needs wrow");
+        if (mode == 0 && (a->n_wp < 1 || a->n_wp > sdfn::RP_MAX_WP || !a->wp_p || !a->wp_q))
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref mode 0 needs 1..32 waypoints (wp_p, wp_q)");
+        if (mode == 1 && !a->vw) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref mode 1 needs vw");
+        ra.B = s->B; ra.N = s->N; ra.np = s->np; ra.ny = s->ny; ra.n_wp = mode == 0 ? a->n_wp : 0;
+        ra.x0 = s->x0; ra.x0_stride = 10;
+        ra.wp_p = a->wp_p; ra.wp_q = a->wp_q; ra.vw = a->vw; ra.wrow = a->wrow;
+        ra.p = s->p; ra.yref = s->yref; ra.W = s->W; ra.yNref = s->yNref; ra.WN = s->WN; ra.nyN = s->nyN;
+    }
+    return SDFNMPC_OK;
+}
+
 extern "C" int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a) {
     return sdfnmpc_solver_rollout_perceive(s, a, nullptr);
 }
@@ -409,24 +437,9 @@ extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const s
     if (sensor && !pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: a sensor model needs perception (perc)");
     if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
-    if (a->steps < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
-    if (!a->x_log || !a->u_log) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: x_log and u_log are required");
-    // every refusal before the first launch: the plant's options, then what sdfnmpc_pack_refs would refuse
     sdfn::PlantArgs pa{};
-    if (int rc = sdfnmpc_plant_args_(&a->plant, s->B, s->x0, s->u0, s->x0, &pa)) return rc;
     sdfnmpc_ref_args ra{};
-    if (a->ref) {
-        const int mode = a->ref->mode;
-        if (mode < 0 || mode > 2) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref->mode must be 0, 1 or 2");
-        if (!a->wrow) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref needs wrow");
-        if (mode == 0 && (a->n_wp < 1 || a->n_wp > sdfn::RP_MAX_WP || !a->wp_p || !a->wp_q))
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref mode 0 needs 1..32 waypoints (wp_p, wp_q)");
-        if (mode == 1 && !a->vw) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref mode 1 needs vw");
-        ra.B = s->B; ra.N = s->N; ra.np = s->np; ra.ny = s->ny; ra.n_wp = mode == 0 ? a->n_wp : 0;
-        ra.x0 = s->x0; ra.x0_stride = 10;
-        ra.wp_p = a->wp_p; ra.wp_q = a->wp_q; ra.vw = a->vw; ra.wrow = a->wrow;
-        ra.p = s->p; ra.yref = s->yref; ra.W = s->W; ra.yNref = s->yNref; ra.WN = s->WN; ra.nyN = s->nyN;
-    }
+    if (int rc = rollout_args(s, a, pa, ra)) return rc;
     // perception: the pose and render blocks, and what sdfnmpc_vae_encode / sdfnmpc_pack_refs (mode -1) would refuse
     sdfn::ScenePoseArgs spa{};
     sdfn::SceneRenderArgs sra{};
@@ -484,6 +497,95 @@ extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const s
                 if (int rc = sdfnmpc_sensor_launch_(s->ctx, &sna, &ora, sensor->outlier_rm != 0, pc->phase + k)) return rc;
             if (int rc = sdfnmpc_vae_encode(s->ctx, pc->vae, &vo, pc->images, pc->latent, pc->latent64)) return rc;
             if (int rc = sdfnmpc_pack_refs(s->ctx, &lo, &lra)) return rc;
+        }
+        if (a->ref)
+            if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
+        if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
+        if (int rc = step_enqueue(s)) return rc;
+        pa.k = k;
+        if (int rc = sdfnmpc_plant_launch_(s->ctx, &pa)) return rc;
+    }
+    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
+    s->pending = true;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_solver_set_sdf_scene(sdfnmpc_solver* s, const sdfnmpc_scene* scene, const int* scene_of,
+                                            double max_df, int predict) {
+    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
+    if (!scene) {  // back to the network
+        s->sdf_src = sdfnmpc_scene_sdf_opts{};
+        return SDFNMPC_OK;
+    }
+    if (s->no_sdf)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_sdf_scene: no row or cost of the solver's constraint set reads the SDF");
+    if (!sdfnmpc_scene_on_ctx_(scene, s->ctx))
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_sdf_scene: the scene must live on the solver's context");
+    if (!(max_df > 0.0) || !std::isfinite(max_df))
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_sdf_scene: max_df must be positive and finite");
+    SolverDevice sd(s->device);
+    if (predict && !s->tau) {  // tau[0] = 0, tau[k] = tau[k-1] + dt[k-1], summed in that order
+        std::vector<double> tau(s->N + 1, 0.0);
+        for (int k = 1; k <= s->N; ++k) tau[k] = tau[k - 1] + s->h_dt[k - 1];
+        double* d = nullptr;
+        SCHK(s->alloc(&d, (size_t)s->N + 1));
+        SCHK(hipMemcpyAsync(d, tau.data(), tau.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        SCHK(hipStreamSynchronize(s->stream));  // tau is a host temporary
+        s->tau = d;
+    }
+    const double t = s->sdf_src.t0;  // the scene time survives a change of source
+    s->sdf_src = sdfnmpc_scene_sdf_opts{scene, scene_of, max_df, t, predict ? s->tau : nullptr};
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_solver_set_scene_time(sdfnmpc_solver* s, double t) {
+    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
+    if (!std::isfinite(t)) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_scene_time: the time must be finite");
+    s->sdf_src.t0 = t;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_solver_rollout_scene_sdf(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
+                                                const sdfnmpc_pose_refresh_args* pose, int phase, double t0, double dt) {
+    if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_scene_sdf");
+    if (!s->sdf_src.scene)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: no scene source set (sdfnmpc_solver_set_sdf_scene)");
+    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
+    if (phase < 0) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: phase must be >= 0");
+    sdfn::PlantArgs pa{};
+    sdfnmpc_ref_args ra{};
+    if (int rc = rollout_args(s, a, pa, ra)) return rc;
+    // the pose refresh: the pose block, and what sdfnmpc_pack_refs (mode -2) would refuse
+    sdfn::ScenePoseArgs spa{};
+    sdfnmpc_ref_opts po{};
+    sdfnmpc_ref_args pra{};
+    if (pose) {
+        if (pose->every < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: pose->every must be >= 1");
+        if (!pose->W_p_Bo || !pose->W_R_Bo || !pose->W_p_C || !pose->W_R_C)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: the pose refresh needs its workspaces");
+        if (int rc = sdfnmpc_scene_pose_args_(pose->B_p_C, pose->B_R_C, s->B, s->x0, pose->W_p_Bo, pose->W_R_Bo,
+                                              pose->W_p_C, pose->W_R_C, &spa))
+            return rc;
+        po.mode = -2;
+        for (int i = 0; i < 3; ++i) po.B_p_C[i] = pose->B_p_C[i];
+        for (int i = 0; i < 9; ++i) po.B_R_C[i] = pose->B_R_C[i];
+        pra.B = s->B; pra.N = s->N; pra.np = s->np; pra.ny = s->ny; pra.nyN = s->nyN;
+        pra.W_p_Bo = pose->W_p_Bo; pra.W_R_Bo = pose->W_R_Bo; pra.p = s->p;
+    }
+    pa.K = a->steps;
+    pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
+    pa.pts_log = a->pts_log;
+    pa.status = s->status; pa.iters = s->iters;
+    pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
+    SolverDevice sd(s->device);
+    for (int k = 0; k < a->steps; ++k) {
+        // the scene's time at step k, the product rounded on its own as in sdfnmpc_solver_rollout_perceive_at
+        volatile double steps_dt = (double)(phase + k) * dt;
+        s->sdf_src.t0 = t0 + steps_dt;
+        if (pose && (k + phase) % pose->every == 0) {  // the camera pose the FOV rows read, from the current state
+            if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
+            if (int rc = sdfnmpc_pack_refs(s->ctx, &po, &pra)) return rc;
         }
         if (a->ref)
             if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;

@@ -22,6 +22,8 @@ World frame z up; camera frame x forward, y left, z up, the pixel grid of ``ColC
 """
 from __future__ import annotations
 
+import weakref
+
 import numpy as np
 
 from . import _lib
@@ -84,6 +86,7 @@ class Scene:
                 flat.append((_lib.PRIM_KINDS.get(kind, kind if isinstance(kind, int) else -1), vals))
                 motion.append(mo[0] if mo else None)
         self.ctx, self.S = ctx, len(scenes)
+        self._sdf_users = weakref.WeakSet()  # controllers whose SDF source this scene is (Nmpc.set_sdf_scene)
         # plain primitives only: the call a scene has always made
         self.h = _lib.scene_create(ctx, [len(s) for s in scenes], flat,
                                    motion if any(m is not None for m in motion) else None)
@@ -192,6 +195,9 @@ class Scene:
 
     def close(self):
         if getattr(self, "h", None):
+            for n in list(getattr(self, "_sdf_users", ())):  # a solver keeps the handle: back to the network first
+                if n._sdf_scene is self and n.ocp.parts and n.ocp.parts[0].solver.h:
+                    n.set_sdf_scene(None)
             _lib.load().sdfnmpc_scene_free(self.h)
             self.h = None
 
