@@ -59,6 +59,11 @@
  *                                      network's epilogue writes as the sdf row of h / J_h (gen_model.py:46-61),
  *                                      from the scene's exact distance; sdfnmpc_lin_args.sdf_scene, sdfnmpc_solver_
  *                                      set_sdf_scene and sdfnmpc_solver_rollout_scene_sdf carry it through the step
+ *   sdfnmpc_img_sdf_rows               DfComputer.get_df (utils/df_computer.py:152-221), the network's training target
+ *                                      (scripts/neural_nets/df_train.py:52,123,168), under the same epilogue at the
+ *                                      node positions of the batch: the field the camera image itself implies, in
+ *                                      the frame of the image; sdfnmpc_lin_args.sdf_image, sdfnmpc_solver_set_sdf_image
+ *                                      and sdfnmpc_solver_rollout_image_sdf carry it through the step
  *   sdfnmpc_morph / sdfnmpc_outlier_rm Dilate / Erode (and with them Open / Close) and RemoveCloseOutliers
  *                                      (utils/preprocessing.py:100-259), batched
  *   sdfnmpc_sensor_apply               ImageAugmenter's noise and erasing (utils/data.py:11-108) as a reproducible
@@ -77,7 +82,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 12
+#define SDFNMPC_ABI_VERSION 13
 
 enum {
     SDFNMPC_OK = 0,
@@ -101,6 +106,8 @@ typedef struct {
     double t0;                   /* finite: the scene's time at node 0 */
     const double* tau;           /* device [N+1] or NULL: node k sees the scene at t0 + tau[k]; NULL: every node at t0 */
 } sdfnmpc_scene_sdf_opts;
+/* A camera image as the source of the SDF row (sdfnmpc_img_sdf_rows, defined with the image ground truth below) */
+typedef struct sdfnmpc_img_sdf_opts sdfnmpc_img_sdf_opts;
 
 #define SDFNMPC_POLY_DEG_MAX 6 /* braking-distance polynomial: degree bound ... */
 #define SDFNMPC_POLY_MAX 84    /* ... and its coefficient count (deg + 3 choose 3) */
@@ -169,6 +176,11 @@ typedef struct {
                          exact distance of this scene (sdfnmpc_scene_sdf_rows on x, p, h, Jh): net may be NULL and no
                          network is evaluated; linearize, then the rows kernel, then the record pack, on the context
                          stream.  Refused together with no_sdf (SDFNMPC_E_ARG), and by sdfnmpc_step_create
+                         (SDFNMPC_E_UNSUPPORTED) */
+    const sdfnmpc_img_sdf_opts* sdf_image; /* NULL: the network.  Else the SDF row is the field of this camera image
+                         (sdfnmpc_img_sdf_rows on x, p, h, Jh), with the semantics of sdf_scene: net may be NULL;
+                         linearize, then the rows kernel, then the record pack, on the context stream, no fork.  Refused
+                         together with no_sdf and together with sdf_scene (SDFNMPC_E_ARG), and by sdfnmpc_step_create
                          (SDFNMPC_E_UNSUPPORTED) */
 } sdfnmpc_lin_args;
 
@@ -470,6 +482,49 @@ int sdfnmpc_sdf_truth(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* opts, float min_
                       const float* dist, const int* orig_idx, int G, const float* img, int n_img, int H, int W,
                       const float* points, const int* p_to_i, long long n, float* sdf, float* grad, int* vox_idx);
 
+/* ---- the camera image's own field as the controller's SDF (csrc/df_truth.hip: img_sdf_rows_kernel) ----
+ * The network's training target is DfComputer.get_df(img, points) (df_train.py:52,123,168, signed_df = True): the
+ * distance and gradient the camera image itself implies -- limited to what the camera saw, quantised by the voxel
+ * grid, in the frame of the image.  sdfnmpc_img_sdf_rows evaluates that field at the node positions of a batch and
+ * writes what the network kernels' epilogue writes (gen_model.py:46-61): a controller flying on its own labels, the
+ * perfect network with the learned one's partial observability and image staleness and no approximation error.
+ * One 256-lane workgroup per node row r = b (N+1) + k:
+ *   flag = p[r][0];  Co_p_B = W_R_Co^T (x[r][0:3] - W_p_Co) in fp64 from the row's own parameters (W_p_Co = p[r][1:4],
+ *   W_R_Co = p[r][4:13] row-major), the network kernels' statements, rounded to fp32 (stored into pts[r], device float32
+ *   [B][N+1][3], when pts != NULL -- for every row);
+ *   (df, g) = the field at that point against image b (img_of[b] when img_of != NULL; the entries are the caller's to
+ *   keep in range): is_signed -- exactly sdfnmpc_sdf_truth (sign from the collision test in mode extrapolate with safe
+ *   ball 0, the distance-sorted voxel scan with its early stop, ties on the original voxel index, clamp to [min_df,
+ *   max_df] with a zero gradient where saturated); else exactly sdfnmpc_udf's scan of `pooled` (the virtual wall at
+ *   dmax, clamp to [0, max_df]).  Bitwise what those two return for the same fp32 point and image;
+ *   h[r][2] = flag df + (1 - flag) max_df,  Jh[r][j][2] = flag ((R[j][0] g0 + R[j][1] g1) + R[j][2] g2) for j < 3 with
+ *   R = W_R_Co, in that association, 0 for j = 3..9 -- fp64 on the widened fp32 values, no fused multiply-add.
+ * Where flag == 0 exactly the scan is skipped: h[r][2] = max_df, Jh[r][.][2] = 0 (what the epilogue gives, the field
+ * being finite).  Columns 0 and 1 of h and Jh are not touched; a row does not depend on its place in the batch.
+ * "img_sdf_rows" in sdfnmpc_ctx_kernel_stats.  x [B][N+1][10], p [B][N+1][np], h [B][N+1][3], Jh [B][N+1][10][3] device
+ * float64.  Asynchronous on the context stream; B == 0 is a no-op.  SDFNMPC_E_ARG (nothing is launched, outputs
+ * untouched): NULL arguments (pts may be NULL), B < 0, N < 1, np < 17, non-positive dmax / hfov / vfov, H or W < 1, a
+ * non-finite or non-positive max_df, min_df >= max_df, NULL images; signed without grid / dist or with G < 1; unsigned
+ * with an H or W that is not a multiple of 5 or without pooled. */
+struct sdfnmpc_img_sdf_opts {
+    sdfnmpc_img_opts img;      /* the sensor */
+    int H, W;                  /* image size */
+    const float* images;       /* device [n_img][H][W] float32, normalised by dmax */
+    const int* img_of;         /* device [B] int32 or NULL: instance b reads image b */
+    int is_signed;             /* 1: get_sdf over the voxel grid; 0: get_udf over the pooled image */
+    float min_df, max_df;      /* the clamps (DfComputer: -0.3 and 1) */
+    const float* grid;         /* signed: device [G][3], [G], [G] as sdfnmpc_sdf_truth takes them (orig_idx NULL: */
+    const float* dist;         /*   any order, full scan; else sorted by dist with the original indices) */
+    const int* orig_idx;
+    int G;
+    const float* pooled;       /* unsigned: device [n_img][H/5][W/5], the 5x5 min-pool of images (sdfnmpc_img_sdf_pool) */
+};
+int sdfnmpc_img_sdf_rows(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* opts, int B, int N, int np, const double* x,
+                         const double* p, double* h, double* Jh, float* pts);
+/* The zero-skipping 5x5 min-pool sdfnmpc_udf runs in front of its scan, of opts->images [n_img] into opts->pooled
+ * ("minpool5" in the kernel stats).  SDFNMPC_E_ARG: NULL arguments, n_img < 0, H or W not a positive multiple of 5. */
+int sdfnmpc_img_sdf_pool(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* opts, int n_img);
+
 /* ---- device memory on a context (inputs of the device-side setters without a tensor library) ----
  * memcpy kind: 1 host -> device, 2 device -> host, 3 device -> device; ordered on the context stream,
  * synchronous (returns when the copy has completed). */
@@ -737,6 +792,13 @@ typedef struct {
 int sdfnmpc_solver_rollout_scene_sdf(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
                                      const sdfnmpc_pose_refresh_args* pose, int phase, double t0, double dt);
 
+/* The solver's SDF source, an image: opts != NULL -- every later step evaluates sdfnmpc_img_sdf_rows instead of the
+ * network (sdfnmpc_lin_args.sdf_image) with the camera pose that is in p.  NULL returns to the network.  Setting either
+ * source (scene or image) replaces the other.  The solver copies the option block but keeps its pointers, not what they
+ * point to: images, img_of, grid and pooled stay the caller's and must stay alive while they are the source.
+ * SDFNMPC_E_ARG: no row or cost of the solver's constraint set reads the SDF, what sdfnmpc_img_sdf_rows refuses. */
+int sdfnmpc_solver_set_sdf_image(sdfnmpc_solver* s, const sdfnmpc_img_sdf_opts* opts);
+
 /* ---- image morphology (csrc/morph.hip) ----
  * The reference's Dilate / Erode (utils/preprocessing.py:100-199) on images in / out [B][H][W] (device float32, in !=
  * out) with a structuring element kernel [k_h][k_w] (host bytes, row-major; a tap is included where the byte is not
@@ -811,6 +873,21 @@ int sdfnmpc_sensor_apply(sdfnmpc_ctx* ctx, const sdfnmpc_sensor_opts* opts, int 
 int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
                                            const sdfnmpc_perceive_args* perc, double t0, double dt,
                                            const sdfnmpc_sensor_opts* sensor, float* scratch);
+
+/* sdfnmpc_solver_rollout for a solver with an image source.  With perc != NULL (scene, scene_of, img, h, w, extrinsics,
+ * scale, every, phase and the four pose workspaces are read; no encoder: vae, vae_opts, images and the latents are
+ * ignored), before step k with (k + perc->phase) % perc->every == 0 it enqueues, in this order: (1) sdfnmpc_scene_pose
+ * from the solver's x0 field; (2) sdfnmpc_scene_render_at of the normalised image (perc->scale = 1 / dmax, the scale
+ * ColChecker takes) into the source's images, at t0 + (double)(phase + k) * dt formed as sdfnmpc_solver_rollout_perceive_at forms
+ * it; (3) with sensor != NULL sdfnmpc_sensor_apply as frame phase + k (its vmax and min_range in normalised units);
+ * (4) in unsigned mode sdfnmpc_img_sdf_pool; (5) sdfnmpc_pack_refs in mode -2 (the pose columns of p).  Then the step's
+ * sequence of sdfnmpc_solver_rollout.  perc == NULL keeps the image and the pose as they are set.  A plain launch
+ * sequence.  SDFNMPC_E_ARG, all before the first launch: what the other rollouts refuse, no image source set on the
+ * solver, a render size other than the source's H x W, a source that maps instances to images (img_of) with perc, a
+ * sensor without perc. */
+int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
+                                     const sdfnmpc_perceive_args* perc, double t0, double dt,
+                                     const sdfnmpc_sensor_opts* sensor, float* scratch);
 
 /* ---- shooting grid (host, bit-exact numpy.linspace/diff semantics of ocp.py:21-27) ---- */
 int sdfnmpc_shooting_grid(int N, double T, int uniform, int nb_short_nodes, double dt_short, double* nodes,

@@ -43,6 +43,7 @@ SYMBOLS = [
     "sdfnmpc_morph", "sdfnmpc_outlier_rm", "sdfnmpc_sensor_apply", "sdfnmpc_solver_rollout_perceive_sensor",
     "sdfnmpc_scene_sdf_rows", "sdfnmpc_solver_set_sdf_scene", "sdfnmpc_solver_set_scene_time",
     "sdfnmpc_solver_rollout_scene_sdf",
+    "sdfnmpc_img_sdf_rows", "sdfnmpc_img_sdf_pool", "sdfnmpc_solver_set_sdf_image", "sdfnmpc_solver_rollout_image_sdf",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -78,10 +79,22 @@ class SceneSdfOptsC(C.Structure):
                 ("tau", C.c_void_p)]
 
 
+class ImgOptsC(C.Structure):
+    _fields_ = [("dmax", C.c_float), ("hfov", C.c_float), ("vfov", C.c_float), ("is_depth", C.c_int),
+                ("is_spherical", C.c_int)]
+
+
+class ImgSdfOptsC(C.Structure):
+    _fields_ = [("img", ImgOptsC), ("H", C.c_int), ("W", C.c_int), ("images", C.c_void_p), ("img_of", C.c_void_p),
+                ("is_signed", C.c_int), ("min_df", C.c_float), ("max_df", C.c_float), ("grid", C.c_void_p),
+                ("dist", C.c_void_p), ("orig_idx", C.c_void_p), ("G", C.c_int), ("pooled", C.c_void_p)]
+
+
 class LinArgsC(C.Structure):
     _fields_ = [("B", C.c_int), ("N", C.c_int), ("np", C.c_int), ("latent_mode", C.c_int)] + [
         (n, C.c_void_p) for n in LIN_PTRS] + [("nyN", C.c_int), ("no_sdf", C.c_int), ("hE", C.c_void_p),
-                                             ("JhE", C.c_void_p), ("sdf_scene", C.POINTER(SceneSdfOptsC))]
+                                             ("JhE", C.c_void_p), ("sdf_scene", C.POINTER(SceneSdfOptsC)),
+                                             ("sdf_image", C.POINTER(ImgSdfOptsC))]
 
 
 class QpOptsC(C.Structure):
@@ -117,11 +130,6 @@ QP_OUT = ("dx", "du", "slack", "status", "iters", "res")
 class VaeOptsC(C.Structure):
     _fields_ = [("B", C.c_int), ("in_h", C.c_int), ("in_w", C.c_int), ("dtype", C.c_int), ("clip", C.c_float),
                 ("yz", C.c_void_p)]
-
-
-class ImgOptsC(C.Structure):
-    _fields_ = [("dmax", C.c_float), ("hfov", C.c_float), ("vfov", C.c_float), ("is_depth", C.c_int),
-                ("is_spherical", C.c_int)]
 
 
 class SolverOptsC(C.Structure):
@@ -276,11 +284,15 @@ def load():
         "sdfnmpc_solver_set_sdf_scene": (i, [vp, vp, vp, d, i]),
         "sdfnmpc_solver_set_scene_time": (i, [vp, d]),
         "sdfnmpc_solver_rollout_scene_sdf": (i, [vp, P(RolloutArgsC), P(PoseRefreshArgsC), i, d, d]),
+        "sdfnmpc_img_sdf_rows": (i, [vp, P(ImgSdfOptsC), i, i, i, vp, vp, vp, vp, vp]),
+        "sdfnmpc_img_sdf_pool": (i, [vp, P(ImgSdfOptsC), i]),
+        "sdfnmpc_solver_set_sdf_image": (i, [vp, P(ImgSdfOptsC)]),
+        "sdfnmpc_solver_rollout_image_sdf": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d, P(SensorOptsC), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 12:
+    if lib.sdfnmpc_abi_version() != 13:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -507,21 +519,49 @@ def scene_sdf_opts(scene_h, max_df: float, scene_of=None, t0: float = 0.0, tau=N
                          float(t0), _ptr(tau))
 
 
-def lin_args(B: int, N: int, np_: int, bufs: dict, latent_mode=0, nyN=4, no_sdf=False, sdf_scene=None) -> LinArgsC:
-    """sdf_scene: a SceneSdfOptsC (scene_sdf_opts) -- the scene's exact distance as the SDF row, no network."""
+def img_sdf_opts(opts: "ImgOptsC", images, signed=True, min_df=-0.3, max_df=1.0, grid=None, dist=None, orig_idx=None,
+                 pooled=None, img_of=None) -> ImgSdfOptsC:
+    """sdfnmpc_img_sdf_opts: images device float32 [n_img][H][W] (normalised) as the source of the SDF row; signed: the
+    voxel grid [G][3] / dist [G] / orig_idx [G] or None as sdf_truth takes them; unsigned: pooled device float32
+    [n_img][H/5][W/5] (img_sdf_pool fills it); img_of device int32 [B] or None.  The caller keeps what it names alive."""
+    _, H, W = (int(v) for v in images.shape)
+    return ImgSdfOptsC(opts, H, W, _ptr(images), _ptr(img_of), int(bool(signed)), float(min_df), float(max_df),
+                       _ptr(grid), _ptr(dist), _ptr(orig_idx), 0 if dist is None else int(dist.shape[0]), _ptr(pooled))
+
+
+def img_sdf_rows(ctx: "Context", opts: ImgSdfOptsC, B: int, N: int, np_: int, x, p, h, Jh, pts=None):
+    """Enqueue sdfnmpc_img_sdf_rows: the field of the camera image as the SDF row of h [B][N+1][3] / Jh [B][N+1][10][3]
+    (column 2) at the positions x [B][N+1][10][:3] seen through the pose in p [B][N+1][np]; pts: device float32
+    [B][N+1][3] or None, the camera-frame points."""
+    _check(load().sdfnmpc_img_sdf_rows(ctx.h, C.byref(opts), int(B), int(N), int(np_), _ptr(x), _ptr(p), _ptr(h),
+                                       _ptr(Jh), _ptr(pts)))
+
+
+def img_sdf_pool(ctx: "Context", opts: ImgSdfOptsC, n_img: int):
+    """Enqueue sdfnmpc_img_sdf_pool: the 5x5 min-pool of opts.images [n_img] into opts.pooled."""
+    _check(load().sdfnmpc_img_sdf_pool(ctx.h, C.byref(opts), int(n_img)))
+
+
+def lin_args(B: int, N: int, np_: int, bufs: dict, latent_mode=0, nyN=4, no_sdf=False, sdf_scene=None,
+             sdf_image=None) -> LinArgsC:
+    """sdf_scene: a SceneSdfOptsC (scene_sdf_opts) -- the scene's exact distance as the SDF row, no network;
+    sdf_image: an ImgSdfOptsC (img_sdf_opts) -- the camera image's own field."""
     a = LinArgsC(B, N, np_, latent_mode, *[_ptr(bufs.get(k)) for k in LIN_PTRS], int(nyN), int(bool(no_sdf)),
                  _ptr(bufs.get("hE")), _ptr(bufs.get("JhE")))
     if sdf_scene is not None:
         a.sdf_scene = C.pointer(sdf_scene)
         a._keep = sdf_scene
+    if sdf_image is not None:
+        a.sdf_image = C.pointer(sdf_image)
+        a._keep_img = sdf_image
     return a
 
 
 def linearize(ctx: Context, net, model: QuadModelC, B: int, N: int, np_: int, bufs: dict, latent_mode=0, nyN=4,
-              no_sdf=False, sdf_scene=None):
+              no_sdf=False, sdf_scene=None, sdf_image=None):
     """Enqueue the batched preparation phase.  bufs: device tensors named as sdfnmpc_lin_args (net may be
-    None with no_sdf or sdf_scene)."""
-    a = lin_args(B, N, np_, bufs, latent_mode, nyN, no_sdf, sdf_scene)
+    None with no_sdf, sdf_scene or sdf_image)."""
+    a = lin_args(B, N, np_, bufs, latent_mode, nyN, no_sdf, sdf_scene, sdf_image)
     _check(load().sdfnmpc_linearize(ctx.h, None if net is None else net.h, C.byref(model), C.byref(a)))
 
 
@@ -548,10 +588,10 @@ def qp_solve(ctx: Context, opts: QpOptsC, B: int, N: int, bufs: dict):
 
 
 def rti_prepare(ctx: Context, net, model: QuadModelC, opts: QpOptsC, B: int, N: int, np_: int, bufs: dict,
-                latent_mode=0, no_sdf=False, sdf_scene=None):
+                latent_mode=0, no_sdf=False, sdf_scene=None, sdf_image=None):
     """Enqueue the RTI preparation phase acados-style: linearisation + the QP's stage records (everything
     but x0).  bufs: device tensors named as sdfnmpc_lin_args and sdfnmpc_qp_args."""
-    la = lin_args(B, N, np_, bufs, latent_mode, opts.nyN, no_sdf, sdf_scene)
+    la = lin_args(B, N, np_, bufs, latent_mode, opts.nyN, no_sdf, sdf_scene, sdf_image)
     qa = QpArgsC(B, N, *[_ptr(bufs.get(k)) for k in QP_IN + QP_OUT])
     _check(load().sdfnmpc_rti_prepare(ctx.h, None if net is None else net.h, C.byref(model), C.byref(la),
                                       C.byref(opts), C.byref(qa)))
@@ -577,11 +617,11 @@ class RtiStep:
     must stay alive and at the same addresses."""
 
     def __init__(self, ctx: Context, net, model: QuadModelC, opts: QpOptsC, B: int, N: int, np_: int, bufs: dict,
-                 u0=None, latent_mode=0, no_sdf=False, graph=False, sdf_scene=None):
+                 u0=None, latent_mode=0, no_sdf=False, graph=False, sdf_scene=None, sdf_image=None):
         self._lib = load()
         self._ctx, self._net = ctx.h, None if net is None else net.h
         self._model, self._opts, self._B, self._N = model, opts, B, N
-        self._la = lin_args(B, N, np_, bufs, latent_mode, opts.nyN, no_sdf, sdf_scene)
+        self._la = lin_args(B, N, np_, bufs, latent_mode, opts.nyN, no_sdf, sdf_scene, sdf_image)
         self._qa = QpArgsC(B, N, *[_ptr(bufs.get(k)) for k in QP_IN + QP_OUT])
         self._apply = (_ptr(bufs["x"]), _ptr(bufs["u"]), _ptr(bufs["dx"]), _ptr(bufs["du"]), _ptr(u0),
                        _ptr(bufs.get("status")))
@@ -1038,6 +1078,7 @@ class Solver:
         scene_h None returns to the network.  scene_of: a device int32 [B] array, kept alive here."""
         _check(load().sdfnmpc_solver_set_sdf_scene(self.h, scene_h, _ptr(scene_of), float(max_df), int(bool(predict))))
         self._sdf_scene_keep = (scene_h, scene_of)
+        self._sdf_image_keep = None  # setting either source replaces the other
 
     def set_scene_time(self, t: float):
         _check(load().sdfnmpc_solver_set_scene_time(self.h, float(t)))
@@ -1054,6 +1095,29 @@ class Solver:
         self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, pose)
         _check(load().sdfnmpc_solver_rollout_scene_sdf(self.h, C.byref(a), None if pose is None else C.byref(pose),
                                                        int(phase), float(t0), float(dt)))
+
+    def set_sdf_image(self, opts: "ImgSdfOptsC" = None, keep=()):
+        """sdfnmpc_solver_set_sdf_image: the field of a camera image instead of the network from the next step on; None
+        returns to the network.  keep: the device arrays the options name, kept alive here while they are the source."""
+        _check(load().sdfnmpc_solver_set_sdf_image(self.h, None if opts is None else C.byref(opts)))
+        self._sdf_image_keep = (opts, keep)
+        self._sdf_scene_keep = None
+
+    def rollout_image_sdf(self, steps: int, plant: PlantOpts, x_log, u_log, perceive: "PerceiveArgsC" = None,
+                          t0: float = 0.0, dt: float = 0.0, sensor=None, status_log=None, iters_log=None, pts_log=None,
+                          shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0):
+        """Enqueue sdfnmpc_solver_rollout_image_sdf: `rollout` for a solver with an image source -- with perceive (a
+        PerceiveArgsC without an encoder) a new normalised image rendered into the source, degraded by sensor
+        ((SensorOptsC, scratch), normalised units), pooled in unsigned mode, and the camera pose of p refreshed, before
+        every `every`-th step."""
+        a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
+                         _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
+                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
+        self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, perceive,
+                              sensor)
+        _check(load().sdfnmpc_solver_rollout_image_sdf(
+            self.h, C.byref(a), None if perceive is None else C.byref(perceive), float(t0), float(dt),
+            None if sensor is None else C.byref(sensor[0]), None if sensor is None else _ptr(sensor[1])))
 
     def wait(self):
         _check(load().sdfnmpc_solver_wait(self.h, self.u0.ctypes.data, self.status.ctypes.data, self.iters.ctypes.data))

@@ -65,6 +65,7 @@ class Nmpc:
         self.cmd_TRPYr_min = [0, -lim.roll, -lim.pitch, -lim.wz]
         self.cmd_TRPYr_max = [lim.gamma, lim.roll, lim.pitch, lim.wz]
         self._sdf_scene = None  # the scene whose exact distance replaces the network (set_sdf_scene)
+        self._sdf_image = None  # or the image source: its option block and the device arrays it names (set_sdf_image)
         self.reset()
 
     # ---- state of the controller (host arrays, batch-leading; B == 1 keeps the reference's shapes)
@@ -164,7 +165,7 @@ class Nmpc:
             solver.set_sdf_scene(None)
             if self._sdf_scene is not None:
                 self._sdf_scene._sdf_users.discard(self)
-            self._sdf_scene = None
+            self._sdf_scene = self._sdf_image = None
             return
         if scene.ctx is not self.ocp.ctx:
             raise ValueError("set_sdf_scene(): the scene must be built on the controller's context (ctx=nmpc.ocp.ctx)")
@@ -178,7 +179,91 @@ class Nmpc:
         if self._sdf_scene is not None:
             self._sdf_scene._sdf_users.discard(self)
         self._sdf_scene = scene  # kept alive here; Scene.close() takes itself out of its users first
+        self._sdf_image = None   # the two sources replace each other
         scene._sdf_users.add(self)
+
+    # ---- the camera image's own field as the SDF (csrc/df_truth.hip: img_sdf_rows_kernel)
+    def set_sdf_image(self, imgs, signed=True, max_df=None, img_of=None):
+        """The SDF row of the constraints (and the sdf cost) from the distance field the camera image itself implies --
+        ``DfComputer.get_df``, the network's training target -- instead of the network: the perfect network, with the
+        learned one's partial observability and image staleness and no approximation error.  imgs: [B, H, W] (or [H, W]
+        for one instance) float32 range images normalised by sensor.dmax, host or device (copied: the controller owns
+        its image buffer, the pooled buffer of the unsigned mode and the device voxel grid of the signed one, and keeps
+        them alive while they are the source).  signed: ``get_sdf`` over the voxel grid, clamped to [-0.3, max_df];
+        else ``get_udf`` over the 5x5 min-pooled image, clamped to [0, max_df] (H and W multiples of 5).  max_df
+        defaults to model.max_df.  img_of: int [B], the image of each instance (imgs then holds any number of images;
+        a rollout that re-images needs one per instance, img_of None).  The camera pose is whatever ``set_latent`` /
+        ``set_pose_device`` put in p.  ``solve`` and ``rollout`` use the source from the next call on; None restores the
+        network.  ``set_sdf_scene`` and ``set_sdf_image`` replace each other.  ValueError, before anything is enqueued:
+        a batch split over several devices, a model whose flags read no SDF, a wrong image count, unsigned with H or W
+        not a multiple of 5."""
+        from . import _lib
+        if len(self.ocp.parts) != 1:
+            raise ValueError("set_sdf_image(): the batch is split over several devices; sharded batches are not built")
+        solver, ctx, Bn = self.ocp.parts[0].solver, self.ocp.ctx, max(self.B, 1)
+        if imgs is None:
+            solver.set_sdf_image(None)
+            if self._sdf_scene is not None:
+                self._sdf_scene._sdf_users.discard(self)
+            self._sdf_scene = self._sdf_image = None
+            return
+        if not self.model.need_sdf:
+            raise ValueError("set_sdf_image(): no constraint row or cost of this model's flags reads the SDF")
+        md = float(self.model.max_df if max_df is None else max_df)
+        if not (np.isfinite(md) and md > 0.0):
+            raise ValueError(f"max_df {max_df}: positive and finite")
+        on_dev = hasattr(imgs, "data_ptr")
+        if on_dev and np.dtype(str(imgs.dtype).replace("torch.", "")) != np.float32:
+            raise TypeError(f"device images must be float32, got {imgs.dtype}")
+        shape = tuple(int(v) for v in imgs.shape) if on_dev else np.shape(imgs)
+        if len(shape) == 2:
+            shape = (1,) + tuple(shape)
+        if len(shape) != 3:
+            raise ValueError("input image must have size [B, H, W] or [H, W]")
+        io = None
+        if img_of is not None:
+            io = np.ascontiguousarray(np.asarray(img_of).reshape(-1), dtype=np.int32)
+            if io.size != Bn or io.min() < 0 or io.max() >= shape[0]:
+                raise ValueError(f"img_of: {Bn} entries in [0, {shape[0]})")
+        elif shape[0] != Bn:
+            raise ValueError(f"expected {Bn} images, got {shape[0]}")
+        if not signed and (shape[1] % 5 or shape[2] % 5):
+            raise ValueError(f"unsigned mode: H and W must be multiples of 5, got {shape[1]} x {shape[2]}")
+        if on_dev:  # a copy on the device, once the producer has finished
+            dimg = _lib.DeviceArray(ctx, shape, np.float32)
+            _lib._check(_lib.load().sdfnmpc_memcpy(ctx.h, dimg.data_ptr(), _lib.sync_producer(imgs).data_ptr(), dimg.nbytes, 3))
+        else:
+            dimg = _lib.DeviceArray.from_numpy(ctx, np.asarray(imgs, dtype=np.float32).reshape(shape))
+        keep = {"images": dimg, "img_of": None if io is None else _lib.DeviceArray.from_numpy(ctx, io)}
+        sn = self.cfg.sensor
+        io_c = _lib.img_opts(sn.dmax, sn.hfov, sn.vfov, sn.is_depth, sn.is_spherical)
+        if signed:
+            keep.update(self._image_grid())
+            o = _lib.img_sdf_opts(io_c, dimg, True, -0.3, md, keep["grid"], keep["dist"], keep["orig_idx"],
+                                  img_of=keep["img_of"])
+        else:
+            keep["pooled"] = _lib.DeviceArray(ctx, (shape[0], shape[1] // 5, shape[2] // 5), np.float32)
+            o = _lib.img_sdf_opts(io_c, dimg, False, -0.3, md, pooled=keep["pooled"], img_of=keep["img_of"])
+            _lib.img_sdf_pool(ctx, o, shape[0])
+        solver.set_sdf_image(o, keep)
+        if self._sdf_scene is not None:
+            self._sdf_scene._sdf_users.discard(self)
+        self._sdf_scene = None
+        self._sdf_image = {"opts": o, "shape": shape, "signed": bool(signed), **keep}
+
+    def _image_grid(self):
+        """The distance-sorted voxel grid ``DfComputer`` builds (its ``generate_dist_grid``), on the controller's
+        device: built once per controller."""
+        from . import _lib
+        g = getattr(self, "_img_grid", None)
+        if g is None:
+            from .df_computer import DfComputer
+            sn, ctx = self.cfg.sensor, self.ocp.ctx
+            grid, dist, orig = DfComputer(True, sn.dmax, sn.hfov, sn.vfov, 1, sn.is_depth, sn.is_spherical, device=ctx)._sorted
+            g = self._img_grid = {"grid": _lib.DeviceArray.from_numpy(ctx, grid.numpy(), dtype=np.float32),
+                                  "dist": _lib.DeviceArray.from_numpy(ctx, dist.numpy(), dtype=np.float32),
+                                  "orig_idx": _lib.DeviceArray.from_numpy(ctx, orig.numpy(), dtype=np.int32)}
+        return g
 
     def set_scene_time(self, t):
         """The time a scene source is seen at by the next ``solve`` (0 at creation)."""
@@ -250,6 +335,15 @@ class Nmpc:
         ``set_img``; ``encode_to``.  ``keep_img`` then returns the degraded image the encoder saw; ``clearance`` stays
         the exact distance to the scene -- the clearance kept under a degraded camera.
 
+        With an image source (``set_sdf_image``) ``scene`` needs no ``vae`` (giving one is a ValueError): before every
+        ``perceive_every``-th step the scene is rendered from the plant state as a normalised image of the source's
+        own shape (``img_shape``, when given, must equal it) into the source's buffer, degraded by ``sensor`` as frame
+        ``perceive_phase + k`` (normalised units), min-pooled in the unsigned mode, and the camera pose goes into p
+        (sdfnmpc_solver_rollout_image_sdf): the loop ``render_from_state(normalized=True)``; ``sensor.apply``;
+        ``set_sdf_image``; ``set_pose_device``.  ``keep_img`` returns the image the source last held; ``clearance``
+        and ``t`` are measured against the scene as above.  Without ``scene`` the image and the pose stay as set, and
+        ``imgs`` labelling works as without a source.
+
         Returns a ``Rollout`` of numpy arrays, batch-leading also for one instance: x [B, K+1, 10] (row 0 the
         start), u [B, K, 4], status / iters [B, K]; with imgs also col [B, K+1] bool and pts [B, K+1, 3] float32.
         Afterwards ``self.x0`` is the final plant state and ``ocp.u`` / ``ocp.status`` / ``ocp.iters`` are the last
@@ -273,6 +367,28 @@ class Nmpc:
                 raise ValueError("rollout(): scene, vae and sensor exclude a scene source (set_sdf_scene): the "
                                  "controller reads the scene's exact distance, not an image")
             _check_schedule(perceive_every, perceive_phase, scene_t0, scene_dt)
+        elif self._sdf_image is not None:  # an image source: re-imaged from ``scene`` inside the loop, no encoder
+            isrc = self._sdf_image
+            if vae is not None:
+                raise ValueError("rollout(): vae excludes an image source (set_sdf_image): the controller reads the "
+                                 "image's own distance field, not a latent")
+            if img_shape is not None and tuple(int(v) for v in img_shape) != isrc["shape"][1:]:
+                raise ValueError(f"rollout(): img_shape {tuple(img_shape)} is not the image source's {isrc['shape'][1:]}")
+            if scene is None:
+                if sensor is not None:
+                    raise ValueError("rollout(): sensor degrades a scene's images; give scene too")
+            else:
+                if imgs is not None:
+                    raise ValueError("rollout(): scene and imgs exclude each other (the image changes inside the loop)")
+                if scene.ctx is not ctx:
+                    raise ValueError("rollout(): the scene must be built on the controller's context (ctx=nmpc.ocp.ctx)")
+                if isrc["img_of"] is not None:
+                    raise ValueError("rollout(): re-imaging renders one image per instance; the source maps instances to "
+                                     "images (img_of)")
+                _check_schedule(perceive_every, perceive_phase, scene_t0, scene_dt)
+                scene._batch(Bn)
+                if sensor is not None and sensor.ctx is not ctx:
+                    raise ValueError("rollout(): the SensorModel must be built on the controller's context (ctx=nmpc.ocp.ctx)")
         elif scene is None:
             if vae is not None:
                 raise ValueError("rollout(): vae is the encoder of a scene's images; give scene too")
@@ -310,7 +426,18 @@ class Nmpc:
         if plant is None:
             plant = _lib.plant_opts(self.cfg, dt=float(self.ocp.dt[0]))
         perc = None
-        if scene is not None:
+        isrc = self._sdf_image if src is None else None
+        if isrc is not None:
+            if scene is not None:  # pose, render (normalised, into the source), sensor, pool, pose columns: no encoder
+                ih, iw = isrc["shape"][1:]
+                ws = _pose_workspaces(ctx, Bn)
+                perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(self.cfg), ih, iw,
+                                          scene.scale(self.cfg, normalized=True), *_extrinsics(self.cfg), None,
+                                          _lib.VaeOptsC(), int(perceive_every), int(perceive_phase), None, None, None,
+                                          *[ws[k].data_ptr() for k in POSE_WS])
+                perc._keep = ws
+                t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)
+        elif scene is not None:
             ih, iw = (int(v) for v in (img_shape if img_shape is not None else self.cfg.sensor.shape_imgs[-2:]))
             ws = dict(_pose_workspaces(ctx, Bn), images=_lib.DeviceArray(ctx, (Bn, ih, iw), np.float32))
             vo = _lib.VaeOptsC(Bn, ih, iw, 0, float(vae.opts.clip), _lib._ptr(vae.yz) if vae.depth2range else None)
@@ -343,6 +470,13 @@ class Nmpc:
             solver.rollout_scene_sdf(K, plant, pose=pose, phase=int(perceive_phase), t0=t0, dt=dts,
                                      shift=int(self.cfg.mpc.shift), **kw, **log)
             self._clean("pose")  # written on the device, as after set_pose_device
+        elif isrc is not None:
+            sn = None if sensor is None else sensor.opts(Bn, ih, iw, normalized=True)  # the source's images are normalised
+            clock = (t0, dts) if perc is not None else (0.0, 0.0)
+            solver.rollout_image_sdf(K, plant, perceive=perc, t0=clock[0], dt=clock[1], sensor=sn,
+                                     shift=int(self.cfg.mpc.shift), **kw, **log)
+            if perc is not None:
+                self._clean("pose")
         else:
             solver.rollout(K, plant, shift=int(self.cfg.mpc.shift), **kw, **log)
         u0 = solver.wait().copy()
@@ -357,8 +491,10 @@ class Nmpc:
             out.pts = log["pts_log"].numpy()
         if perc is not None or src is not None:  # against the rendered scene, or the source scene
             _log_clearance(out, scene if perc is not None else src, t0 + (int(perceive_phase) + np.arange(K + 1)) * dts)
-            if perc is not None and keep_img:
+            if perc is not None and keep_img and isrc is None:
                 out.img = ws["images"].numpy()
+        if isrc is not None and keep_img:  # the (normalised) image the source last held
+            out.img = isrc["images"].numpy()
         self.x0 = out.x[:, -1].copy() if self.B > 1 else out.x[0, -1].copy()
         ocp = self.ocp
         ocp.status, ocp.iters = solver.status.copy(), solver.iters.copy()

@@ -39,6 +39,17 @@ struct UdfArgs {
     int* pix_idx;       // [n] or nullptr
 };
 
+// udf_kernel / sdf_grid_kernel as the image field's rows kernel (x != nullptr): point pt is node row pt
+struct DfRowsArgs {
+    const double* x;    // [rows][10]
+    const double* p;    // [rows][np]
+    double* h;          // [rows][3]: column 2 is written
+    double* Jh;         // [rows][10][3]: column 2 is written
+    float* pts;         // [rows][3], == the kernel's im.points: written by the kernel, then read by its scan
+    const int* img_of;  // [B] or nullptr
+    int N1, np;
+};
+
 struct SdfGridArgs {
     DfImg im;
     float min_df, max_df;
@@ -51,6 +62,30 @@ struct SdfGridArgs {
     int* vox_idx;       // [n] or nullptr; -1 where no voxel counts
 };
 
+// launch_img_sdf_rows: the field of sdf_grid_kernel (is_signed) or udf_kernel at the node rows of a batch, as the SDF
+// row of h / J_h
+struct ImgSdfArgs {
+    const float* images;  // [n_img][H][W], normalised by dmax (signed)
+    const float* pooled;  // [n_img][H/5][W/5], the min-pooled images (unsigned)
+    const int* img_of;    // [B] or nullptr: instance b -> image b
+    int H, W;             // of the images (the pooled size is H / 5, W / 5)
+    float dmax, hfov, vfov;
+    int is_depth, is_spherical;
+    int is_signed;
+    float min_df, max_df;
+    const float* grid;    // signed: as SdfGridArgs
+    const float* dist;
+    const int* orig_idx;
+    int G;
+    long long rows;       // B (N+1)
+    int N1, np;           // nodes per instance, parameters per node
+    const double* x;      // [rows][10]: the world position is x[r][0:3]
+    const double* p;      // [rows][np]: flag p[r][0], W_p_Co p[r][1:4], W_R_Co p[r][4:13] row-major
+    double* h;            // [rows][3]: column 2 is written
+    double* Jh;           // [rows][10][3]: column 2 is written
+    float* pts;           // [rows][3]: the camera-frame point of every row (required at the launch)
+};
+
 constexpr int DF_BLOCK = 256;
 // LDS of udf_kernel: (cos, sin) or tan per pooled column and row
 inline size_t udf_lds_bytes(int h, int w) { return (size_t)2 * ((size_t)h + (size_t)w) * sizeof(float); }
@@ -60,5 +95,6 @@ hipError_t launch_colcheck(const ColcheckArgs& a, hipStream_t s);
 hipError_t launch_minpool5(const MinpoolArgs& a, hipStream_t s);
 hipError_t launch_udf(const UdfArgs& a, hipStream_t s);
 hipError_t launch_sdf_grid(const SdfGridArgs& a, hipStream_t s);
+hipError_t launch_img_sdf_rows(const ImgSdfArgs& a, hipStream_t s);
 
 }  // namespace sdfn

@@ -5,9 +5,13 @@
 //   minpool5_kernel   utils/df_computer.py:154-162       the zero-skipping 5x5 min-pool of get_udf
 //   udf_kernel        utils/df_computer.py:102-149,177-180  _kernel_pixel_wise_udf + the min / gradient
 //   sdf_grid_kernel   utils/df_computer.py:200-221       get_sdf, fused: no n x G buffer exists
+//   img_sdf_rows      gen_model.py:46-61 on df_computer.py:152-221: sdf_grid_kernel / udf_kernel in their rows mode, at
+//                     the node positions of a batch, written as the SDF row of h / J_h -- the controller flying
+//                     on the network's own training labels (DfComputer.get_df), no network
 //
 // fp32 throughout (Warp float32).  Reductions are (value, index) minima with ties to the lowest index,
 // in-wave by shuffles and across waves through LDS: no atomics, so results do not depend on scheduling.
+#include "cam_point.h"
 #include "df_kernels.h"
 
 #include <climits>
@@ -21,9 +25,14 @@ struct ImgCfg {
     int is_depth, is_spherical, H, W;
 };
 
-__device__ __forceinline__ ImgCfg img_cfg(const DfImg& im) {
+__device__ __forceinline__ ImgCfg img_cfg(float dmax, float hfov, float vfov, int is_depth, int is_spherical, int H,
+                                          int W) {
     // tan(hfov), tan(vfov): launch constants of collision_checker.py:83-84
-    return ImgCfg{im.dmax, im.hfov, im.vfov, tanf(im.hfov), tanf(im.vfov), im.is_depth, im.is_spherical, im.H, im.W};
+    return ImgCfg{dmax, hfov, vfov, tanf(hfov), tanf(vfov), is_depth, is_spherical, H, W};
+}
+
+__device__ __forceinline__ ImgCfg img_cfg(const DfImg& im) {
+    return img_cfg(im.dmax, im.hfov, im.vfov, im.is_depth, im.is_spherical, im.H, im.W);
 }
 
 __device__ __forceinline__ const float* img_of(const DfImg& im, long long j) {
@@ -147,7 +156,57 @@ __device__ __forceinline__ float udf_pix(const float* __restrict__ img, const Im
     return d_p;
 }
 
-__global__ __launch_bounds__(DF_BLOCK) void udf_kernel(UdfArgs a) {
+// gen_model.py:46-61 with the image's own field in the place of the network: h[r][2] = flag df + (1 - flag) max_df and
+// J_h[r][j][2] = flag (W_R_Co g)_j, df and the camera-frame gradient g widened from fp32.  fp64, no contraction: a host
+// restatement of these statements gives the same bits.
+__device__ __forceinline__ void img_sdf_epilogue(double flag, float df, float g0, float g1, float g2, const double* R,
+                                                 double max_df, double* h2, double* J) {
+#pragma clang fp contract(off)
+    const double d = (double)df, a0 = (double)g0, a1 = (double)g1, a2 = (double)g2;
+    *h2 = flag * d + (1.0 - flag) * max_df;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) J[j * 3] = flag * ((R[3 * j] * a0 + R[3 * j + 1] * a1) + R[3 * j + 2] * a2);
+#pragma unroll
+    for (int j = 3; j < 10; ++j) J[j * 3] = 0.0;
+}
+
+// The image field as the SDF row ("img_sdf_rows"; launch_img_sdf_rows) is udf_kernel / sdf_grid_kernel themselves with
+// r.x != nullptr: point pt is then node row pt = b (N+1) + k.  rows_prologue: thread 0 forms the row's camera-frame
+// point (cam_point, the network kernels' statements) and stores it where the scan reads its point from (a.im.points:
+// the caller's pts or a workspace); where the flag is 0 the row is written at once and the scan skipped (false is
+// returned, uniformly); else a barrier makes the point visible.  After the scan thread 0 writes img_sdf_epilogue
+// instead of (df, grad).  One kernel per field, so that the scan of a row is the very machine code that labels a point:
+// the same bits by construction, whatever the compiler fuses.
+__device__ __forceinline__ bool rows_prologue(const DfRowsArgs& r, long long pt, float max_df, double& flag) {
+    const double* pr = r.p + (size_t)pt * r.np;
+    flag = pr[0];
+    if (threadIdx.x == 0) {  // the point of every row, whatever its flag
+        const float4 P = cam_point(r.x + (size_t)pt * 10, pr);
+        float* w = r.pts + (size_t)pt * 3;  // == a.im.points + 3 pt
+        w[0] = P.x;
+        w[1] = P.y;
+        w[2] = P.z;
+    }
+    if (flag == 0.0) {  // uniform over the workgroup.  The field is always finite (clamped), so the epilogue would give
+        // 0 df + 1 max_df = max_df, the same bits, and flag (..) = a zero (of either sign)
+        if (threadIdx.x == 0) {
+            r.h[pt * 3 + 2] = (double)max_df;
+#pragma unroll
+            for (int j = 0; j < 10; ++j) r.Jh[pt * 30 + j * 3 + 2] = 0.0;
+        }
+        return false;
+    }
+    __syncthreads();  // thread 0's point is visible to the workgroup
+    return true;
+}
+
+// the image of row pt: instance b = pt / N1 reads image b, or img_of[b] (entries are the caller's to keep in range)
+__device__ __forceinline__ const float* rows_img(const DfImg& im, const DfRowsArgs& r, long long pt) {
+    const long long b = pt / r.N1;
+    return im.img + (size_t)(r.img_of ? (long long)r.img_of[b] : b) * im.H * im.W;
+}
+
+__global__ __launch_bounds__(DF_BLOCK) void udf_kernel(UdfArgs a, DfRowsArgs r) {
     extern __shared__ float tab[];  // col [2 w] | row [2 h]
     __shared__ float sd[DF_BLOCK / 64];
     __shared__ int si[DF_BLOCK / 64], sp[DF_BLOCK / 64];
@@ -171,9 +230,11 @@ __global__ __launch_bounds__(DF_BLOCK) void udf_kernel(UdfArgs a) {
     }
     __syncthreads();
     const long long pt = blockIdx.x;
+    double flag = 1.0;
+    if (r.x && !rows_prologue(r, pt, a.max_df, flag)) return;
     const float* p = a.im.points + (size_t)pt * 3;
     const float px = p[0], py = p[1], pz = p[2];
-    const float* img = img_of(a.im, pt);
+    const float* img = r.x ? rows_img(a.im, r, pt) : img_of(a.im, pt);
     const float d_bg = c.dmax - (c.is_depth ? px : sqrtf(px * px + py * py + pz * pz));  // :140-143
     float best = INFINITY;
     int bi = INT_MAX, bp = 0;
@@ -190,6 +251,11 @@ __global__ __launch_bounds__(DF_BLOCK) void udf_kernel(UdfArgs a) {
         const float udf = clampf(d, 0.f, a.max_df);  // :178
         const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
         const bool sat = udf == a.max_df;            // :180
+        if (r.x) {
+            img_sdf_epilogue(flag, udf, sat ? 0.f : -(dx / nrm), sat ? 0.f : -(dy / nrm), sat ? 0.f : -(dz / nrm),
+                             r.p + (size_t)pt * r.np + 4, (double)a.max_df, r.h + pt * 3 + 2, r.Jh + pt * 30 + 2);
+            return;
+        }
         a.udf[pt] = udf;
         a.grad[pt * 3 + 0] = sat ? 0.f : -(dx / nrm);
         a.grad[pt * 3 + 1] = sat ? 0.f : -(dy / nrm);
@@ -198,56 +264,75 @@ __global__ __launch_bounds__(DF_BLOCK) void udf_kernel(UdfArgs a) {
     }
 }
 
-// df_computer.py:200-221 for one point per workgroup.  A voxel counts when its collision label differs from
-// the point's (_get_mindist_occgrid, :193-197); the result is the counting voxel of least dist, ties to the
-// lowest voxel index.  With orig_idx the grid is sorted by dist: the scan stops after the first chunk that
-// holds a counting voxel and the chunks that may still hold one at the same dist.
-__global__ __launch_bounds__(DF_BLOCK) void sdf_grid_kernel(SdfGridArgs a) {
-    __shared__ float sd[DF_BLOCK / 64];
-    __shared__ int si[DF_BLOCK / 64], sp[DF_BLOCK / 64];
-    const ImgCfg c = img_cfg(a.im);
-    const long long pt = blockIdx.x;
-    const float* p = a.im.points + (size_t)pt * 3;
-    const float px = p[0], py = p[1], pz = p[2];
-    const float* img = img_of(a.im, pt);
+// df_computer.py:200-221 for the point (px, py, pz) by the whole workgroup.  A voxel counts when its collision label
+// differs from the point's (_get_mindist_occgrid, :193-197); the result is the counting voxel of least dist, ties to
+// the lowest voxel index.  With orig_idx the grid is sorted by dist: the scan stops after the first chunk that
+// holds a counting voxel and the chunks that may still hold one at the same dist.  Every argument is uniform over
+// the workgroup (the loop holds barriers); results valid in thread 0, vox = -1 where no voxel counts.
+__device__ __forceinline__ void sdf_grid_point(const float* __restrict__ img, const ImgCfg& c, float px, float py,
+                                               float pz, float min_df, float max_df, const float* grid,
+                                               const float* dist, const int* orig_idx, int G, float* sd, int* si,
+                                               int* sp, float& sdf, float& gx, float& gy, float& gz, int& vox) {
     const int occ = col_test(img, c, 2, 0.f, px, py, pz);  // :201, ColChecker(.., 0, .., 'extrapolate') (:22)
-    const bool sorted = a.orig_idx != nullptr;
+    const bool sorted = orig_idx != nullptr;
     float best = INFINITY;
     int bi = INT_MAX, bp = 0;
     bool stopping = false;
     float stop_d = 0.f;
-    for (int base = 0; base < a.G; base += DF_BLOCK) {
-        if (stopping && !(a.dist[base] <= stop_d)) break;  // uniform: every later voxel is farther
+    for (int base = 0; base < G; base += DF_BLOCK) {
+        if (stopping && !(dist[base] <= stop_d)) break;  // uniform: every later voxel is farther
         const int g = base + (int)threadIdx.x;
-        if (g < a.G) {
-            const float* v = a.grid + (size_t)g * 3;
+        if (g < G) {
+            const float* v = grid + (size_t)g * 3;
             if (col_test(img, c, 2, 0.f, px + v[0], py + v[1], pz + v[2]) != occ)  // :188,213
-                lexmin(best, bi, bp, a.dist[g], sorted ? a.orig_idx[g] : g, g);
+                lexmin(best, bi, bp, dist[g], sorted ? orig_idx[g] : g, g);
         }
         if (sorted && !stopping && __syncthreads_or(bi != INT_MAX)) {
             stopping = true;
-            stop_d = a.dist[min(base + DF_BLOCK, a.G) - 1];  // no found voxel is farther than this one
+            stop_d = dist[min(base + DF_BLOCK, G) - 1];  // no found voxel is farther than this one
         }
     }
     block_lexmin(best, bi, bp, sd, si, sp);
     if (threadIdx.x == 0) {
         const bool found = bi != INT_MAX;
         const float sign = occ ? -1.f : 1.f;                                     // :202
-        const float sdf = clampf(sign * (found ? best : a.max_df), a.min_df, a.max_df);  // :195,217
-        const bool sat = !found || sdf == a.min_df || sdf == a.max_df;           // :219
-        float gx = 0.f, gy = 0.f, gz = 0.f;
+        sdf = clampf(sign * (found ? best : max_df), min_df, max_df);            // :195,217
+        const bool sat = !found || sdf == min_df || sdf == max_df;               // :219
+        gx = 0.f, gy = 0.f, gz = 0.f;
         if (!sat) {
-            const float* v = a.grid + (size_t)bp * 3;
+            const float* v = grid + (size_t)bp * 3;
             const float nrm = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);   // :218
             gx = -sign * (v[0] / nrm);
             gy = -sign * (v[1] / nrm);
             gz = -sign * (v[2] / nrm);
         }
+        vox = found ? bi : -1;
+    }
+}
+
+__global__ __launch_bounds__(DF_BLOCK) void sdf_grid_kernel(SdfGridArgs a, DfRowsArgs r) {
+    __shared__ float sd[DF_BLOCK / 64];
+    __shared__ int si[DF_BLOCK / 64], sp[DF_BLOCK / 64];
+    const ImgCfg c = img_cfg(a.im);
+    const long long pt = blockIdx.x;
+    double flag = 1.0;
+    if (r.x && !rows_prologue(r, pt, a.max_df, flag)) return;
+    const float* p = a.im.points + (size_t)pt * 3;
+    float sdf = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+    int vox = -1;
+    sdf_grid_point(r.x ? rows_img(a.im, r, pt) : img_of(a.im, pt), c, p[0], p[1], p[2], a.min_df, a.max_df, a.grid, a.dist,
+                   a.orig_idx, a.G, sd, si, sp, sdf, gx, gy, gz, vox);
+    if (threadIdx.x == 0) {
+        if (r.x) {
+            img_sdf_epilogue(flag, sdf, gx, gy, gz, r.p + (size_t)pt * r.np + 4, (double)a.max_df, r.h + pt * 3 + 2,
+                             r.Jh + pt * 30 + 2);
+            return;
+        }
         a.sdf[pt] = sdf;
         a.grad[pt * 3 + 0] = gx;
         a.grad[pt * 3 + 1] = gy;
         a.grad[pt * 3 + 2] = gz;
-        if (a.vox_idx) a.vox_idx[pt] = found ? bi : -1;
+        if (a.vox_idx) a.vox_idx[pt] = vox;
     }
 }
 
@@ -266,12 +351,33 @@ hipError_t launch_minpool5(const MinpoolArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_udf(const UdfArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(udf_kernel, dim3((unsigned)a.im.n), dim3(DF_BLOCK), udf_lds_bytes(a.im.H, a.im.W), s, a);
+    hipLaunchKernelGGL(udf_kernel, dim3((unsigned)a.im.n), dim3(DF_BLOCK), udf_lds_bytes(a.im.H, a.im.W), s, a,
+                       DfRowsArgs{});
     return hipGetLastError();
 }
 
 hipError_t launch_sdf_grid(const SdfGridArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(sdf_grid_kernel, dim3((unsigned)a.im.n), dim3(DF_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(sdf_grid_kernel, dim3((unsigned)a.im.n), dim3(DF_BLOCK), 0, s, a, DfRowsArgs{});
+    return hipGetLastError();
+}
+
+// the labelling kernels in their rows mode: the points buffer a.pts is the rows' own (required)
+hipError_t launch_img_sdf_rows(const ImgSdfArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return hipSuccess;
+    const DfRowsArgs r{a.x, a.p, a.h, a.Jh, a.pts, a.img_of, a.N1, a.np};
+    if (a.is_signed) {
+        SdfGridArgs g{};
+        g.im = DfImg{a.images, 0, a.H, a.W, a.dmax, a.hfov, a.vfov, a.is_depth, a.is_spherical, a.pts, nullptr, a.rows, a.N1};
+        g.min_df = a.min_df; g.max_df = a.max_df;
+        g.grid = a.grid; g.dist = a.dist; g.orig_idx = a.orig_idx; g.G = a.G;
+        hipLaunchKernelGGL(sdf_grid_kernel, dim3((unsigned)a.rows), dim3(DF_BLOCK), 0, s, g, r);
+    } else {  // on the pooled images
+        const int h = a.H / 5, w = a.W / 5;
+        UdfArgs u{};
+        u.im = DfImg{a.pooled, 0, h, w, a.dmax, a.hfov, a.vfov, a.is_depth, a.is_spherical, a.pts, nullptr, a.rows, a.N1};
+        u.max_df = a.max_df;
+        hipLaunchKernelGGL(udf_kernel, dim3((unsigned)a.rows), dim3(DF_BLOCK), udf_lds_bytes(h, w), s, u, r);
+    }
     return hipGetLastError();
 }
 

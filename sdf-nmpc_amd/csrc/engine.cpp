@@ -90,6 +90,7 @@ struct sdfnmpc_ctx {
     bool timing = false;
     DevBuf c13, sdf4, lat, out4, glat, qpw, qpst, wws;
     DevBuf dfpool;  // sdfnmpc_udf: the 5x5 min-pooled images
+    DevBuf imgpts;  // sdfnmpc_img_sdf_rows without the caller's pts: the camera-frame points of the rows
     DevBuf morph_t, morph_e;  // sdfnmpc_outlier_rm with kernel_size != 3: the thresholded image and its erosion
     // host-pointer path (sdf_eval_host, the CasADi external): pinned staging, its own hoist buffer and
     // the latents it was computed for (consecutive acados calls share one latent: the hoist is reused)
@@ -1299,6 +1300,22 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
 // the option check + argument block of sdfnmpc_scene_sdf_rows (below, with the scenes): nothing is launched
 extern "C" int sdfnmpc_scene_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int B, int N, int np,
                                        const double* x, const double* p, double* h, double* Jh, SceneSdfArgs* out);
+// the same split for sdfnmpc_img_sdf_rows (below, with the image ground truth)
+extern "C" int sdfnmpc_img_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int B, int N, int np,
+                                     const double* x, const double* p, double* h, double* Jh, float* pts,
+                                     ImgSdfArgs* out);
+
+// the launch of sdfnmpc_img_sdf_rows on the context stream: the scan reads its point from a buffer, the caller's pts or a
+// workspace of the context
+static int img_sdf_launch(sdfnmpc_ctx* ctx, ImgSdfArgs a) {
+    if (a.rows <= 0) return SDFNMPC_OK;
+    if (!a.pts) {
+        HIPCHK(ctx->imgpts.ensure((size_t)a.rows * 3 * sizeof(float)));
+        a.pts = (float*)ctx->imgpts.p;
+    }
+    HIPCHK(timed(ctx, "img_sdf_rows", [&] { return launch_img_sdf_rows(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // batched preparation phase
@@ -1306,7 +1323,8 @@ extern "C" int sdfnmpc_scene_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf
 // the pack runs after the linearisation on the aux stream, beside the SDF kernel, and only the sdf row
 // of C^T waits for the join; with the sdf cost (ny == 12) H and g depend on h[2], so the whole pack
 // follows the join.  With lin_args.sdf_scene no network runs: linearize, the scene's rows kernel (scene_sdf.hip) and the
-// whole pack follow each other on the main stream.
+// whole pack follow each other on the main stream; lin_args.sdf_image is the same sequence with the image field's rows
+// kernel (df_truth.hip: img_sdf_rows_kernel) in the middle.
 static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad_model* mdl,
                     const sdfnmpc_lin_args* a, const QpArgs* pk, bool* split_out = nullptr) {
     if (!ctx || !mdl || !a) return fail(SDFNMPC_E_ARG, "NULL argument");
@@ -1319,9 +1337,13 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
             return fail(SDFNMPC_E_ARG, "model.kind 1 ('att_tau') needs tau_roll > 0 and tau_pitch > 0");
     }
     if (a->no_sdf && a->sdf_scene) return fail(SDFNMPC_E_ARG, "lin_args.sdf_scene together with lin_args.no_sdf");
-    // no network is evaluated: nothing reads the SDF, or the SDF row is the scene's exact distance (sdf_scene)
-    const bool no_sdf = a->no_sdf != 0 || a->sdf_scene;
-    if (!net && !no_sdf) return fail(SDFNMPC_E_ARG, "NULL network (only allowed with lin_args.no_sdf or .sdf_scene)");
+    if (a->no_sdf && a->sdf_image) return fail(SDFNMPC_E_ARG, "lin_args.sdf_image together with lin_args.no_sdf");
+    if (a->sdf_scene && a->sdf_image) return fail(SDFNMPC_E_ARG, "lin_args.sdf_image together with lin_args.sdf_scene");
+    // no network is evaluated: nothing reads the SDF, or the SDF row is the scene's exact distance (sdf_scene) or the
+    // field of the camera image (sdf_image)
+    const bool no_sdf = a->no_sdf != 0 || a->sdf_scene || a->sdf_image;
+    if (!net && !no_sdf)
+        return fail(SDFNMPC_E_ARG, "NULL network (only allowed with lin_args.no_sdf, .sdf_scene or .sdf_image)");
     if (a->B < 0 || a->N < 1 || a->np < 17 + (net ? net->host.L : 0) || (a->latent_mode != 0 && a->latent_mode != 1))
         return fail(SDFNMPC_E_ARG, "bad B/N/np/latent_mode");
     const int nyN = a->nyN == 0 ? 4 : a->nyN;
@@ -1339,6 +1361,10 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
     SceneSdfArgs ssa{};
     if (a->sdf_scene)  // refused before the first launch
         if (int rc_ = sdfnmpc_scene_sdf_args_(ctx, a->sdf_scene, a->B, a->N, a->np, a->x, a->p, a->h, a->Jh, &ssa)) return rc_;
+    ImgSdfArgs isa{};
+    if (a->sdf_image)
+        if (int rc_ = sdfnmpc_img_sdf_args_(ctx, a->sdf_image, a->B, a->N, a->np, a->x, a->p, a->h, a->Jh, nullptr, &isa))
+            return rc_;
     ScopedDevice sd(ctx->device);
     const long long rows = (long long)a->B * (a->N + 1);
     float4* sdf4 = (float4*)a->sdf;
@@ -1414,6 +1440,8 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
         HIPCHK(timed(ctx, "linearize", [&] { return launch_linearize(la, ctx->stream); }, ctx->stream));
         if (a->sdf_scene)  // the SDF row from the scene's closed forms, between the linearisation and the pack
             HIPCHK(timed(ctx, "scene_sdf_rows", [&] { return launch_scene_sdf_rows(ssa, ctx->stream); }));
+        if (a->sdf_image)  // or from the field of the camera image
+            if (int rc_ = img_sdf_launch(ctx, isa)) return rc_;
         return finish_pack();
     }
     // 2. latent hoisting (latent = p[.][17:] as fp32)
@@ -1659,6 +1687,7 @@ extern "C" int sdfnmpc_step_create(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, con
     *out = nullptr;
     if (qa->B < 1) return fail(SDFNMPC_E_ARG, "step_create: B must be >= 1");
     if (la->sdf_scene) return fail(SDFNMPC_E_UNSUPPORTED, "step_create: lin_args.sdf_scene (a scene as the SDF source) is not captured");
+    if (la->sdf_image) return fail(SDFNMPC_E_UNSUPPORTED, "step_create: lin_args.sdf_image (an image as the SDF source) is not captured");
     // once eagerly: every workspace is allocated and every argument checked before the capture (no
     // allocation may happen inside it)
     if (int rc = step_eager(ctx, net, mdl, la, o, qa, u0, status)) return rc;
@@ -2151,6 +2180,67 @@ extern "C" int sdfnmpc_sdf_truth(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* o, fl
     a.vox_idx = vox_idx;
     ScopedDevice sd(ctx->device);
     HIPCHK(timed(ctx, "sdf_grid", [&] { return launch_sdf_grid(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+// the image's own field as the SDF row (df_truth.hip: img_sdf_rows_kernel): the option check and the argument block,
+// split from the launch for the preparation phase (lin_args.sdf_image) and the solver.  Nothing is launched.
+extern "C" int sdfnmpc_img_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int B, int N, int np,
+                                     const double* x, const double* p, double* h, double* Jh, float* pts,
+                                     ImgSdfArgs* out) {
+    if (!ctx || !o || !out) return fail(SDFNMPC_E_ARG, "img_sdf_rows: NULL context or options");
+    if (B < 0 || N < 1 || np < 17) return fail(SDFNMPC_E_ARG, "img_sdf_rows: B >= 0, N >= 1 and np >= 17 required");
+    if (!(o->img.dmax > 0.f) || !(o->img.hfov > 0.f) || !(o->img.vfov > 0.f))
+        return fail(SDFNMPC_E_ARG, "img_sdf_rows: dmax, hfov and vfov must be positive");
+    if (o->H < 1 || o->W < 1 || (long long)o->H * o->W > 2147483647LL)
+        return fail(SDFNMPC_E_ARG, "img_sdf_rows: bad image size");
+    if (!(o->max_df > 0.f) || !std::isfinite(o->max_df))
+        return fail(SDFNMPC_E_ARG, "img_sdf_rows: max_df must be positive and finite");
+    if (!(o->min_df < o->max_df)) return fail(SDFNMPC_E_ARG, "img_sdf_rows: min_df must be below max_df");
+    if (!o->images) return fail(SDFNMPC_E_ARG, "img_sdf_rows: NULL images");
+    if (o->is_signed) {
+        if (!o->grid || !o->dist || o->G < 1) return fail(SDFNMPC_E_ARG, "img_sdf_rows: the signed field needs its voxel grid");
+    } else {
+        if (o->H % 5 != 0 || o->W % 5 != 0)
+            return fail(SDFNMPC_E_ARG, "img_sdf_rows: H and W must be multiples of 5 (the min-pool kernel)");
+        if (udf_lds_bytes(o->H / 5, o->W / 5) > UDF_LDS_MAX) return fail(SDFNMPC_E_ARG, "img_sdf_rows: image too large");
+        if (!o->pooled) return fail(SDFNMPC_E_ARG, "img_sdf_rows: the unsigned field needs the pooled images");
+    }
+    if ((long long)B * (N + 1) > 2147483647LL) return fail(SDFNMPC_E_ARG, "img_sdf_rows: too many rows");
+    if (B > 0 && (!x || !p || !h || !Jh)) return fail(SDFNMPC_E_ARG, "img_sdf_rows: NULL x, p, h or Jh");
+    ImgSdfArgs a{};
+    a.images = o->images; a.pooled = o->pooled; a.img_of = o->img_of; a.H = o->H; a.W = o->W;
+    a.dmax = o->img.dmax; a.hfov = o->img.hfov; a.vfov = o->img.vfov;
+    a.is_depth = o->img.is_depth != 0; a.is_spherical = o->img.is_spherical != 0;
+    a.is_signed = o->is_signed != 0; a.min_df = o->min_df; a.max_df = o->max_df;
+    a.grid = o->grid; a.dist = o->dist; a.orig_idx = o->orig_idx; a.G = o->G;
+    a.rows = (long long)B * (N + 1); a.N1 = N + 1; a.np = np;
+    a.x = x; a.p = p; a.h = h; a.Jh = Jh; a.pts = pts;
+    *out = a;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_img_sdf_rows(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int B, int N, int np,
+                                    const double* x, const double* p, double* h, double* Jh, float* pts) {
+    ImgSdfArgs a{};
+    if (int rc = sdfnmpc_img_sdf_args_(ctx, o, B, N, np, x, p, h, Jh, pts, &a)) return rc;
+    if (B == 0) return SDFNMPC_OK;
+    ScopedDevice sd(ctx->device);
+    return img_sdf_launch(ctx, a);
+}
+
+// the min-pool of an image source's images into its pooled buffer: what sdfnmpc_udf does in front of its scan
+extern "C" int sdfnmpc_img_sdf_pool(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int n_img) {
+    if (!ctx || !o) return fail(SDFNMPC_E_ARG, "img_sdf_pool: NULL context or options");
+    if (n_img < 0 || o->H < 1 || o->W < 1 || o->H % 5 != 0 || o->W % 5 != 0)
+        return fail(SDFNMPC_E_ARG, "img_sdf_pool: n_img >= 0 and H, W positive multiples of 5 required");
+    if (!(o->img.dmax > 0.f)) return fail(SDFNMPC_E_ARG, "img_sdf_pool: dmax must be positive");
+    if ((long long)n_img * o->H * o->W > 2147483647LL) return fail(SDFNMPC_E_ARG, "img_sdf_pool: too many pixels");
+    if (n_img == 0) return SDFNMPC_OK;
+    if (!o->images || !o->pooled) return fail(SDFNMPC_E_ARG, "img_sdf_pool: NULL images or pooled buffer");
+    ScopedDevice sd(ctx->device);
+    MinpoolArgs m{o->images, const_cast<float*>(o->pooled), n_img, o->H, o->W, o->img.dmax};
+    HIPCHK(timed(ctx, "minpool5", [&] { return launch_minpool5(m, ctx->stream); }));
     return SDFNMPC_OK;
 }
 

@@ -20,6 +20,7 @@
 //     (cos(xb), cos(xb + pi/2)) also stay in registers until the final contraction.
 #include <hip/hip_runtime.h>
 
+#include "cam_point.h"
 #include "sdf_kernels.h"
 #include "sincos.h"
 
@@ -223,12 +224,7 @@ __global__ __launch_bounds__(256, (M == 32) ? 2 : 1) void sdf_mlp_kernel(SdfArgs
         const int rr = r < A.rows ? r : A.rows - 1;
         float4 p;
         if (A.x) {  // Co_p_B = W_R_Co^T (W_p_B - W_p_Co) in fp64, handed over as fp32 (gen_model.py:46-51)
-            const double* xr = A.x + (size_t)rr * 10;
-            const double* pr = A.p + (size_t)rr * A.np;
-            const double* R = pr + 4;
-            const double e0 = xr[0] - pr[1], e1 = xr[1] - pr[2], e2 = xr[2] - pr[3];
-            p = make_float4((float)((e0 * R[0] + e1 * R[3]) + e2 * R[6]), (float)((e0 * R[1] + e1 * R[4]) + e2 * R[7]),
-                            (float)((e0 * R[2] + e1 * R[5]) + e2 * R[8]), 0.0f);
+            p = cam_point(A.x + (size_t)rr * 10, A.p + (size_t)rr * A.np);
         } else {
             p = A.pos[rr];
         }

@@ -15,6 +15,7 @@
 // returns; the arithmetic of the embedding and its derivative is sdf_mlp.hip's / sdf_wide.hip's.
 #include <hip/hip_runtime.h>
 
+#include "cam_point.h"
 #include "sdf_row_dev.h"
 
 namespace sdfn {
@@ -130,12 +131,7 @@ __device__ __forceinline__ void row_eval(const SdfRowArgs& A, const int r) {
     const float w0 = A.w0;
     float4 p;
     if (A.x) {  // Co_p_B = W_R_Co^T (W_p_B - W_p_Co) in fp64, handed over as fp32 (sdf_mlp_kernel's)
-        const double* xr = A.x + (size_t)r * 10;
-        const double* pr = A.p + (size_t)r * A.np;
-        const double* R = pr + 4;
-        const double e0 = xr[0] - pr[1], e1 = xr[1] - pr[2], e2 = xr[2] - pr[3];
-        p = make_float4((float)((e0 * R[0] + e1 * R[3]) + e2 * R[6]), (float)((e0 * R[1] + e1 * R[4]) + e2 * R[7]),
-                        (float)((e0 * R[2] + e1 * R[5]) + e2 * R[8]), 0.0f);
+        p = cam_point(A.x + (size_t)r * 10, A.p + (size_t)r * A.np);
     } else {
         p = A.c.pos[r];
     }

@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "cam_point.h"
 #include "sdf_kernels.h"
 #include "sincos.h"
 
@@ -296,13 +297,8 @@ __global__ __launch_bounds__(256) void wide_emb_kernel(WideSdfArgs a) {
     const int r = (int)(i / NEK), m = (int)(i - (long long)r * NEK);
     float px, py, pz;
     if (a.x) {  // Co_p_B = W_R_Co^T (W_p_B - W_p_Co) in fp64, handed over as fp32 (gen_model.py:46-51)
-        const double* xr = a.x + (size_t)r * 10;
-        const double* pr = a.p + (size_t)r * a.np;
-        const double* R = pr + 4;
-        const double e0 = xr[0] - pr[1], e1 = xr[1] - pr[2], e2 = xr[2] - pr[3];
-        px = (float)((e0 * R[0] + e1 * R[3]) + e2 * R[6]);
-        py = (float)((e0 * R[1] + e1 * R[4]) + e2 * R[7]);
-        pz = (float)((e0 * R[2] + e1 * R[5]) + e2 * R[8]);
+        const float4 p = cam_point(a.x + (size_t)r * 10, a.p + (size_t)r * a.np);
+        px = p.x; py = p.y; pz = p.z;
     } else {
         const float4 p = a.pos[r];
         px = p.x; py = p.y; pz = p.z;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/sdfnmpc.h"
+#include "df_kernels.h"
 #include "plant_kernels.h"
 #include "ref_kernels.h"
 #include "scene_kernels.h"
@@ -43,6 +44,10 @@ extern "C" int sdfnmpc_sensor_args_(const sdfnmpc_sensor_opts* o, float* img, in
 extern "C" int sdfnmpc_sensor_launch_(sdfnmpc_ctx* ctx, const sdfn::SensorArgs* sa, const sdfn::OutlierArgs* oa,
                                       int outlier_rm, int frame);
 extern "C" int sdfnmpc_scene_on_ctx_(const sdfnmpc_scene* sc, const sdfnmpc_ctx* ctx);
+// engine.cpp: the option check of sdfnmpc_img_sdf_rows (nothing is launched)
+extern "C" int sdfnmpc_img_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int B, int N, int np,
+                                     const double* x, const double* p, double* h, double* Jh, float* pts,
+                                     sdfn::ImgSdfArgs* out);
 
 namespace {
 
@@ -113,6 +118,10 @@ struct sdfnmpc_solver {
     sdfnmpc_scene_sdf_opts sdf_src{};
     double* tau = nullptr;
     std::vector<double> h_dt;
+    // or the field of a camera image (sdfnmpc_solver_set_sdf_image): a copy of the caller's option block, its pointers
+    // the caller's.  At most one of the two sources is set.
+    sdfnmpc_img_sdf_opts img_src{};
+    bool has_img = false;
     sdfnmpc_quad_model model{};
     sdfnmpc_qp_opts qp{};
     std::vector<void*> allocs;
@@ -371,6 +380,7 @@ static int step_enqueue(sdfnmpc_solver* s) {
     la.xn = s->xn; la.AB = s->AB; la.y = s->y; la.Jy = s->Jy; la.yN = s->yN; la.JyN = s->JyN; la.h = s->h; la.Jh = s->Jh;
     la.nyN = s->nyN; la.no_sdf = s->no_sdf ? 1 : 0; la.hE = s->hE; la.JhE = s->JhE;
     if (s->sdf_src.scene) la.sdf_scene = &s->sdf_src;  // t0: the solver's scene time (sdfnmpc_solver_set_scene_time)
+    if (s->has_img) la.sdf_image = &s->img_src;
     sdfnmpc_qp_args qa{};
     qa.B = s->B; qa.N = s->N;
     qa.xn = s->xn; qa.AB = s->AB; qa.y = s->y; qa.Jy = s->Jy; qa.yN = s->yN; qa.JyN = s->JyN; qa.h = s->h; qa.Jh = s->Jh;
@@ -513,8 +523,9 @@ extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const s
 extern "C" int sdfnmpc_solver_set_sdf_scene(sdfnmpc_solver* s, const sdfnmpc_scene* scene, const int* scene_of,
                                             double max_df, int predict) {
     if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
-    if (!scene) {  // back to the network
-        s->sdf_src = sdfnmpc_scene_sdf_opts{};
+    if (!scene) {  // back to the network, from either source; the scene time stays
+        s->sdf_src = sdfnmpc_scene_sdf_opts{nullptr, nullptr, 0.0, s->sdf_src.t0, nullptr};
+        s->has_img = false;
         return SDFNMPC_OK;
     }
     if (s->no_sdf)
@@ -535,6 +546,20 @@ extern "C" int sdfnmpc_solver_set_sdf_scene(sdfnmpc_solver* s, const sdfnmpc_sce
     }
     const double t = s->sdf_src.t0;  // the scene time survives a change of source
     s->sdf_src = sdfnmpc_scene_sdf_opts{scene, scene_of, max_df, t, predict ? s->tau : nullptr};
+    s->has_img = false;  // setting either source replaces the other
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_solver_set_sdf_image(sdfnmpc_solver* s, const sdfnmpc_img_sdf_opts* o) {
+    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
+    if (!o) return sdfnmpc_solver_set_sdf_scene(s, nullptr, nullptr, 0.0, 0);  // back to the network
+    if (s->no_sdf)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_sdf_image: no row or cost of the solver's constraint set reads the SDF");
+    sdfn::ImgSdfArgs ia{};
+    if (int rc = sdfnmpc_img_sdf_args_(s->ctx, o, s->B, s->N, s->np, s->x, s->p, s->h, s->Jh, nullptr, &ia)) return rc;
+    s->img_src = *o;
+    s->has_img = true;
+    s->sdf_src = sdfnmpc_scene_sdf_opts{nullptr, nullptr, 0.0, s->sdf_src.t0, nullptr};
     return SDFNMPC_OK;
 }
 
@@ -585,6 +610,86 @@ extern "C" int sdfnmpc_solver_rollout_scene_sdf(sdfnmpc_solver* s, const sdfnmpc
         s->sdf_src.t0 = t0 + steps_dt;
         if (pose && (k + phase) % pose->every == 0) {  // the camera pose the FOV rows read, from the current state
             if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
+            if (int rc = sdfnmpc_pack_refs(s->ctx, &po, &pra)) return rc;
+        }
+        if (a->ref)
+            if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
+        if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
+        if (int rc = step_enqueue(s)) return rc;
+        pa.k = k;
+        if (int rc = sdfnmpc_plant_launch_(s->ctx, &pa)) return rc;
+    }
+    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
+    s->pending = true;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
+                                                const sdfnmpc_perceive_args* pc, double t0, double dt,
+                                                const sdfnmpc_sensor_opts* sensor, float* scratch) {
+    if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_image_sdf");
+    if (!s->has_img)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: no image source set (sdfnmpc_solver_set_sdf_image)");
+    if (sensor && !pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: a sensor model needs perception (perc)");
+    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
+    sdfn::PlantArgs pa{};
+    sdfnmpc_ref_args ra{};
+    if (int rc = rollout_args(s, a, pa, ra)) return rc;
+    // re-imaging: the pose and render blocks, the sensor's, and what sdfnmpc_pack_refs (mode -2) would refuse
+    const sdfnmpc_img_sdf_opts& src = s->img_src;
+    sdfn::ScenePoseArgs spa{};
+    sdfn::SceneRenderArgs sra{};
+    sdfnmpc_ref_opts po{};
+    sdfnmpc_ref_args pra{};
+    sdfn::SensorArgs sna{};
+    sdfn::OutlierArgs ora{};
+    if (pc) {
+        if (pc->every < 1 || pc->phase < 0)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
+        if (!pc->scene || !sdfnmpc_scene_on_ctx_(pc->scene, s->ctx))
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging needs a scene on the solver's context");
+        if (pc->h != src.H || pc->w != src.W)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: the render size must equal the source's H x W");
+        if (src.img_of)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging renders one image per instance (img_of must be NULL)");
+        if (!pc->W_p_Bo || !pc->W_R_Bo || !pc->W_p_C || !pc->W_R_C)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging needs the pose workspaces");
+        if (int rc = sdfnmpc_scene_pose_args_(pc->B_p_C, pc->B_R_C, s->B, s->x0, pc->W_p_Bo, pc->W_R_Bo, pc->W_p_C,
+                                              pc->W_R_C, &spa))
+            return rc;
+        if (int rc = sdfnmpc_scene_render_args_(s->ctx, pc->scene, pc->scene_of, &pc->img, pc->h, pc->w, pc->scale, s->B,
+                                                pc->W_p_C, pc->W_R_C, const_cast<float*>(src.images), &sra))
+            return rc;
+        po.mode = -2;
+        for (int i = 0; i < 3; ++i) po.B_p_C[i] = pc->B_p_C[i];
+        for (int i = 0; i < 9; ++i) po.B_R_C[i] = pc->B_R_C[i];
+        pra.B = s->B; pra.N = s->N; pra.np = s->np; pra.ny = s->ny; pra.nyN = s->nyN;
+        pra.W_p_Bo = pc->W_p_Bo; pra.W_R_Bo = pc->W_R_Bo; pra.p = s->p;
+        if (sensor) {
+            if ((long long)pc->phase + a->steps > 2147483647LL)
+                return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the sensor's frame counter (phase + steps) overflows");
+            if (int rc = sdfnmpc_sensor_args_(sensor, const_cast<float*>(src.images), s->B, pc->h, pc->w, scratch, &sna, &ora))
+                return rc;
+        }
+    }
+    pa.K = a->steps;
+    pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
+    pa.pts_log = a->pts_log;
+    pa.status = s->status; pa.iters = s->iters;
+    pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
+    SolverDevice sd(s->device);
+    for (int k = 0; k < a->steps; ++k) {
+        if (pc && (k + pc->phase) % pc->every == 0) {  // a new image from the current state: pose, render, sensor, pool, pose into p
+            if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
+            // the scene's time at step k, the product rounded on its own as in sdfnmpc_solver_rollout_perceive_at
+            volatile double steps_dt = (double)(pc->phase + k) * dt;
+            const double t = t0 + steps_dt;
+            if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pc->scene, &sra, t)) return rc;
+            if (sensor)
+                if (int rc = sdfnmpc_sensor_launch_(s->ctx, &sna, &ora, sensor->outlier_rm != 0, pc->phase + k)) return rc;
+            if (!src.is_signed)
+                if (int rc = sdfnmpc_img_sdf_pool(s->ctx, &src, s->B)) return rc;
             if (int rc = sdfnmpc_pack_refs(s->ctx, &po, &pra)) return rc;
         }
         if (a->ref)
