@@ -64,6 +64,9 @@
  *                                      node positions of the batch: the field the camera image itself implies, in
  *                                      the frame of the image; sdfnmpc_lin_args.sdf_image, sdfnmpc_solver_set_sdf_image
  *                                      and sdfnmpc_solver_rollout_image_sdf carry it through the step
+ *   sdfnmpc_vae_decode                 VaeWrapper.decode (sdf_nmpc/vae.py:42-45): Decoder.forward (network/vae.py:63-90),
+ *                                      the image a latent retains; sdfnmpc_solver_rollout_image_recon flies on it (the
+ *                                      image source holds the reconstruction of every new camera image)
  *   sdfnmpc_morph / sdfnmpc_outlier_rm Dilate / Erode (and with them Open / Close) and RemoveCloseOutliers
  *                                      (utils/preprocessing.py:100-259), batched
  *   sdfnmpc_sensor_apply               ImageAugmenter's noise and erasing (utils/data.py:11-108) as a reproducible
@@ -82,7 +85,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 13
+#define SDFNMPC_ABI_VERSION 14
 
 enum {
     SDFNMPC_OK = 0,
@@ -442,6 +445,27 @@ int sdfnmpc_vae_size_latent(const sdfnmpc_vae* vae);
  * is owned by the encoder object and grows with B. */
 int sdfnmpc_vae_encode(sdfnmpc_ctx* ctx, sdfnmpc_vae* vae, const sdfnmpc_vae_opts* opts, const void* img,
                        float* latent, double* latent64);
+
+/* ---- VAE decoder (csrc/vae_dec.hip) ----
+ * Replaces VaeWrapper.decode (sdf_nmpc/vae.py:42-45): Decoder.forward (network/vae.py:63-90, eval mode) for B
+ * latents in one call on the context stream: Linear(L, 512*8*15) + ELU, four ResBlockDeconvs (512 -> 32 channels,
+ * 8x15 -> 128x240), ConvTranspose2d(32, 1, 5), a bilinear resize (align_corners false) to out_h x out_w, sigmoid.
+ * The result is a normalised RANGE image in [0, 1] whatever sensor.is_depth says (the encoder's input is
+ * Depth2Range'd).  Weights come as a `.vaed` blob of their own (sdf-nmpc_amd/vae.py:pack_decoder) with every
+ * BatchNorm folded into its transposed convolution; the encoder's `.vaew` layout is unchanged.
+ * latent: device [B][L] float32; img: device [B][out_h][out_w] float32; logits: optional device [B][128][240]
+ * float32, the values before the resize and the sigmoid.  Asynchronous; B == 0 is a no-op.  An image does not
+ * depend on its batch neighbours (bitwise).  The activation workspace (about 22 MB an image, for at most 64
+ * images: larger batches are decoded in passes of 64) is owned by the decoder object and grows with B.
+ * The workspace ties the object to the context it was loaded on (one stream orders its calls): decode on any other
+ * context is refused.  SDFNMPC_E_ARG with nothing launched: a NULL context / decoder / latent / img, B < 0, out_h or
+ * out_w < 1, a decoder loaded on another context. */
+typedef struct sdfnmpc_vae_dec sdfnmpc_vae_dec;
+int sdfnmpc_vae_dec_load(sdfnmpc_ctx* ctx, const void* vaed_blob, size_t bytes, sdfnmpc_vae_dec** out);
+void sdfnmpc_vae_dec_free(sdfnmpc_vae_dec* dec);
+int sdfnmpc_vae_dec_size_latent(const sdfnmpc_vae_dec* dec);
+int sdfnmpc_vae_decode(sdfnmpc_ctx* ctx, sdfnmpc_vae_dec* dec, int B, const float* latent, int out_h, int out_w,
+                       float* img, float* logits);
 
 /* ---- ground truth from range images (csrc/df_truth.hip) ----
  * What the image itself says about a point: the reference's Warp kernels ColChecker._kernel_colcheck
@@ -888,6 +912,24 @@ int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const sdfnmpc_roll
 int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
                                      const sdfnmpc_perceive_args* perc, double t0, double dt,
                                      const sdfnmpc_sensor_opts* sensor, float* scratch);
+
+/* sdfnmpc_solver_rollout_image_sdf for an image source that holds the RECONSTRUCTION of the camera image: what the
+ * VAE's latent retains of it (encode, decode), the rung between the camera image and the network.  perc is required
+ * and names, beside what sdfnmpc_solver_rollout_image_sdf reads, the encoder (perc->vae), the camera buffer
+ * perc->images [B][h][w] float32 (not the source's images), perc->latent [B][L] float32, optionally perc->latent64, and
+ * perc->vae_opts.yz, the Depth2Range table, required when perc->img.is_depth.  Before step k with (k + perc->phase) %
+ * perc->every == 0 it enqueues, in this order: (1) sdfnmpc_scene_pose; (2) sdfnmpc_scene_render_at of the normalised
+ * image (perc->scale = 1 / dmax) into the camera buffer; (3) with sensor != NULL sdfnmpc_sensor_apply on that buffer as
+ * frame phase + k, in normalised units; (4) sdfnmpc_vae_encode with clip = 1 and the yz table exactly when the camera
+ * measures depth; (5) sdfnmpc_vae_decode of that latent into the source's images at the source's H x W (a range image:
+ * set the source's img.is_depth = 0); (6) in unsigned mode sdfnmpc_img_sdf_pool; (7) sdfnmpc_pack_refs in mode -2.
+ * Then the step's sequence.  The latent columns of p are not written: no network is evaluated.  A plain launch
+ * sequence.  SDFNMPC_E_ARG, all before the first launch: what sdfnmpc_solver_rollout_image_sdf refuses, perc == NULL,
+ * no decoder, no encoder, either on another context, different latent sizes, missing workspaces, a camera buffer that
+ * is the source's, a depth camera without the table. */
+int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args,
+                                       const sdfnmpc_perceive_args* perc, double t0, double dt,
+                                       const sdfnmpc_sensor_opts* sensor, float* scratch, sdfnmpc_vae_dec* dec);
 
 /* ---- shooting grid (host, bit-exact numpy.linspace/diff semantics of ocp.py:21-27) ---- */
 int sdfnmpc_shooting_grid(int N, double T, int uniform, int nb_short_nodes, double dt_short, double* nodes,

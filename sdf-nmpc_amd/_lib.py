@@ -31,6 +31,7 @@ SYMBOLS = [
     "sdfnmpc_linearize", "sdfnmpc_shooting_grid", "sdfnmpc_qp_solve", "sdfnmpc_rti_prepare", "sdfnmpc_qp_feedback",
     "sdfnmpc_rti_apply", "sdfnmpc_step_create", "sdfnmpc_step_launch", "sdfnmpc_step_destroy", "sdfnmpc_pack_refs",
     "sdfnmpc_vae_load", "sdfnmpc_vae_free", "sdfnmpc_vae_size_latent", "sdfnmpc_vae_encode",
+    "sdfnmpc_vae_dec_load", "sdfnmpc_vae_dec_free", "sdfnmpc_vae_dec_size_latent", "sdfnmpc_vae_decode",
     "sdfnmpc_colcheck", "sdfnmpc_udf", "sdfnmpc_sdf_truth",
     "sdfnmpc_ctx_device", "sdfnmpc_dev_alloc", "sdfnmpc_dev_free", "sdfnmpc_memcpy",
     "sdfnmpc_solver_create", "sdfnmpc_solver_destroy", "sdfnmpc_solver_field", "sdfnmpc_solver_upload",
@@ -44,6 +45,7 @@ SYMBOLS = [
     "sdfnmpc_scene_sdf_rows", "sdfnmpc_solver_set_sdf_scene", "sdfnmpc_solver_set_scene_time",
     "sdfnmpc_solver_rollout_scene_sdf",
     "sdfnmpc_img_sdf_rows", "sdfnmpc_img_sdf_pool", "sdfnmpc_solver_set_sdf_image", "sdfnmpc_solver_rollout_image_sdf",
+    "sdfnmpc_solver_rollout_image_recon",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -247,6 +249,10 @@ def load():
         "sdfnmpc_vae_free": (None, [vp]),
         "sdfnmpc_vae_size_latent": (i, [vp]),
         "sdfnmpc_vae_encode": (i, [vp, vp, P(VaeOptsC), vp, vp, vp]),
+        "sdfnmpc_vae_dec_load": (i, [vp, vp, sz, P(vp)]),
+        "sdfnmpc_vae_dec_free": (None, [vp]),
+        "sdfnmpc_vae_dec_size_latent": (i, [vp]),
+        "sdfnmpc_vae_decode": (i, [vp, vp, i, vp, i, i, vp, vp]),
         "sdfnmpc_colcheck": (i, [vp, P(ImgOptsC), i, f, vp, i, i, i, vp, vp, ll, vp]),
         "sdfnmpc_udf": (i, [vp, P(ImgOptsC), f, vp, i, i, i, vp, vp, ll, vp, vp, vp]),
         "sdfnmpc_sdf_truth": (i, [vp, P(ImgOptsC), f, f, vp, vp, vp, i, vp, i, i, i, vp, vp, ll, vp, vp, vp]),
@@ -288,11 +294,12 @@ def load():
         "sdfnmpc_img_sdf_pool": (i, [vp, P(ImgSdfOptsC), i]),
         "sdfnmpc_solver_set_sdf_image": (i, [vp, P(ImgSdfOptsC)]),
         "sdfnmpc_solver_rollout_image_sdf": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d, P(SensorOptsC), vp]),
+        "sdfnmpc_solver_rollout_image_recon": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d, P(SensorOptsC), vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 13:
+    if lib.sdfnmpc_abi_version() != 14:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -713,6 +720,39 @@ class Vae:
             pass
 
 
+class VaeDec:
+    """Device-resident VAE decoder (sdfnmpc_vae_dec) from a `.vaed` blob (sdf_nmpc_amd.vae.pack_decoder)."""
+
+    def __init__(self, ctx: Context, blob: bytes):
+        self.ctx = ctx
+        h = C.c_void_p()
+        buf = C.create_string_buffer(blob, len(blob))
+        _check(load().sdfnmpc_vae_dec_load(ctx.h, buf, len(blob), C.byref(h)))
+        self.h = h
+
+    @property
+    def size_latent(self) -> int:
+        return int(load().sdfnmpc_vae_dec_size_latent(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            load().sdfnmpc_vae_dec_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def vae_decode(ctx: Context, dec: VaeDec, latent, img, logits=None):
+    """Enqueue sdfnmpc_vae_decode: latent device [B][L] fp32 -> img device [B][H][W] fp32 (the output size is
+    img's), logits optional device [B][128][240] fp32."""
+    _check(load().sdfnmpc_vae_decode(ctx.h, dec.h, int(latent.shape[0]), _ptr(latent), int(img.shape[-2]),
+                                     int(img.shape[-1]), _ptr(img), _ptr(logits)))
+
+
 def vae_opts(cfg, clip: float) -> VaeOptsC:
     """Per-call options from the config (sensor.dmax / mm_resolution, is_depth); B / size / dtype / yz per call."""
     o = VaeOptsC()
@@ -1105,16 +1145,23 @@ class Solver:
 
     def rollout_image_sdf(self, steps: int, plant: PlantOpts, x_log, u_log, perceive: "PerceiveArgsC" = None,
                           t0: float = 0.0, dt: float = 0.0, sensor=None, status_log=None, iters_log=None, pts_log=None,
-                          shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0):
+                          shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0,
+                          dec: "VaeDec" = None):
         """Enqueue sdfnmpc_solver_rollout_image_sdf: `rollout` for a solver with an image source -- with perceive (a
         PerceiveArgsC without an encoder) a new normalised image rendered into the source, degraded by sensor
         ((SensorOptsC, scratch), normalised units), pooled in unsigned mode, and the camera pose of p refreshed, before
-        every `every`-th step."""
+        every `every`-th step.  dec: a VaeDec -- sdfnmpc_solver_rollout_image_recon: the image is rendered into
+        the camera buffer perceive names, encoded by perceive's encoder, and its reconstruction goes into the source."""
         a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
                          _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
                          _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
         self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, perceive,
-                              sensor)
+                              sensor, dec)
+        if dec is not None:
+            _check(load().sdfnmpc_solver_rollout_image_recon(
+                self.h, C.byref(a), None if perceive is None else C.byref(perceive), float(t0), float(dt),
+                None if sensor is None else C.byref(sensor[0]), None if sensor is None else _ptr(sensor[1]), dec.h))
+            return
         _check(load().sdfnmpc_solver_rollout_image_sdf(
             self.h, C.byref(a), None if perceive is None else C.byref(perceive), float(t0), float(dt),
             None if sensor is None else C.byref(sensor[0]), None if sensor is None else _ptr(sensor[1])))

@@ -183,7 +183,7 @@ class Nmpc:
         scene._sdf_users.add(self)
 
     # ---- the camera image's own field as the SDF (csrc/df_truth.hip: img_sdf_rows_kernel)
-    def set_sdf_image(self, imgs, signed=True, max_df=None, img_of=None):
+    def set_sdf_image(self, imgs, signed=True, max_df=None, img_of=None, reconstruct=None):
         """The SDF row of the constraints (and the sdf cost) from the distance field the camera image itself implies --
         ``DfComputer.get_df``, the network's training target -- instead of the network: the perfect network, with the
         learned one's partial observability and image staleness and no approximation error.  imgs: [B, H, W] (or [H, W]
@@ -194,9 +194,15 @@ class Nmpc:
         defaults to model.max_df.  img_of: int [B], the image of each instance (imgs then holds any number of images;
         a rollout that re-images needs one per instance, img_of None).  The camera pose is whatever ``set_latent`` /
         ``set_pose_device`` put in p.  ``solve`` and ``rollout`` use the source from the next call on; None restores the
-        network.  ``set_sdf_scene`` and ``set_sdf_image`` replace each other.  ValueError, before anything is enqueued:
-        a batch split over several devices, a model whose flags read no SDF, a wrong image count, unsigned with H or W
-        not a multiple of 5."""
+        network.  ``set_sdf_scene`` and ``set_sdf_image`` replace each other.  reconstruct: a ``VaeWrapper`` with a
+        decoder on the controller's context and ``batch=B`` -- the source then holds ``reconstruct.reconstruct(imgs)``,
+        the image the VAE's latent retains (imgs: normalised images of the configured sensor, encoded with clip = 1 and
+        Depth2Range when sensor.is_depth), the rung between the camera image and the network; the reconstruction is a
+        RANGE image, so the source's image options have is_depth off.  A ``rollout(scene=...)`` of such a source
+        re-images through the VAE (sdfnmpc_solver_rollout_image_recon).  reconstruct excludes img_of.  ValueError,
+        before anything is enqueued: a batch split over several devices, a model whose flags read no SDF, a wrong image
+        count, unsigned with H or W not a multiple of 5, a reconstruct wrapper without a decoder, on another context or
+        of another batch size, reconstruct with img_of."""
         from . import _lib
         if len(self.ocp.parts) != 1:
             raise ValueError("set_sdf_image(): the batch is split over several devices; sharded batches are not built")
@@ -229,6 +235,15 @@ class Nmpc:
             raise ValueError(f"expected {Bn} images, got {shape[0]}")
         if not signed and (shape[1] % 5 or shape[2] % 5):
             raise ValueError(f"unsigned mode: H and W must be multiples of 5, got {shape[1]} x {shape[2]}")
+        if reconstruct is not None:
+            if getattr(reconstruct, "dec", None) is None:
+                raise ValueError("set_sdf_image(): reconstruct needs a VaeWrapper with a decoder (decoder=...)")
+            if reconstruct.ctx is not ctx:
+                raise ValueError("set_sdf_image(): the VaeWrapper must be built on the controller's context (ctx=nmpc.ocp.ctx)")
+            if reconstruct.B != Bn:
+                raise ValueError(f"set_sdf_image(): the VaeWrapper reconstructs {reconstruct.B} images, the batch has {Bn}")
+            if img_of is not None:
+                raise ValueError("set_sdf_image(): reconstruct excludes img_of (one reconstruction per instance)")
         if on_dev:  # a copy on the device, once the producer has finished
             dimg = _lib.DeviceArray(ctx, shape, np.float32)
             _lib._check(_lib.load().sdfnmpc_memcpy(ctx.h, dimg.data_ptr(), _lib.sync_producer(imgs).data_ptr(), dimg.nbytes, 3))
@@ -236,7 +251,12 @@ class Nmpc:
             dimg = _lib.DeviceArray.from_numpy(ctx, np.asarray(imgs, dtype=np.float32).reshape(shape))
         keep = {"images": dimg, "img_of": None if io is None else _lib.DeviceArray.from_numpy(ctx, io)}
         sn = self.cfg.sensor
-        io_c = _lib.img_opts(sn.dmax, sn.hfov, sn.vfov, sn.is_depth, sn.is_spherical)
+        is_depth = sn.is_depth
+        if reconstruct is not None:  # the source holds what the latent retains of the camera image: a range image
+            keep.update(camera=dimg, recon=reconstruct,
+                        images=reconstruct.reconstruct(dimg, normalized=True, out=_lib.DeviceArray(ctx, shape, np.float32)))
+            dimg, is_depth = keep["images"], False
+        io_c = _lib.img_opts(sn.dmax, sn.hfov, sn.vfov, is_depth, sn.is_spherical)
         if signed:
             keep.update(self._image_grid())
             o = _lib.img_sdf_opts(io_c, dimg, True, -0.3, md, keep["grid"], keep["dist"], keep["orig_idx"],
@@ -337,7 +357,10 @@ class Nmpc:
 
         With an image source (``set_sdf_image``) ``scene`` needs no ``vae`` (giving one is a ValueError): before every
         ``perceive_every``-th step the scene is rendered from the plant state as a normalised image of the source's
-        own shape (``img_shape``, when given, must equal it) into the source's buffer, degraded by ``sensor`` as frame
+        own shape (``img_shape``, when given, must equal it) into the source's buffer (a source set with ``reconstruct=``:
+        into its camera buffer, then encoded and decoded into the source, sdfnmpc_solver_rollout_image_recon -- the loop
+        ``render_from_state(normalized=True)``; ``sensor.apply``; ``set_sdf_image(img, reconstruct=vae)``;
+        ``set_pose_device``; ``keep_img`` then returns the reconstruction), degraded by ``sensor`` as frame
         ``perceive_phase + k`` (normalised units), min-pooled in the unsigned mode, and the camera pose goes into p
         (sdfnmpc_solver_rollout_image_sdf): the loop ``render_from_state(normalized=True)``; ``sensor.apply``;
         ``set_sdf_image``; ``set_pose_device``.  ``keep_img`` returns the image the source last held; ``clearance``
@@ -431,10 +454,19 @@ class Nmpc:
             if scene is not None:  # pose, render (normalised, into the source), sensor, pool, pose columns: no encoder
                 ih, iw = isrc["shape"][1:]
                 ws = _pose_workspaces(ctx, Bn)
-                perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(self.cfg), ih, iw,
-                                          scene.scale(self.cfg, normalized=True), *_extrinsics(self.cfg), None,
-                                          _lib.VaeOptsC(), int(perceive_every), int(perceive_phase), None, None, None,
-                                          *[ws[k].data_ptr() for k in POSE_WS])
+                rv = isrc.get("recon")
+                if rv is None:
+                    perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(self.cfg), ih, iw,
+                                              scene.scale(self.cfg, normalized=True), *_extrinsics(self.cfg), None,
+                                              _lib.VaeOptsC(), int(perceive_every), int(perceive_phase), None, None, None,
+                                              *[ws[k].data_ptr() for k in POSE_WS])
+                else:  # through the VAE: rendered into the camera buffer, encoded, the reconstruction into the source
+                    vo = _lib.VaeOptsC(Bn, ih, iw, 0, 1.0, _lib._ptr(rv.yz) if rv.depth2range else None)
+                    perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(self.cfg), ih, iw,
+                                              scene.scale(self.cfg, normalized=True), *_extrinsics(self.cfg), rv.vae.h,
+                                              vo, int(perceive_every), int(perceive_phase), isrc["camera"].data_ptr(),
+                                              rv.latent.data_ptr(), rv.latent64.data_ptr(),
+                                              *[ws[k].data_ptr() for k in POSE_WS])
                 perc._keep = ws
                 t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)
         elif scene is not None:
@@ -473,7 +505,8 @@ class Nmpc:
         elif isrc is not None:
             sn = None if sensor is None else sensor.opts(Bn, ih, iw, normalized=True)  # the source's images are normalised
             clock = (t0, dts) if perc is not None else (0.0, 0.0)
-            solver.rollout_image_sdf(K, plant, perceive=perc, t0=clock[0], dt=clock[1], sensor=sn,
+            dec = isrc["recon"].dec if perc is not None and isrc.get("recon") is not None else None
+            solver.rollout_image_sdf(K, plant, perceive=perc, t0=clock[0], dt=clock[1], sensor=sn, dec=dec,
                                      shift=int(self.cfg.mpc.shift), **kw, **log)
             if perc is not None:
                 self._clean("pose")

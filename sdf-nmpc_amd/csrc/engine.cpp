@@ -2102,6 +2102,249 @@ extern "C" int sdfnmpc_vae_encode(sdfnmpc_ctx* ctx, sdfnmpc_vae* v, const sdfnmp
 }
 
 // ------------------------------------------------------------------------------------------------
+// VAE decoder (vae_dec.hip): .vaed blob -> device weights + activation workspace
+struct VaeDecOp {
+    size_t wpl_off = 0, b_off = 0;  // in floats from the device block
+    const unsigned short* wpl = nullptr;
+    const float* b = nullptr;
+    size_t wps = 0;
+    int cin = 0, cout = 0, nphase = 0;
+    int ntaps[4] = {0}, py[4] = {0}, px[4] = {0};
+    unsigned woff[4] = {0};
+    signed char dy[4][VAE_DEC_TAPS] = {{0}}, dx[4][VAE_DEC_TAPS] = {{0}};
+};
+
+struct sdfnmpc_vae_dec {
+    int device = 0;
+    const sdfnmpc_ctx* ctx = nullptr;
+    int L = 0;
+    void* dmem = nullptr;
+    const float *head_w = nullptr, *head_b = nullptr, *tail_w = nullptr, *tail_b = nullptr;
+    VaeDecOp up[4], sc[4], cv[4];  // per ResBlockDeconv: the stride-2 3x3, the shortcut, the stride-1 3x3
+    DevBuf ws;
+};
+
+static const int kDecH0 = 8, kDecW0 = 15, kDecC0 = 512, kDecF = 512 * 8 * 15;
+static const int kDecChunk = 64;  // images decoded per pass: bounds the workspace (about 22 MB an image)
+
+extern "C" int sdfnmpc_vae_dec_load(sdfnmpc_ctx* ctx, const void* blob, size_t bytes, sdfnmpc_vae_dec** out) {
+    if (!ctx || !blob || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_vae_dec_load");
+    *out = nullptr;
+    struct Hdr {
+        char magic[8];
+        uint32_t version, L, batchnorm, n_floats;
+    } h;
+    if (bytes < sizeof(Hdr)) return fail(SDFNMPC_E_FORMAT, "vaed: truncated header");
+    memcpy(&h, blob, sizeof(Hdr));
+    if (memcmp(h.magic, "SDFNVAED", 8) != 0 || h.version != 1) return fail(SDFNMPC_E_FORMAT, "not a version-1 .vaed blob");
+    if (h.L < 1 || h.L > (uint32_t)VAE_DEC_LMAX) return fail(SDFNMPC_E_UNSUPPORTED, "vaed: size_latent outside [1, 1024]");
+    if (bytes != sizeof(Hdr) + 4ull * h.n_floats) return fail(SDFNMPC_E_FORMAT, "vaed: size mismatch");
+    size_t need = (size_t)h.L * kDecF + kDecF + 25 * 32 + 1;
+    for (int k = 0; k < 4; ++k) {
+        const size_t ci = kDecC0 >> k, co = ci / 2;
+        need += 9 * ci * co + co + ci * co + co + 9 * co * co + co;
+    }
+    if (need != h.n_floats) return fail(SDFNMPC_E_FORMAT, "vaed: parameter count does not match the reference decoder");
+    const float* src = (const float*)((const char*)blob + sizeof(Hdr));
+    auto split3 = [](float x, unsigned short* hi, unsigned short* mid, unsigned short* lo) {
+        uint32_t u, hb, mb, lb;
+        memcpy(&u, &x, 4);
+        hb = u & 0xffff0000u;
+        float hf, r1, mf, r2;
+        memcpy(&hf, &hb, 4);
+        r1 = x - hf;  // exact (the leading 8 significant bits removed)
+        memcpy(&u, &r1, 4);
+        mb = u & 0xffff0000u;
+        memcpy(&mf, &mb, 4);
+        r2 = r1 - mf;
+        memcpy(&u, &r2, 4);
+        lb = u & 0xffff0000u;
+        *hi = (unsigned short)(hb >> 16);
+        *mid = (unsigned short)(mb >> 16);
+        *lo = (unsigned short)(lb >> 16);
+    };
+    auto* d = new sdfnmpc_vae_dec();
+    d->device = ctx->device;
+    d->ctx = ctx;
+    d->L = (int)h.L;
+    std::vector<float> dev;
+    auto put = [&](const float* p, size_t n) {  // 16-byte aligned sections
+        const size_t o = dev.size();
+        dev.insert(dev.end(), p, p + n);
+        dev.resize((dev.size() + 3) & ~(size_t)3, 0.0f);
+        return o;
+    };
+    // one GEMM operand: w [KS][KS][cin][cout] (the transposed convolution's own tap indices), split into three
+    // bf16 planes of K-tile rows [phase][tap cin / 16][cout][16]
+    struct Tap { int ky, kx, dy, dx; };
+    auto put_op = [&](VaeDecOp& op, const float* w, const float* b, int ks, int cin, int cout,
+                      const std::vector<std::vector<Tap>>& phases, const int (*pyx)[2]) {
+        op.cin = cin;
+        op.cout = cout;
+        op.nphase = (int)phases.size();
+        size_t total = 0;
+        for (int p = 0; p < op.nphase; ++p) {
+            op.woff[p] = (unsigned)total;
+            op.ntaps[p] = (int)phases[p].size();
+            op.py[p] = pyx[p][0];
+            op.px[p] = pyx[p][1];
+            total += phases[p].size() * (size_t)cin * cout;
+        }
+        op.wps = total;
+        op.b_off = put(b, cout);
+        op.wpl_off = dev.size();
+        dev.resize(dev.size() + (((3 * total + 1) / 2 + 3) & ~(size_t)3), 0.0f);
+        unsigned short* pl = (unsigned short*)&dev[op.wpl_off];
+        for (int p = 0; p < op.nphase; ++p)
+            for (size_t t = 0; t < phases[p].size(); ++t) {
+                const Tap& tp = phases[p][t];
+                op.dy[p][t] = (signed char)tp.dy;
+                op.dx[p][t] = (signed char)tp.dx;
+                const float* wt = w + (size_t)(tp.ky * ks + tp.kx) * cin * cout;
+                for (int ci = 0; ci < cin; ++ci)
+                    for (int n = 0; n < cout; ++n) {
+                        const size_t e = op.woff[p] + (((t * (cin / 16) + ci / 16) * (size_t)cout) + n) * 16 + ci % 16;
+                        split3(wt[(size_t)ci * cout + n], &pl[e], &pl[total + e], &pl[2 * total + e]);
+                    }
+            }
+    };
+    size_t off = 0;
+    const size_t head_w = put(src + off, (size_t)h.L * kDecF);
+    off += (size_t)h.L * kDecF;
+    const size_t head_b = put(src + off, kDecF);
+    off += kDecF;
+    // ConvTranspose2d(k3, s2, p1, op1): output row 2 i + 1 - 1 + ky ... o = 2 i - 1 + ky, so an even output row takes
+    // ky = 1 from input row i and an odd one ky = 0 from row i + 1 and ky = 2 from row i; columns alike
+    static const int pyx4[4][2] = {{0, 0}, {0, 1}, {1, 0}, {1, 1}}, pyx1[1][2] = {{0, 0}};
+    std::vector<std::vector<Tap>> up_ph(4), cv_ph(1), sc_ph(1);
+    for (int p = 0; p < 4; ++p) {
+        const int py = pyx4[p][0], px = pyx4[p][1];
+        const int ry[2][2] = {{py ? 0 : 1, py ? 1 : 0}, {2, 0}}, rx[2][2] = {{px ? 0 : 1, px ? 1 : 0}, {2, 0}};
+        for (int a = 0; a < (py ? 2 : 1); ++a)
+            for (int b = 0; b < (px ? 2 : 1); ++b) up_ph[p].push_back({ry[a][0], rx[b][0], ry[a][1], rx[b][1]});
+    }
+    // ConvTranspose2d(k3, s1, p1): o = i - 1 + ky, so tap ky reads input row o + 1 - ky
+    for (int ky = 0; ky < 3; ++ky)
+        for (int kx = 0; kx < 3; ++kx) cv_ph[0].push_back({ky, kx, 1 - ky, 1 - kx});
+    sc_ph[0].push_back({0, 0, 0, 0});
+    for (int k = 0; k < 4; ++k) {
+        const int ci = kDecC0 >> k, co = ci / 2;
+        put_op(d->up[k], src + off, src + off + (size_t)9 * ci * co, 3, ci, co, up_ph, pyx4);
+        off += (size_t)9 * ci * co + co;
+        put_op(d->sc[k], src + off, src + off + (size_t)ci * co, 1, ci, co, sc_ph, pyx1);
+        off += (size_t)ci * co + co;
+        put_op(d->cv[k], src + off, src + off + (size_t)9 * co * co, 3, co, co, cv_ph, pyx1);
+        off += (size_t)9 * co * co + co;
+    }
+    const size_t tail_w = put(src + off, 25 * 32);
+    off += 25 * 32;
+    const size_t tail_b = put(src + off, 1);
+    ScopedDevice sd(ctx->device);
+    if (hipMalloc(&d->dmem, dev.size() * 4) != hipSuccess ||
+        hipMemcpy(d->dmem, dev.data(), dev.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        if (d->dmem) (void)hipFree(d->dmem);
+        delete d;
+        return fail(SDFNMPC_E_HIP, "vaed: device upload failed");
+    }
+    const float* base = (const float*)d->dmem;
+    d->head_w = base + head_w;
+    d->head_b = base + head_b;
+    d->tail_w = base + tail_w;
+    d->tail_b = base + tail_b;
+    for (int k = 0; k < 4; ++k)
+        for (VaeDecOp* op : {&d->up[k], &d->sc[k], &d->cv[k]}) {
+            op->wpl = (const unsigned short*)(base + op->wpl_off);
+            op->b = base + op->b_off;
+        }
+    *out = d;
+    return SDFNMPC_OK;
+}
+
+extern "C" void sdfnmpc_vae_dec_free(sdfnmpc_vae_dec* d) {
+    if (!d) return;
+    ScopedDevice sd(d->device);
+    if (d->dmem) (void)hipFree(d->dmem);
+    delete d;
+}
+
+extern "C" int sdfnmpc_vae_dec_size_latent(const sdfnmpc_vae_dec* d) { return d ? d->L : -1; }
+extern "C" int sdfnmpc_vae_dec_on_ctx_(const sdfnmpc_vae_dec* d, const sdfnmpc_ctx* ctx) { return d && d->ctx == ctx; }
+
+extern "C" int sdfnmpc_vae_decode(sdfnmpc_ctx* ctx, sdfnmpc_vae_dec* d, int B, const float* latent, int out_h, int out_w,
+                                  float* img, float* logits) {
+    if (!ctx || !d) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_vae_decode");
+    if (B < 0 || out_h < 1 || out_w < 1) return fail(SDFNMPC_E_ARG, "vae_decode: B < 0 or an output size < 1");
+    if (B > 0 && (!latent || !img)) return fail(SDFNMPC_E_ARG, "vae_decode: NULL latent or image");
+    // the activation workspace belongs to the decoder object: calls through it are ordered on one stream only
+    if (d->ctx != ctx) return fail(SDFNMPC_E_ARG, "vae_decode: decoder loaded on another context");
+    if (B == 0) return SDFNMPC_OK;
+    ScopedDevice sd(ctx->device);
+    const int Hl = kDecH0 * 16, Wl = kDecW0 * 16;            // the logits' map, 128 x 240
+    const size_t n_max = (size_t)Hl * Wl * 32;               // values per image of the largest map
+    const int ch = std::min(B, kDecChunk);
+    // workspace: three plane tensors P0..P2 (block input, conv_a output, shortcut / block output, rotating), the
+    // last block's output in fp32 for the tail, and the logits when the caller does not want them
+    const size_t pl_bytes = 3 * n_max * ch * sizeof(unsigned short);
+    HIPCHK(d->ws.ensure(3 * pl_bytes + (n_max + (size_t)Hl * Wl) * ch * sizeof(float)));
+    unsigned short* P[3];
+    for (int i = 0; i < 3; ++i) P[i] = (unsigned short*)((char*)d->ws.p + i * pl_bytes);
+    float* F32 = (float*)((char*)d->ws.p + 3 * pl_bytes);
+    float* LG = F32 + n_max * ch;
+    hipStream_t st = ctx->stream;
+    static const char* const kUp[4] = {"vae_dec_up256", "vae_dec_up128", "vae_dec_up64", "vae_dec_up32"};
+    static const char* const kSc[4] = {"vae_dec_sc256", "vae_dec_sc128", "vae_dec_sc64", "vae_dec_sc32"};
+    static const char* const kCv[4] = {"vae_dec_conv256", "vae_dec_conv128", "vae_dec_conv64", "vae_dec_conv32"};
+    auto gemm = [&](const char* name, const VaeDecOp& op, int nb, const unsigned short* in, int hi, int wi, int hm, int wm,
+                    int ho, int wo, int os, int relu, int fill3, const unsigned short* resid, unsigned short* outp,
+                    float* out32) {
+        VaeDecGemmArgs a{};
+        a.in = in;
+        a.ips = (size_t)nb * hi * wi * op.cin;
+        a.wpl = op.wpl;
+        a.wps = op.wps;
+        a.b = op.b;
+        a.resid = resid;
+        a.rps = a.ops = (size_t)nb * ho * wo * op.cout;
+        a.out = outp;
+        a.out_f32 = out32;
+        a.B = nb; a.Hi = hi; a.Wi = wi; a.Cin = op.cin; a.Hm = hm; a.Wm = wm; a.Ho = ho; a.Wo = wo; a.Cout = op.cout;
+        a.os = os; a.relu = relu; a.fill3 = fill3; a.nphase = op.nphase;
+        memcpy(a.ntaps, op.ntaps, sizeof a.ntaps);
+        memcpy(a.py, op.py, sizeof a.py);
+        memcpy(a.px, op.px, sizeof a.px);
+        memcpy(a.woff, op.woff, sizeof a.woff);
+        memcpy(a.dy, op.dy, sizeof a.dy);
+        memcpy(a.dx, op.dx, sizeof a.dx);
+        return timed(ctx, name, [&] { return launch_vae_dec_gemm(a, st); });
+    };
+    for (int b0 = 0; b0 < B; b0 += ch) {
+        const int nb = std::min(ch, B - b0);
+        unsigned short *X = P[0], *T = P[1], *O = P[2];
+        VaeDecHeadArgs ha{latent + (size_t)b0 * d->L, d->head_w, d->head_b, X, (size_t)nb * kDecF, nb, d->L, kDecF, kDecC0};
+        HIPCHK(timed(ctx, "vae_dec_head", [&] { return launch_vae_dec_head(ha, st); }));
+        int hi = kDecH0, wi = kDecW0;
+        for (int k = 0; k < 4; ++k) {
+            const int ho = 2 * hi, wo = 2 * wi;
+            HIPCHK(gemm(kUp[k], d->up[k], nb, X, hi, wi, hi, wi, ho, wo, 2, 1, 0, nullptr, T, nullptr));
+            HIPCHK(gemm(kSc[k], d->sc[k], nb, X, hi, wi, hi, wi, ho, wo, 2, 0, 1, nullptr, O, nullptr));
+            // the block's output: in place over the shortcut (a thread reads the residual it then overwrites);
+            // the last block's goes out in fp32, for the tail
+            HIPCHK(gemm(kCv[k], d->cv[k], nb, T, ho, wo, ho, wo, ho, wo, 1, 1, 0, O, k < 3 ? O : nullptr,
+                        k < 3 ? nullptr : F32));
+            std::swap(X, O);  // the next block reads O; its conv_a output and shortcut take the other two
+            hi = ho;
+            wi = wo;
+        }
+        float* lg = logits ? logits + (size_t)b0 * Hl * Wl : LG;
+        VaeDecTailArgs ta{F32, d->tail_w, d->tail_b, lg, nb, Hl, Wl, 32};
+        HIPCHK(timed(ctx, "vae_dec_tail", [&] { return launch_vae_dec_tail(ta, st); }));
+        VaeDecResizeArgs ra{lg, img + (size_t)b0 * out_h * out_w, nb, Hl, Wl, out_h, out_w};
+        HIPCHK(timed(ctx, "vae_dec_resize", [&] { return launch_vae_dec_resize(ra, st); }));
+    }
+    return SDFNMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // ground truth from range images (df_truth.hip)
 static int df_img_args(const char* who, sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* o, const float* img, int n_img, int H,
                        int W, const float* points, const int* p_to_i, long long n, DfImg* im) {

@@ -38,6 +38,7 @@ extern "C" int sdfnmpc_scene_pose_args_(const double* B_p_C, const double* B_R_C
                                         sdfn::ScenePoseArgs* out);
 extern "C" int sdfnmpc_scene_pose_launch_(sdfnmpc_ctx* ctx, const sdfn::ScenePoseArgs* a);
 extern "C" int sdfnmpc_vae_on_ctx_(const sdfnmpc_vae* v, const sdfnmpc_ctx* ctx);
+extern "C" int sdfnmpc_vae_dec_on_ctx_(const sdfnmpc_vae_dec* d, const sdfnmpc_ctx* ctx);
 // engine.cpp: the same split for the sensor stage of a perceiving rollout (degradation, then the fused outlier removal)
 extern "C" int sdfnmpc_sensor_args_(const sdfnmpc_sensor_opts* o, float* img, int B, int H, int W, float* scratch,
                                     sdfn::SensorArgs* sa, sdfn::OutlierArgs* oa);
@@ -688,6 +689,96 @@ extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc
             if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pc->scene, &sra, t)) return rc;
             if (sensor)
                 if (int rc = sdfnmpc_sensor_launch_(s->ctx, &sna, &ora, sensor->outlier_rm != 0, pc->phase + k)) return rc;
+            if (!src.is_signed)
+                if (int rc = sdfnmpc_img_sdf_pool(s->ctx, &src, s->B)) return rc;
+            if (int rc = sdfnmpc_pack_refs(s->ctx, &po, &pra)) return rc;
+        }
+        if (a->ref)
+            if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
+        if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
+        if (int rc = step_enqueue(s)) return rc;
+        pa.k = k;
+        if (int rc = sdfnmpc_plant_launch_(s->ctx, &pa)) return rc;
+    }
+    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
+    s->pending = true;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
+                                                  const sdfnmpc_perceive_args* pc, double t0, double dt,
+                                                  const sdfnmpc_sensor_opts* sensor, float* scratch, sdfnmpc_vae_dec* dec) {
+    if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_image_recon");
+    if (!s->has_img)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: no image source set (sdfnmpc_solver_set_sdf_image)");
+    if (!pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: perception (perc) is required");
+    if (!dec) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: no decoder");
+    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
+    sdfn::PlantArgs pa{};
+    sdfnmpc_ref_args ra{};
+    if (int rc = rollout_args(s, a, pa, ra)) return rc;
+    const sdfnmpc_img_sdf_opts& src = s->img_src;
+    sdfn::ScenePoseArgs spa{};
+    sdfn::SceneRenderArgs sra{};
+    sdfnmpc_ref_opts po{};
+    sdfnmpc_ref_args pra{};
+    sdfn::SensorArgs sna{};
+    sdfn::OutlierArgs ora{};
+    if (pc->every < 1 || pc->phase < 0)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
+    if (!pc->scene || !sdfnmpc_scene_on_ctx_(pc->scene, s->ctx))
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: re-imaging needs a scene on the solver's context");
+    if (!pc->vae || !sdfnmpc_vae_on_ctx_(pc->vae, s->ctx) || !sdfnmpc_vae_dec_on_ctx_(dec, s->ctx))
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: the encoder and the decoder must live on the solver's context");
+    if (sdfnmpc_vae_size_latent(pc->vae) != sdfnmpc_vae_dec_size_latent(dec))
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: the encoder and the decoder have different latent sizes");
+    if (pc->h != src.H || pc->w != src.W)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: the render size must equal the source's H x W");
+    if (src.img_of)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: re-imaging renders one image per instance (img_of must be NULL)");
+    if (!pc->images || !pc->latent || !pc->W_p_Bo || !pc->W_R_Bo || !pc->W_p_C || !pc->W_R_C)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: perception needs its workspaces (camera images, latent, poses)");
+    if (pc->images == src.images)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: the camera buffer must not be the source's images");
+    if (pc->img.is_depth && !pc->vae_opts.yz)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: a depth camera needs the Depth2Range table (vae_opts.yz)");
+    if (int rc = sdfnmpc_scene_pose_args_(pc->B_p_C, pc->B_R_C, s->B, s->x0, pc->W_p_Bo, pc->W_R_Bo, pc->W_p_C,
+                                          pc->W_R_C, &spa))
+        return rc;
+    if (int rc = sdfnmpc_scene_render_args_(s->ctx, pc->scene, pc->scene_of, &pc->img, pc->h, pc->w, pc->scale, s->B,
+                                            pc->W_p_C, pc->W_R_C, pc->images, &sra))
+        return rc;
+    // the images are normalised: clip = 1, and Depth2Range exactly when the camera measures depth
+    sdfnmpc_vae_opts vo{s->B, pc->h, pc->w, 0, 1.0f, pc->img.is_depth ? pc->vae_opts.yz : nullptr};
+    po.mode = -2;
+    for (int i = 0; i < 3; ++i) po.B_p_C[i] = pc->B_p_C[i];
+    for (int i = 0; i < 9; ++i) po.B_R_C[i] = pc->B_R_C[i];
+    pra.B = s->B; pra.N = s->N; pra.np = s->np; pra.ny = s->ny; pra.nyN = s->nyN;
+    pra.W_p_Bo = pc->W_p_Bo; pra.W_R_Bo = pc->W_R_Bo; pra.p = s->p;
+    if (sensor) {
+        if ((long long)pc->phase + a->steps > 2147483647LL)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the sensor's frame counter (phase + steps) overflows");
+        if (int rc = sdfnmpc_sensor_args_(sensor, pc->images, s->B, pc->h, pc->w, scratch, &sna, &ora)) return rc;
+    }
+    pa.K = a->steps;
+    pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
+    pa.pts_log = a->pts_log;
+    pa.status = s->status; pa.iters = s->iters;
+    pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
+    SolverDevice sd(s->device);
+    for (int k = 0; k < a->steps; ++k) {
+        if ((k + pc->phase) % pc->every == 0) {  // pose, render into the camera buffer, sensor, encode, decode into the source, pool, pose into p
+            if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
+            // the scene's time at step k, the product rounded on its own as in sdfnmpc_solver_rollout_perceive_at
+            volatile double steps_dt = (double)(pc->phase + k) * dt;
+            const double t = t0 + steps_dt;
+            if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pc->scene, &sra, t)) return rc;
+            if (sensor)
+                if (int rc = sdfnmpc_sensor_launch_(s->ctx, &sna, &ora, sensor->outlier_rm != 0, pc->phase + k)) return rc;
+            if (int rc = sdfnmpc_vae_encode(s->ctx, pc->vae, &vo, pc->images, pc->latent, pc->latent64)) return rc;
+            if (int rc = sdfnmpc_vae_decode(s->ctx, dec, s->B, pc->latent, src.H, src.W, const_cast<float*>(src.images), nullptr))
+                return rc;
             if (!src.is_signed)
                 if (int rc = sdfnmpc_img_sdf_pool(s->ctx, &src, s->B)) return rc;
             if (int rc = sdfnmpc_pack_refs(s->ctx, &po, &pra)) return rc;

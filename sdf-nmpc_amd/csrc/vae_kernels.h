@@ -102,6 +102,64 @@ struct VaeHeadArgs {
     int B, h, w, L;
 };
 
+// ---- decoder (csrc/vae_dec.hip).  Activations are channel-blocked as the encoder's, pre-split into three bf16
+// planes [3][B][C/16][H][W][16] (plane p at p * ps elements; x = hi + mid + lo exactly).
+constexpr int VAE_DEC_LMAX = 1024;  // latent sizes the head kernel holds in LDS
+constexpr int VAE_DEC_TAPS = 9;
+
+// Linear(L, F) + ELU, F = 512 * 8 * 15 in the map's NHWC order (sdf_nmpc/network/vae.py:75-77)
+struct VaeDecHeadArgs {
+    const float* z;      // [B][L]
+    const float* wt;     // [L][F]
+    const float* b;      // [F]
+    unsigned short* out; // planes [3][B][C/16][F/C][16], plane stride ops
+    size_t ops;
+    int B, L, F, C;      // F features = F/C pixels x C channels, feature f = pixel * C + channel
+};
+
+// A transposed convolution (BatchNorm folded) as an implicit GEMM over a tap list, per output phase ph:
+//   out[img][os i + py[ph]][os j + px[ph]][n] = act(b[n] + sum_t in[img][i + dy[ph][t]][j + dx[ph][t]][:] . W_ph,t[:][n]
+//                                                 (+ resid)),   (i, j) over the Hm x Wm grid
+struct VaeDecGemmArgs {
+    const unsigned short* in;   // planes [3][B][Cin/16][Hi][Wi][16], plane stride ips
+    size_t ips;
+    const unsigned short* wpl;  // weight planes (stride wps); phase ph at woff[ph]: [ntaps Cin / 16][Cout][16]
+    size_t wps;
+    const float* b;             // [Cout], 16-byte aligned
+    const unsigned short* resid;  // planes [3][B][Cout/16][Ho][Wo][16] (stride rps) or nullptr; may alias out
+    size_t rps;
+    unsigned short* out;        // planes [3][B][Cout/16][Ho][Wo][16] (stride ops), and / or
+    size_t ops;
+    float* out_f32;             // fp32 channel-quad planes [B][Cout / 4][Ho][Wo][4] (the tail's input)
+    int B, Hi, Wi, Cin, Hm, Wm, Ho, Wo, Cout, os, relu;
+    int fill3;                  // also write b[n] to the three other pixels of each cell's 2 x 2 output block
+    int nphase;
+    int ntaps[4], py[4], px[4];
+    unsigned woff[4];
+    signed char dy[4][VAE_DEC_TAPS], dx[4][VAE_DEC_TAPS];
+};
+
+// ConvTranspose2d(C, 1, 5, s1, p2) with bias -> logits
+struct VaeDecTailArgs {
+    const float* in;     // fp32 channel-quad planes [B][C / 4][H][W][4]
+    const float* w;      // [5][5][C] (ky, kx, ci)
+    const float* b;      // [1]
+    float* logits;       // [B][H][W]
+    int B, H, W, C;
+};
+
+// bilinear resize (align_corners false) + sigmoid
+struct VaeDecResizeArgs {
+    const float* logits; // [B][Hi][Wi]
+    float* img;          // [B][H][W]
+    int B, Hi, Wi, H, W;
+};
+
+hipError_t launch_vae_dec_head(const VaeDecHeadArgs& a, hipStream_t s);
+hipError_t launch_vae_dec_gemm(const VaeDecGemmArgs& a, hipStream_t s);
+hipError_t launch_vae_dec_tail(const VaeDecTailArgs& a, hipStream_t s);
+hipError_t launch_vae_dec_resize(const VaeDecResizeArgs& a, hipStream_t s);
+
 hipError_t launch_vae_pre(const VaePreArgs& a, hipStream_t s);
 hipError_t launch_vae_stem(const VaeStemArgs& a, int n_cu, hipStream_t s);  // n_cu: the device's CUs (sdfnmpc_ctx::n_cu)
 hipError_t launch_vae_conv(const VaeConvArgs& a, int ks, int stride, hipStream_t s);

@@ -11,6 +11,16 @@ counts: h[2] = max_df with the flag on).
 
     timeout 900 python tools/image_sdf_probe.py --B 256 --N 40
     timeout 900 python tools/image_sdf_probe.py --B 1024 --N 40 --K 10 --reps 1
+    timeout 900 python tools/image_sdf_probe.py --reconstruct --B 1024 --N 40 --K 10 --reps 1
+
+--reconstruct flies the rung between the camera image and the network instead: the field of the image the VAE's latent
+retains (Nmpc.set_sdf_image(..., reconstruct=vae), sdfnmpc_solver_rollout_image_recon), signed and unsigned, beside the
+network, the camera image and the exact scene, and prints the reconstructing rollout's ms per step beside the
+host-driven loop of the same pieces (render_from_state, set_sdf_image(reconstruct=), set_pose_device, gen_refs_device,
+solve, plant_step) from the same run.  A clearance lost with the reconstruction is the bottleneck's; one lost only below
+it is the NeuralDF's.  WITH SYNTHETIC VAE WEIGHTS THE RECONSTRUCTION IS NOISE in about [0.27, 0.77] dmax, so the
+recon arms' clearance numbers mean nothing until a trained checkpoint is converted (vae.from_torchscript /
+decoder_from_torchscript); the timings do not depend on the weights.
 Prints a summary and a JSON line.  Diagnostic, not a test."""
 import argparse
 import json
@@ -34,6 +44,7 @@ from rollout_probe import controller
 
 Q = (0, 5, 25, 50, 75, 95, 100)
 ARMS = ("net", "img_signed", "img_unsigned", "img_signed_sensor", "img_unsigned_sensor", "exact")
+RECON_ARMS = ("net", "img_signed", "recon_signed", "recon_unsigned", "exact")
 KERNELS = ("sdf_hoist", "sdf_mlp", "img_sdf_rows", "scene_sdf_rows", "scene_render", "sensor", "minpool5", "linearize",
            "rti_qp_pack", "rti_qp")
 
@@ -50,6 +61,11 @@ def fly(cfg, a, arm, timed=False, keep=False):
         kw = dict(scene=scene, vae=vae, perceive_every=a.every, img_shape=shape)
     elif arm == "exact":
         n.set_sdf_scene(scene)
+    elif arm.startswith("recon"):
+        vae = VaeWrapper(cfg, batch=a.B, ctx=ctx, decoder=True)
+        n.set_sdf_image(scene.render_from_state(x0, cfg, shape, normalized=True), signed="unsigned" not in arm,
+                        reconstruct=vae)
+        kw = dict(scene=scene, perceive_every=a.every, img_shape=shape)
     else:
         n.set_sdf_image(scene.render_from_state(x0, cfg, shape, normalized=True), signed="unsigned" not in arm)
         kw = dict(scene=scene, perceive_every=a.every, img_shape=shape)
@@ -89,9 +105,72 @@ def fly(cfg, a, arm, timed=False, keep=False):
                 "rows": a.B * (a.N + 1)}
     if vae is not None:
         vae.vae.close()
+        if vae.dec is not None:
+            vae.dec.close()
     scene.close()
     n.ocp.close()
     return r, ms, stats, rows
+
+
+def host_loop_recon(cfg, a, signed=True):
+    """The loop a user writes around solve() with a reconstructing source, on a fresh controller: ms per step."""
+    n, x0, wps = controller(cfg, a.B, 1)
+    ctx = n.ocp.ctx
+    scene = Scene(ctx, forest(16))
+    shape = tuple(int(v) for v in a.shape)
+    vae = VaeWrapper(cfg, batch=a.B, ctx=ctx, decoder=True)
+    plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]))
+    x = np.reshape(x0, (a.B, 10)).copy()
+    dx = _lib.DeviceArray(ctx, (a.B, 10))
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    for k in range(a.K):
+        n.set_x0(x if a.B > 1 else x[0])
+        if k % a.every == 0:
+            img = scene.render_from_state(x, cfg, shape, normalized=True)
+            n.set_sdf_image(img, signed=signed, reconstruct=vae)
+            n.set_pose_device(img.pose["W_p_Bo"], img.pose["W_R_Bo"])
+        n.gen_refs_device("wps", wps=wps)
+        n.solve()
+        dx.upload(x)
+        _lib.plant_step(ctx, plant, a.B, dx, n.ocp.field("u0"), dx)
+        x = dx.numpy()
+    ms = (time.perf_counter() - t0) / a.K * 1e3
+    vae.vae.close()
+    vae.dec.close()
+    scene.close()
+    n.ocp.close()
+    return ms
+
+
+def main_reconstruct(cfg, a):
+    res = {"B": a.B, "N": a.N, "K": a.K, "every": a.every, "shape": list(a.shape), "reconstruct": True}
+    ms = {k: [] for k in RECON_ARMS + ("recon_signed_host_loop",)}
+    runs = {}
+    for rep in range(a.reps + 1):  # repetition 0 warms up; the arms alternate inside every repetition
+        for arm in RECON_ARMS:
+            r, t, _, _ = fly(cfg, a, arm)
+            runs[arm] = r
+            if rep:
+                ms[arm].append(t)
+        t = host_loop_recon(cfg, a)
+        if rep:
+            ms["recon_signed_host_loop"].append(t)
+    print(f"B={a.B} N={a.N} K={a.K} images {a.shape[0]} x {a.shape[1]}: ms per control step (best of {a.reps}), min clearance "
+          f"over the batch at percentiles {Q}")
+    for arm in RECON_ARMS:
+        mc = runs[arm].clearance.min(axis=1)
+        res[f"{arm}_ms_per_step"] = min(ms[arm])
+        res[f"{arm}_min_clearance_percentiles"] = dict(zip(map(str, Q), np.percentile(mc, Q).round(4).tolist()))
+        res[f"{arm}_collided"] = int((mc < 0).sum())
+        print(f"  {arm:22s} {res[f'{arm}_ms_per_step']:.3f} ms/step  clearance "
+              f"{list(res[f'{arm}_min_clearance_percentiles'].values())}  collided {res[f'{arm}_collided']}")
+    res["recon_signed_host_loop_ms_per_step"] = min(ms["recon_signed_host_loop"])
+    print(f"reconstructing rollout {res['recon_signed_ms_per_step']:.3f} ms/step against the host-driven loop of the same "
+          f"pieces {res['recon_signed_host_loop_ms_per_step']:.3f} ms/step")
+    print("NOTE: synthetic VAE weights reconstruct noise in about [0.27, 0.77] dmax: the recon arms' clearance numbers mean "
+          "nothing until a trained checkpoint is converted; the timings hold")
+    print(json.dumps(res))
 
 
 def main():
@@ -102,9 +181,12 @@ def main():
     ap.add_argument("--every", type=int, default=1)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--shape", type=int, nargs=2, default=(270, 480), help="image size (multiples of 5)")
+    ap.add_argument("--reconstruct", action="store_true", help="the rung of the VAE's reconstruction (see above)")
     a = ap.parse_args()
     warnings.simplefilter("ignore")
     cfg = Config(mpc__N=a.N)
+    if a.reconstruct:
+        return main_reconstruct(cfg, a)
     res = {"B": a.B, "N": a.N, "K": a.K, "every": a.every, "shape": list(a.shape)}
     ms = {k: [] for k in ARMS}
     runs = {}
