@@ -341,7 +341,7 @@ int sdfnmpc_ctx_set_tile_rows(sdfnmpc_ctx* ctx, int rows);
 /* per-kernel HIP-event timing on the context stream (off by default) */
 int sdfnmpc_ctx_enable_timing(sdfnmpc_ctx* ctx, int on);
 /* kernel: "sdf_mlp", "sdf_hoist", "linearize", "rti_qp", "plant", "scene_render", "scene_pose", "scene_dist",
- * "scene_render_dyn", "scene_dist_dyn", "morph", "outlier_rm", "sensor_degrade", ...; synchronizes the stream(s) */
+ * "scene_render_dyn", "scene_dist_dyn", "scene_render_grid", "scene_dist_grid", "scene_sdf_rows_grid", "morph", "outlier_rm", "sensor_degrade", ...; synchronizes the stream(s) */
 int sdfnmpc_ctx_kernel_stats(sdfnmpc_ctx* ctx, const char* kernel, double* total_ms, long long* launches);
 int sdfnmpc_ctx_reset_stats(sdfnmpc_ctx* ctx);
 
@@ -644,7 +644,8 @@ typedef struct {
 int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args);
 
 /* ---- analytic scenes (csrc/scene.hip) ----
- * A scene is a union of up to SDFNMPC_SCENE_MAX_PRIMS primitives in the world frame (z up, as in the models):
+ * A scene is a union of up to SDFNMPC_SCENE_MAX_PRIMS primitives (sdfnmpc_scene_create_large below: up to
+ * SDFNMPC_SCENE_LARGE_MAX_PRIMS static ones, with a grid index) in the world frame (z up, as in the models):
  *   SDFNMPC_PRIM_SPHERE    a = (cx, cy, cz, r)
  *   SDFNMPC_PRIM_BOX       a = (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z), axis-aligned
  *   SDFNMPC_PRIM_CYLINDER  a = (cx, cy, r, z0, z1), capped, along z
@@ -731,6 +732,34 @@ int sdfnmpc_scene_render_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const 
  * The times are the caller's to keep finite, as the points are. */
 int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const double* points, const int* p_to_scene,
                               const double* times, long long n, double* out);
+
+/* ---- scenes of many primitives: a uniform-grid index (csrc/scene_grid.hip) ----
+ * sdfnmpc_scene_create_large is sdfnmpc_scene_create for S scenes of 0..SDFNMPC_SCENE_LARGE_MAX_PRIMS static
+ * primitives each (the same kinds, checks and fp32 rounding; no motion records), with a uniform grid per scene built
+ * on the host inside the call (synchronous).  cell > 0: the grid's cell edge in metres (rounded to fp32).  cell <= 0:
+ * the default, a function of the scene's primitives only -- cbrt(V / (4 n)) for the volume V of the n primitives'
+ * bounding box, about 4 cells per primitive, and not below (E + R / 1024) / 250 for the box's longest edge E and the
+ * largest absolute coordinate R, which keeps every axis at 1..256 cells; a forest of upright cylinders gets a few
+ * layers in z.  A primitive is listed in every cell that its bounding box inflated by cell / 1024 + R / 4096 overlaps;
+ * the grid's box is the bounding box padded by twice that.  A scene without primitives gets an empty grid.
+ * The handle is used like any other: sdfnmpc_scene_render(_at), sdfnmpc_scene_distance(_at), sdfnmpc_scene_sdf_rows,
+ * sdfnmpc_lin_args.sdf_scene, sdfnmpc_solver_set_sdf_scene and every rollout that takes a scene dispatch on it
+ * (sdfnmpc_scene_is_indexed: 1, else 0) and launch the grid kernels -- "scene_render_grid", "scene_dist_grid",
+ * "scene_sdf_rows_grid" in sdfnmpc_ctx_kernel_stats -- which visit only the cells along a ray or around a point and
+ * return, bit for bit, what the brute-force kernels would return over all primitives of the scene, for a camera
+ * within about 100 times the scene's size of it (farther away a pixel may differ; no read leaves the scene's arrays
+ * for any pose or point).  An indexed set is static: times are ignored, sdfnmpc_scene_is_dynamic is 0.
+ * SDFNMPC_E_ARG (nothing is allocated): what sdfnmpc_scene_create refuses, a count above
+ * SDFNMPC_SCENE_LARGE_MAX_PRIMS, a non-finite cell, a grid of more than SDFNMPC_SCENE_GRID_MAX_AXIS cells along an
+ * axis or SDFNMPC_SCENE_GRID_MAX_CELLS cells in a scene, or more than SDFNMPC_SCENE_GRID_MAX_ITEMS cells plus
+ * cell-list entries in the set. */
+#define SDFNMPC_SCENE_LARGE_MAX_PRIMS 65536
+#define SDFNMPC_SCENE_GRID_MAX_AXIS 1024
+#define SDFNMPC_SCENE_GRID_MAX_CELLS (1 << 22)
+#define SDFNMPC_SCENE_GRID_MAX_ITEMS (1 << 26)
+int sdfnmpc_scene_create_large(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims, double cell,
+                               sdfnmpc_scene** out);
+int sdfnmpc_scene_is_indexed(const sdfnmpc_scene* scene);
 
 /* sdfnmpc_solver_rollout with perception inside the loop.  Before step k with (k + phase) % every == 0 it enqueues, on the
  * solver's stream and in this order: (a) sdfnmpc_scene_pose from the solver's x0 field; (b) sdfnmpc_scene_render of

@@ -46,6 +46,7 @@ SYMBOLS = [
     "sdfnmpc_solver_rollout_scene_sdf",
     "sdfnmpc_img_sdf_rows", "sdfnmpc_img_sdf_pool", "sdfnmpc_solver_set_sdf_image", "sdfnmpc_solver_rollout_image_sdf",
     "sdfnmpc_solver_rollout_image_recon",
+    "sdfnmpc_scene_create_large", "sdfnmpc_scene_is_indexed",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -279,6 +280,8 @@ def load():
         "sdfnmpc_solver_rollout_perceive": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC)]),
         "sdfnmpc_scene_create_moving": (i, [vp, i, P(i), P(PrimC), P(PrimMotionC), P(vp)]),
         "sdfnmpc_scene_is_dynamic": (i, [vp]),
+        "sdfnmpc_scene_create_large": (i, [vp, i, P(i), P(PrimC), d, P(vp)]),
+        "sdfnmpc_scene_is_indexed": (i, [vp]),
         "sdfnmpc_scene_render_at": (i, [vp, vp, vp, P(ImgOptsC), i, i, f, i, vp, vp, d, vp]),
         "sdfnmpc_scene_distance_at": (i, [vp, vp, vp, vp, vp, ll, vp]),
         "sdfnmpc_solver_rollout_perceive_at": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d]),
@@ -827,6 +830,20 @@ def scene_create(ctx: "Context", counts, prims, motion=None):
         mo[k].amp[:] = [float(v) for v in m.get("amp", (0.0, 0.0, 0.0))]
         mo[k].yaw_rate, mo[k].omega, mo[k].phase = (float(m.get(n, 0.0)) for n in ("yaw_rate", "omega", "phase"))
     _check(load().sdfnmpc_scene_create_moving(ctx.h, len(counts), cn, pr, mo, C.byref(h)))
+    return h
+
+
+def scene_create_large(ctx: "Context", counts, prims, cell: float = 0.0):
+    """sdfnmpc_scene_create_large: scene_create for scenes of up to 65536 static primitives each, with a uniform grid
+    of cell edge `cell` [m] (<= 0: the library's default)."""
+    cn = (C.c_int * len(counts))(*[int(c) for c in counts])
+    pr = (PrimC * max(len(prims), 1))()
+    for k, (kind, vals) in enumerate(prims):
+        pr[k].kind = int(kind)
+        for j, v in enumerate(vals):
+            pr[k].a[j] = float(v)
+    h = C.c_void_p()
+    _check(load().sdfnmpc_scene_create_large(ctx.h, len(counts), cn, pr, float(cell), C.byref(h)))
     return h
 
 

@@ -1297,6 +1297,12 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
     return SDFNMPC_OK;
 }
 
+// the scene's rows kernel: an indexed set takes the grid kernel, everything else the launch it has always taken
+static hipError_t scene_sdf_rows_enqueue(sdfnmpc_ctx* ctx, const SceneSdfArgs& a) {
+    if (a.sc.ghdr) return timed(ctx, "scene_sdf_rows_grid", [&] { return launch_scene_sdf_rows_grid(a, ctx->stream); });
+    return timed(ctx, "scene_sdf_rows", [&] { return launch_scene_sdf_rows(a, ctx->stream); });
+}
+
 // the option check + argument block of sdfnmpc_scene_sdf_rows (below, with the scenes): nothing is launched
 extern "C" int sdfnmpc_scene_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int B, int N, int np,
                                        const double* x, const double* p, double* h, double* Jh, SceneSdfArgs* out);
@@ -1439,7 +1445,7 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
     if (no_sdf) {  // no constraint or cost reads the network: the linearisation alone, then the pack
         HIPCHK(timed(ctx, "linearize", [&] { return launch_linearize(la, ctx->stream); }, ctx->stream));
         if (a->sdf_scene)  // the SDF row from the scene's closed forms, between the linearisation and the pack
-            HIPCHK(timed(ctx, "scene_sdf_rows", [&] { return launch_scene_sdf_rows(ssa, ctx->stream); }));
+            HIPCHK(scene_sdf_rows_enqueue(ctx, ssa));
         if (a->sdf_image)  // or from the field of the camera image
             if (int rc_ = img_sdf_launch(ctx, isa)) return rc_;
         return finish_pack();
@@ -2496,6 +2502,8 @@ struct sdfnmpc_scene {
     void* dmem = nullptr;  // count [S] | ScenePrimD [S][32] | ScenePrimF [S][32] | dynamic: ScenePrimDyn [S][32]
     SceneDev dev{};
     const ScenePrimDyn* dyn = nullptr;  // non-NULL: a dynamic set (some primitive is oriented or moves)
+    // an indexed set (sdfnmpc_scene_create_large; dev.ghdr != nullptr): count [S] | SceneGridHdr [S] | ScenePrimD [total]
+    // | ScenePrimF [total] | cell_start | cell_items, every block at a multiple of 16 bytes
 };
 
 extern "C" int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
@@ -2608,6 +2616,179 @@ extern "C" int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* c
     return SDFNMPC_OK;
 }
 
+// kind, values and ranges of one primitive, as sdfnmpc_scene_create checks them; na = the number of values read
+static int scene_prim_check(const sdfnmpc_prim* p, int* na) {
+    const double* a = p->a;
+    bool ok = false;
+    if (p->kind == SDFNMPC_PRIM_SPHERE) { *na = 4; ok = a[3] > 0.0; }
+    else if (p->kind == SDFNMPC_PRIM_BOX) { *na = 6; ok = a[0] < a[3] && a[1] < a[4] && a[2] < a[5]; }
+    else if (p->kind == SDFNMPC_PRIM_CYLINDER) { *na = 5; ok = a[2] > 0.0 && a[3] < a[4]; }
+    else return fail(SDFNMPC_E_ARG, "scene: unknown primitive kind (0 sphere, 1 box, 2 cylinder)");
+    for (int k = 0; k < *na; ++k) ok = ok && std::isfinite(a[k]);
+    if (!ok) return fail(SDFNMPC_E_ARG, "scene: a primitive needs finite values, a radius > 0 and lo < hi");
+    return SDFNMPC_OK;
+}
+
+static void scene_prim_bbox(const sdfnmpc_prim& p, double* lo, double* hi) {
+    const double* a = p.a;
+    if (p.kind == SDFNMPC_PRIM_SPHERE) {
+        for (int k = 0; k < 3; ++k) { lo[k] = a[k] - a[3]; hi[k] = a[k] + a[3]; }
+    } else if (p.kind == SDFNMPC_PRIM_BOX) {
+        for (int k = 0; k < 3; ++k) { lo[k] = a[k]; hi[k] = a[3 + k]; }
+    } else {
+        for (int k = 0; k < 2; ++k) { lo[k] = a[k] - a[2]; hi[k] = a[k] + a[2]; }
+        lo[2] = a[3]; hi[2] = a[4];
+    }
+}
+
+// Static scenes of up to SDFNMPC_SCENE_LARGE_MAX_PRIMS primitives with a uniform grid each, built here on the host
+// (the layout: SceneGridHdr, scene_kernels.h; why the inflation and the padding: scene_grid.hip)
+extern "C" int sdfnmpc_scene_create_large(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
+                                          double cell, sdfnmpc_scene** out) {
+    if (!ctx || !count || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create_large");
+    *out = nullptr;
+    if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "scene: S must be 1..2^20");
+    if (!std::isfinite(cell)) return fail(SDFNMPC_E_ARG, "scene: the grid's cell size must be finite (<= 0: the default)");
+    long long total = 0;
+    for (int s = 0; s < S; ++s) {
+        if (count[s] < 0 || count[s] > SCENE_LARGE_MAX_PRIMS)
+            return fail(SDFNMPC_E_ARG, "scene: at most 65536 primitives per indexed scene (and no negative count)");
+        total += count[s];
+    }
+    if (total > 0 && !prims) return fail(SDFNMPC_E_ARG, "scene: NULL primitives");
+    if (total > 2147483647LL / 64) return fail(SDFNMPC_E_ARG, "scene: more than 2^25 primitives in an indexed set");
+    for (long long i = 0; i < total; ++i) {
+        int na;
+        if (int rc = scene_prim_check(prims + i, &na)) return rc;
+    }
+    std::vector<SceneGridHdr> hdr((size_t)S);
+    std::vector<int> cell_start, cell_items;
+    const char* too_big = "scene: the grid is too large (at most 1024 cells per axis, 2^22 cells per scene, 2^26 cells "
+                          "and cell-list entries per set): choose a larger cell";
+    const sdfnmpc_prim* p = prims;
+    for (int s = 0; s < S; p += count[s], ++s) {
+        SceneGridHdr& G = hdr[(size_t)s];
+        const int n = count[s];
+        G = SceneGridHdr{};
+        G.count = n;
+        G.prim_off = (int)(p - prims);
+        G.cell_off = (int)cell_start.size();
+        if (n == 0) {  // an empty grid: one cell without entries
+            G.cell = G.inv = 1.0;
+            G.n[0] = G.n[1] = G.n[2] = 1;
+            cell_start.push_back((int)cell_items.size());
+            cell_start.push_back((int)cell_items.size());
+            continue;
+        }
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int i = 0; i < n; ++i) {
+            double bl[3], bh[3];
+            scene_prim_bbox(p[i], bl, bh);
+            for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], bl[k]); hi[k] = std::max(hi[k], bh[k]); }
+        }
+        double R = 0.0, ext_max = 0.0, vol = 1.0;
+        for (int k = 0; k < 3; ++k) {
+            R = std::max(R, std::max(std::fabs(lo[k]), std::fabs(hi[k])));
+            ext_max = std::max(ext_max, hi[k] - lo[k]);
+            vol *= hi[k] - lo[k];
+        }
+        // the default: cubes of the volume of the primitives' bounding box over 4 n, about 4 cells per primitive, and
+        // not smaller than 1 / 250 of the padded box's longest edge (at most 256 cells per axis)
+        double c = cell > 0.0 ? cell : std::max(std::cbrt(vol / (4.0 * n)), (ext_max + R * 0x1p-10) / 250.0);
+        c = (double)(float)c;
+        if (!(c > 0.0) || !std::isfinite(c) || !std::isfinite(R) || !std::isfinite(ext_max))
+            return fail(SDFNMPC_E_ARG, "scene: the grid's cell size or the scene's extent is out of fp32 range");
+        const double infl = c * 0x1p-10 + R * 0x1p-12;
+        long long cells = 1;
+        for (int k = 0; k < 3; ++k) {
+            float o = (float)(lo[k] - 2.0 * infl);
+            if ((double)o > lo[k] - 2.0 * infl) o = std::nextafterf(o, -INFINITY);
+            G.org[k] = (double)o;
+            const double top = hi[k] + 2.0 * infl;
+            const double m = std::ceil((top - G.org[k]) / c);
+            if (!(m <= (double)SCENE_GRID_MAX_AXIS)) return fail(SDFNMPC_E_ARG, too_big);
+            G.n[k] = std::max(1, (int)m);
+            while (G.org[k] + G.n[k] * c < top) ++G.n[k];
+            if (G.n[k] > SCENE_GRID_MAX_AXIS) return fail(SDFNMPC_E_ARG, too_big);
+            cells *= G.n[k];
+        }
+        G.cell = c;
+        G.inv = 1.0 / c;
+        if (cells > SCENE_GRID_MAX_CELLS || (long long)cell_start.size() + cells + 1 > SCENE_GRID_MAX_ITEMS)
+            return fail(SDFNMPC_E_ARG, too_big);
+        // the cells of every primitive's inflated box, counted, then filled in ascending primitive order
+        std::vector<int> box((size_t)n * 6);
+        std::vector<long long> cnt((size_t)cells + 1, 0);
+        long long listed = 0;
+        for (int i = 0; i < n; ++i) {
+            double bl[3], bh[3];
+            scene_prim_bbox(p[i], bl, bh);
+            int* q = &box[(size_t)i * 6];
+            for (int k = 0; k < 3; ++k) {
+                q[k] = std::min(std::max((int)std::floor((bl[k] - infl - G.org[k]) / c), 0), G.n[k] - 1);
+                q[3 + k] = std::min(std::max((int)std::floor((bh[k] + infl - G.org[k]) / c), 0), G.n[k] - 1);
+            }
+            listed += (long long)(q[3] - q[0] + 1) * (q[4] - q[1] + 1) * (q[5] - q[2] + 1);
+            if ((long long)cell_items.size() + listed > SCENE_GRID_MAX_ITEMS) return fail(SDFNMPC_E_ARG, too_big);
+            for (int z = q[2]; z <= q[5]; ++z)
+                for (int y = q[1]; y <= q[4]; ++y)
+                    for (int x = q[0]; x <= q[3]; ++x) ++cnt[(size_t)((long long)(z * G.n[1] + y) * G.n[0] + x) + 1];
+        }
+        const size_t base = cell_items.size(), cs0 = cell_start.size();
+        cell_items.resize(base + (size_t)listed);
+        cell_start.resize(cs0 + (size_t)cells + 1);
+        for (long long id = 0; id < cells; ++id) cnt[(size_t)id + 1] += cnt[(size_t)id];
+        for (long long id = 0; id <= cells; ++id) cell_start[cs0 + (size_t)id] = (int)(base + cnt[(size_t)id]);
+        for (int i = 0; i < n; ++i) {
+            const int* q = &box[(size_t)i * 6];
+            for (int z = q[2]; z <= q[5]; ++z)
+                for (int y = q[1]; y <= q[4]; ++y)
+                    for (int x = q[0]; x <= q[3]; ++x)
+                        cell_items[base + (size_t)cnt[(size_t)((long long)(z * G.n[1] + y) * G.n[0] + x)]++] = i;
+        }
+    }
+    // the device image
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_hdr = up16((size_t)S * sizeof(int));
+    const size_t o_pd = up16(o_hdr + (size_t)S * sizeof(SceneGridHdr));
+    const size_t o_pf = up16(o_pd + (size_t)total * sizeof(ScenePrimD));
+    const size_t o_cs = up16(o_pf + (size_t)total * sizeof(ScenePrimF));
+    const size_t o_ci = up16(o_cs + cell_start.size() * sizeof(int));
+    std::vector<char> host(up16(o_ci + cell_items.size() * sizeof(int)) + 16, 0);
+    std::memcpy(host.data(), count, (size_t)S * sizeof(int));
+    std::memcpy(host.data() + o_hdr, hdr.data(), (size_t)S * sizeof(SceneGridHdr));
+    ScenePrimD* hd = (ScenePrimD*)(host.data() + o_pd);
+    ScenePrimF* hf = (ScenePrimF*)(host.data() + o_pf);
+    for (long long i = 0; i < total; ++i) {
+        int na = 0;
+        (void)scene_prim_check(prims + i, &na);
+        hd[i].kind = hf[i].kind = prims[i].kind;
+        for (int k = 0; k < na; ++k) {
+            hd[i].a[k] = prims[i].a[k];
+            hf[i].a[k] = (float)prims[i].a[k];
+        }
+    }
+    std::memcpy(host.data() + o_cs, cell_start.data(), cell_start.size() * sizeof(int));
+    if (!cell_items.empty()) std::memcpy(host.data() + o_ci, cell_items.data(), cell_items.size() * sizeof(int));
+    ScopedDevice sd(ctx->device);
+    auto* sc = new sdfnmpc_scene();
+    sc->device = ctx->device; sc->ctx = ctx; sc->S = S;
+    hipError_t e = hipMalloc(&sc->dmem, host.size());
+    if (e == hipSuccess) e = hipMemcpy(sc->dmem, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (sc->dmem) (void)hipFree(sc->dmem);
+        delete sc;
+        return fail(SDFNMPC_E_HIP, std::string("scene upload: ") + hipGetErrorString(e));
+    }
+    char* d = (char*)sc->dmem;
+    sc->dev = SceneDev{S, (const int*)d, (const ScenePrimF*)(d + o_pf), (const ScenePrimD*)(d + o_pd),
+                       (const SceneGridHdr*)(d + o_hdr), (const int*)(d + o_cs), (const int*)(d + o_ci)};
+    *out = sc;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_is_indexed(const sdfnmpc_scene* sc) { return sc && sc->dev.ghdr; }
+
 extern "C" void sdfnmpc_scene_free(sdfnmpc_scene* sc) {
     if (!sc) return;
     ScopedDevice sd(sc->device);
@@ -2654,6 +2835,10 @@ extern "C" int sdfnmpc_scene_render_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene*
 
 extern "C" int sdfnmpc_scene_render_launch_(sdfnmpc_ctx* ctx, const SceneRenderArgs* a) {
     ScopedDevice sd(ctx->device);
+    if (a->sc.ghdr) {  // an indexed set
+        HIPCHK(timed(ctx, "scene_render_grid", [&] { return launch_scene_render_grid(*a, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     HIPCHK(timed(ctx, "scene_render", [&] { return launch_scene_render(*a, ctx->stream); }));
     return SDFNMPC_OK;
 }
@@ -2729,6 +2914,10 @@ extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* 
     if (!points || !out) return fail(SDFNMPC_E_ARG, "scene_distance: NULL points or output");
     SceneDistArgs a{sc->dev, points, p_to_scene, n, std::max(1LL, n / sc->S), out};
     ScopedDevice sd(ctx->device);
+    if (a.sc.ghdr) {  // an indexed set is static: the times do not matter
+        HIPCHK(timed(ctx, "scene_dist_grid", [&] { return launch_scene_distance_grid(a, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (sc->dyn) {
         const SceneDistDynArgs da{a, sc->dyn, times};
         HIPCHK(timed(ctx, "scene_dist_dyn", [&] { return launch_scene_distance_dyn(da, ctx->stream); }));
@@ -2764,7 +2953,7 @@ extern "C" int sdfnmpc_scene_sdf_rows(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_
     if (int rc = sdfnmpc_scene_sdf_args_(ctx, o, B, N, np, x, p, h, Jh, &a)) return rc;
     if (B == 0) return SDFNMPC_OK;
     ScopedDevice sd(ctx->device);
-    HIPCHK(timed(ctx, "scene_sdf_rows", [&] { return launch_scene_sdf_rows(a, ctx->stream); }));
+    HIPCHK(scene_sdf_rows_enqueue(ctx, a));
     return SDFNMPC_OK;
 }
 

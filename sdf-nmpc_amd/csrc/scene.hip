@@ -18,32 +18,13 @@
 // Every primitive is convex, so a ray meets it in one parameter interval [tn, tf]: the intersection of the
 // slab intervals (box), of the quadratic's root interval (sphere), or of both (cylinder: side wall and caps).
 // The ray hits when tf >= max(tn, 0), at t = max(tn, 0): an origin inside gives t = 0 for every ray.  No
-// atomics, no cross-lane traffic: a pixel depends on its instance's pose and scene only.
+// atomics, no cross-lane traffic: a pixel depends on its instance's pose and scene only.  The per-primitive work
+// (prim_ray_hit, prim_distance) is in scene_dev.h, shared with the grid kernels of scene_grid.hip.
 #include "scene_dev.h"
 
 namespace sdfn {
 
 namespace {
-
-__device__ __forceinline__ float frcp(float a) { return __builtin_amdgcn_rcpf(a); }    // 1 ulp
-__device__ __forceinline__ float fsqrt(float a) { return __builtin_amdgcn_sqrtf(a); }  // 1 ulp
-
-// the root interval of t^2 - 2 b t + c = 0 with h = sqrt(b^2 - c) given (the caller forms the discriminant
-// without cancellation): the root of larger magnitude is q = b + sign(b) h, the other one c / q
-__device__ __forceinline__ void root_interval(float b, float c, float h, float& tn, float& tf) {
-    const float q = b + copysignf(h, b);
-    const float r = c * frcp(q);  // q == 0 only with b == h == 0, c == 0: a double root at 0 (fmin / fmax drop the NaN)
-    tn = fminf(q, r);
-    tf = fmaxf(q, r);
-}
-
-// slab interval of one axis: (lo - o) / d and (hi - o) / d in either order; d == 0 gives -inf / +inf inside
-// the slab and an empty interval outside it
-__device__ __forceinline__ void slab(float lo, float hi, float o, float inv_d, float& tn, float& tf) {
-    const float t1 = (lo - o) * inv_d, t2 = (hi - o) * inv_d;
-    tn = fmaxf(tn, fminf(t1, t2));
-    tf = fminf(tf, fmaxf(t1, t2));
-}
 
 __global__ __launch_bounds__(SCENE_BLOCK) void scene_render_kernel(SceneRenderArgs A) {
     extern __shared__ float tab[];  // spherical: col [2 W] (cos, sin of the azimuth) | row [2 H] (elevation)
@@ -94,38 +75,8 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_render_kernel(SceneRenderAr
 
     float best = INFINITY;
     for (int i = 0; i < cnt; ++i) {  // wave-uniform: one scene per block
-        const float a0 = prim[i].a[0], a1 = prim[i].a[1], a2 = prim[i].a[2], a3 = prim[i].a[3], a4 = prim[i].a[4],
-                    a5 = prim[i].a[5];
-        const int kind = prim[i].kind;
-        float tn = -INFINITY, tf = INFINITY;
-        if (kind == 0) {  // sphere: centre a0..a2, radius a3
-            const float ex = a0 - ox, ey = a1 - oy, ez = a2 - oz;
-            const float bb = fmaf(ex, dx, fmaf(ey, dy, ez * dz));
-            const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey), wz = fmaf(-bb, dz, ez);  // foot of the centre
-            const float h2 = fmaf(a3, a3, -fmaf(wx, wx, fmaf(wy, wy, wz * wz)));                 // r^2 - |w|^2
-            const float cc = fmaf(ex, ex, fmaf(ey, ey, ez * ez)) - a3 * a3;
-            if (h2 >= 0.f) root_interval(bb, cc, fsqrt(h2), tn, tf);
-            else tf = -INFINITY;
-        } else if (kind == 1) {  // box: lo a0..a2, hi a3..a5
-            slab(a0, a3, ox, ix, tn, tf);
-            slab(a1, a4, oy, iy, tn, tf);
-            slab(a2, a5, oz, iz, tn, tf);
-        } else {  // capped cylinder along z: centre a0, a1, radius a2, z in [a3, a4]
-            const float ex = a0 - ox, ey = a1 - oy;
-            const float aa = fmaf(dx, dx, dy * dy), e2 = fmaf(ex, ex, ey * ey);
-            if (aa > 1e-12f) {  // the side wall's quadratic, divided by |d_xy|^2
-                const float k = frcp(aa);
-                const float bb = fmaf(ex, dx, ey * dy) * k;
-                const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey);
-                const float h2 = fmaf(a2, a2, -fmaf(wx, wx, wy * wy));
-                if (h2 >= 0.f) root_interval(bb, (e2 - a2 * a2) * k, fsqrt(h2 * k), tn, tf);
-                else tf = -INFINITY;
-            } else if (e2 > a2 * a2) {  // along the axis, outside the wall
-                tf = -INFINITY;
-            }
-            slab(a3, a4, oz, iz, tn, tf);  // the caps
-        }
-        if (tn <= tf && tf >= 0.f) best = fminf(best, fmaxf(tn, 0.f));
+        best = prim_ray_hit(best, prim[i].kind, prim[i].a[0], prim[i].a[1], prim[i].a[2], prim[i].a[3], prim[i].a[4],
+                            prim[i].a[5], ox, oy, oz, dx, dy, dz, ix, iy, iz);
     }
     float val = A.dmax;  // a miss
     if (best < INFINITY) val = fminf(A.is_depth ? best * cx : best, A.dmax);
@@ -163,13 +114,6 @@ __global__ __launch_bounds__(64) void scene_pose_kernel(ScenePoseArgs A) {
     }
 }
 
-// length of the positive parts plus the largest component where all are negative: the signed distance to a
-// box (or, with two components, to a capped cylinder's section) from its per-axis excesses
-__device__ __forceinline__ double sd_excess3(double qx, double qy, double qz) {
-    const double px = fmax(qx, 0.0), py = fmax(qy, 0.0), pz = fmax(qz, 0.0);
-    return sqrt(px * px + py * py + pz * pz) + fmin(fmax(qx, fmax(qy, qz)), 0.0);
-}
-
 __global__ __launch_bounds__(SCENE_BLOCK) void scene_distance_kernel(SceneDistArgs A) {
     const long long j = (long long)blockIdx.x * SCENE_BLOCK + threadIdx.x;
     if (j >= A.n) return;
@@ -178,22 +122,7 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_distance_kernel(SceneDistAr
     const int cnt = min(A.sc.count[s], SCENE_MAX_PRIMS);
     const double px = A.points[j * 3], py = A.points[j * 3 + 1], pz = A.points[j * 3 + 2];
     double best = INFINITY;
-    for (int i = 0; i < cnt; ++i) {
-        const double* a = P[i].a;
-        double d;
-        if (P[i].kind == 0) {
-            const double ex = px - a[0], ey = py - a[1], ez = pz - a[2];
-            d = sqrt(ex * ex + ey * ey + ez * ez) - a[3];
-        } else if (P[i].kind == 1) {
-            d = sd_excess3(fabs(px - 0.5 * (a[0] + a[3])) - 0.5 * (a[3] - a[0]),
-                           fabs(py - 0.5 * (a[1] + a[4])) - 0.5 * (a[4] - a[1]),
-                           fabs(pz - 0.5 * (a[2] + a[5])) - 0.5 * (a[5] - a[2]));
-        } else {
-            const double ex = px - a[0], ey = py - a[1];
-            d = sd_excess3(sqrt(ex * ex + ey * ey) - a[2], fabs(pz - 0.5 * (a[3] + a[4])) - 0.5 * (a[4] - a[3]), -INFINITY);
-        }
-        best = fmin(best, d);
-    }
+    for (int i = 0; i < cnt; ++i) best = fmin(best, prim_distance(P[i], px, py, pz));
     A.out[j] = best;
 }
 

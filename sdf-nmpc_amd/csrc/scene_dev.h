@@ -1,4 +1,7 @@
-// Device code shared by the scene kernels (scene.hip, scene_sdf.hip).
+// Device code shared by the scene kernels (scene.hip, scene_sdf.hip, scene_grid.hip): a primitive's frame, and the
+// per-primitive work of the three queries -- the ray's hit, the signed distance, the distance with its gradient.  The
+// brute-force kernels and the grid kernels call the same functions, so that a query over a subset of the primitives
+// that holds the minimiser returns the bits of the query over all of them.
 #pragma once
 #include "scene_kernels.h"
 
@@ -17,6 +20,166 @@ __device__ __forceinline__ void prim_frame(const ScenePrimDyn& P, double t, doub
         R[3 + j] = sy * P.R0[j] + cy * P.R0[3 + j];
         R[6 + j] = P.R0[6 + j];
     }
+}
+
+// ---- the ray's hit (fp32)
+__device__ __forceinline__ float frcp(float a) { return __builtin_amdgcn_rcpf(a); }    // 1 ulp
+__device__ __forceinline__ float fsqrt(float a) { return __builtin_amdgcn_sqrtf(a); }  // 1 ulp
+
+// the root interval of t^2 - 2 b t + c = 0 with h = sqrt(b^2 - c) given (the caller forms the discriminant
+// without cancellation): the root of larger magnitude is q = b + sign(b) h, the other one c / q
+__device__ __forceinline__ void root_interval(float b, float c, float h, float& tn, float& tf) {
+    const float q = b + copysignf(h, b);
+    const float r = c * frcp(q);  // q == 0 only with b == h == 0, c == 0: a double root at 0 (fmin / fmax drop the NaN)
+    tn = fminf(q, r);
+    tf = fmaxf(q, r);
+}
+
+// slab interval of one axis: (lo - o) / d and (hi - o) / d in either order; d == 0 gives -inf / +inf inside
+// the slab and an empty interval outside it
+__device__ __forceinline__ void slab(float lo, float hi, float o, float inv_d, float& tn, float& tf) {
+    const float t1 = (lo - o) * inv_d, t2 = (hi - o) * inv_d;
+    tn = fmaxf(tn, fminf(t1, t2));
+    tf = fminf(tf, fmaxf(t1, t2));
+}
+
+// best = min(best, the hit of the ray o + t d with a world-frame primitive (kind, a0..a5); ix, iy, iz = rcp(d)).  Every
+// primitive is convex, so the ray meets it in one parameter interval [tn, tf]; it hits when tf >= max(tn, 0), at
+// t = max(tn, 0).
+__device__ __forceinline__ float prim_ray_hit(float best, int kind, float a0, float a1, float a2, float a3, float a4,
+                                              float a5, float ox, float oy, float oz, float dx, float dy, float dz,
+                                              float ix, float iy, float iz) {
+    float tn = -INFINITY, tf = INFINITY;
+    if (kind == 0) {  // sphere: centre a0..a2, radius a3
+        const float ex = a0 - ox, ey = a1 - oy, ez = a2 - oz;
+        const float bb = fmaf(ex, dx, fmaf(ey, dy, ez * dz));
+        const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey), wz = fmaf(-bb, dz, ez);  // foot of the centre
+        const float h2 = fmaf(a3, a3, -fmaf(wx, wx, fmaf(wy, wy, wz * wz)));                 // r^2 - |w|^2
+        const float cc = fmaf(ex, ex, fmaf(ey, ey, ez * ez)) - a3 * a3;
+        if (h2 >= 0.f) root_interval(bb, cc, fsqrt(h2), tn, tf);
+        else tf = -INFINITY;
+    } else if (kind == 1) {  // box: lo a0..a2, hi a3..a5
+        slab(a0, a3, ox, ix, tn, tf);
+        slab(a1, a4, oy, iy, tn, tf);
+        slab(a2, a5, oz, iz, tn, tf);
+    } else {  // capped cylinder along z: centre a0, a1, radius a2, z in [a3, a4]
+        const float ex = a0 - ox, ey = a1 - oy;
+        const float aa = fmaf(dx, dx, dy * dy), e2 = fmaf(ex, ex, ey * ey);
+        if (aa > 1e-12f) {  // the side wall's quadratic, divided by |d_xy|^2
+            const float k = frcp(aa);
+            const float bb = fmaf(ex, dx, ey * dy) * k;
+            const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey);
+            const float h2 = fmaf(a2, a2, -fmaf(wx, wx, wy * wy));
+            if (h2 >= 0.f) root_interval(bb, (e2 - a2 * a2) * k, fsqrt(h2 * k), tn, tf);
+            else tf = -INFINITY;
+        } else if (e2 > a2 * a2) {  // along the axis, outside the wall
+            tf = -INFINITY;
+        }
+        slab(a3, a4, oz, iz, tn, tf);  // the caps
+    }
+    if (tn <= tf && tf >= 0.f) best = fminf(best, fmaxf(tn, 0.f));
+    return best;
+}
+
+// ---- the signed distance (fp64)
+// length of the positive parts plus the largest component where all are negative: the signed distance to a
+// box (or, with two components, to a capped cylinder's section) from its per-axis excesses
+__device__ __forceinline__ double sd_excess3(double qx, double qy, double qz) {
+    const double px = fmax(qx, 0.0), py = fmax(qy, 0.0), pz = fmax(qz, 0.0);
+    return sqrt(px * px + py * py + pz * pz) + fmin(fmax(qx, fmax(qy, qz)), 0.0);
+}
+
+// the closed-form signed distance from (px, py, pz) to a world-frame primitive
+__device__ __forceinline__ double prim_distance(const ScenePrimD& P, double px, double py, double pz) {
+    const double* a = P.a;
+    if (P.kind == 0) {
+        const double ex = px - a[0], ey = py - a[1], ez = pz - a[2];
+        return sqrt(ex * ex + ey * ey + ez * ez) - a[3];
+    }
+    if (P.kind == 1)
+        return sd_excess3(fabs(px - 0.5 * (a[0] + a[3])) - 0.5 * (a[3] - a[0]),
+                          fabs(py - 0.5 * (a[1] + a[4])) - 0.5 * (a[4] - a[1]),
+                          fabs(pz - 0.5 * (a[2] + a[5])) - 0.5 * (a[5] - a[2]));
+    const double ex = px - a[0], ey = py - a[1];
+    return sd_excess3(sqrt(ex * ex + ey * ey) - a[2], fabs(pz - 0.5 * (a[3] + a[4])) - 0.5 * (a[4] - a[3]), -INFINITY);
+}
+
+// ---- the signed distance with its gradient (fp64)
+__device__ __forceinline__ double sgn1(double v) { return v < 0.0 ? -1.0 : 1.0; }  // sign(0) = +1
+
+// distance and gradient of the canonical centred shape at the point q of its frame (sphere: radius h0; box: half
+// extents h0, h1, hz; capped cylinder along z: radius h0, half height hz).  The distance is sd_excess3 on the per-axis
+// excesses; at a kink the gradient is one of the one-sided values, finite and of norm <= 1.
+__device__ __forceinline__ double shape_sd(int kind, double qx, double qy, double qz, double h0, double h1, double hz,
+                                           double& gx, double& gy, double& gz) {
+    if (kind == 0) {
+        const double n = sqrt(qx * qx + qy * qy + qz * qz);
+        const bool z = n == 0.0;
+        gx = z ? 0.0 : qx / n;
+        gy = z ? 0.0 : qy / n;
+        gz = z ? 1.0 : qz / n;
+        return n - h0;
+    }
+    if (kind == 1) {
+        const double ax = fabs(qx) - h0, ay = fabs(qy) - h1, az = fabs(qz) - hz;
+        const double px = fmax(ax, 0.0), py = fmax(ay, 0.0), pz = fmax(az, 0.0);
+        const double len = sqrt(px * px + py * py + pz * pz);
+        const double amax = fmax(ax, fmax(ay, az));
+        if (amax > 0.0) {
+            gx = sgn1(qx) * px / len;
+            gy = sgn1(qy) * py / len;
+            gz = sgn1(qz) * pz / len;
+        } else {  // inside: the nearest face, the lowest axis on a tie
+            const bool mx = ax >= ay && ax >= az, my = !mx && ay >= az;
+            gx = mx ? sgn1(qx) : 0.0;
+            gy = my ? sgn1(qy) : 0.0;
+            gz = (!mx && !my) ? sgn1(qz) : 0.0;
+        }
+        return len + fmin(amax, 0.0);
+    }
+    const double rho = sqrt(qx * qx + qy * qy);
+    const bool z = rho == 0.0;
+    const double ex = z ? 1.0 : qx / rho, ey = z ? 0.0 : qy / rho;
+    const double a0 = rho - h0, a1 = fabs(qz) - hz;
+    const double p0 = fmax(a0, 0.0), p1 = fmax(a1, 0.0);
+    const double len = sqrt(p0 * p0 + p1 * p1 + 0.0);  // sd_excess3's third component is -inf: its positive part 0
+    const double amax = fmax(a0, a1);
+    if (amax > 0.0) {
+        gx = p0 * ex / len;
+        gy = p0 * ey / len;
+        gz = p1 * sgn1(qz) / len;
+    } else if (a0 >= a1) {
+        gx = ex; gy = ey; gz = 0.0;
+    } else {
+        gx = 0.0; gy = 0.0; gz = sgn1(qz);
+    }
+    return len + fmin(amax, 0.0);
+}
+
+// shape_sd of a world-frame primitive (its frame is the world's, translated): the distance from (px, py, pz) and
+// its world gradient
+__device__ __forceinline__ double prim_sd_grad(const ScenePrimD& P, double px, double py, double pz, double& gx,
+                                               double& gy, double& gz) {
+    const double* a = P.a;
+    const int kind = P.kind;
+    double qx, qy, qz, h0, h1 = 0.0, hz = 0.0;
+    if (kind == 0) {
+        qx = px - a[0]; qy = py - a[1]; qz = pz - a[2];
+        h0 = a[3];
+    } else if (kind == 1) {
+        qx = px - 0.5 * (a[0] + a[3]); qy = py - 0.5 * (a[1] + a[4]); qz = pz - 0.5 * (a[2] + a[5]);
+        h0 = 0.5 * (a[3] - a[0]); h1 = 0.5 * (a[4] - a[1]); hz = 0.5 * (a[5] - a[2]);
+    } else {
+        qx = px - a[0]; qy = py - a[1]; qz = pz - 0.5 * (a[3] + a[4]);
+        h0 = a[2]; hz = 0.5 * (a[4] - a[3]);
+    }
+    return shape_sd(kind, qx, qy, qz, h0, h1, hz, gx, gy, gz);
+}
+
+// ---- the uniform grid of an indexed scene set (scene_grid.hip)
+// the cell of a coordinate u = (v - org) * inv in cells, clamped into [0, n): NaN gives 0
+__device__ __forceinline__ int grid_cell(double u, int n) {
+    return u >= (double)(n - 1) ? n - 1 : (u > 0.0 ? (int)u : 0);
 }
 
 }  // namespace sdfn

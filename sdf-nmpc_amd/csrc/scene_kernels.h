@@ -40,12 +40,34 @@ struct ScenePrimFrame {  // 64 bytes: four 16-byte LDS reads; what only a box re
     float hz, h1;        // box / cylinder: the half extent along z; box: along y
 };
 
-// S scenes of up to SCENE_MAX_PRIMS primitives each, in both precisions, on the device
+// The uniform grid of one scene of an indexed set (sdfnmpc_scene_create_large; scene_grid.hip).  Cell (i, j, k) is
+// the cube org + (i, j, k) cell .. org + (i + 1, j + 1, k + 1) cell; its primitives are the scene-local indices
+// cell_items[cell_start[cell_off + id] .. cell_start[cell_off + id + 1]), id = (k n[1] + j) n[0] + i, in ascending
+// order.  A primitive is listed in every cell that its bounding box, inflated by `infl`, overlaps; the grid's box
+// is the primitives' bounding box padded by 2 infl, so no primitive is within infl of the grid's boundary.  org and
+// cell are representable in fp32: both precisions see the same planes.
+struct SceneGridHdr {
+    double org[3], cell, inv;  // inv = 1 / cell
+    int n[3];                  // cells per axis, each >= 1
+    int count;                 // primitives of the scene
+    int prim_off;              // the scene's first primitive in SceneDev.pf / .pd
+    int cell_off;              // the scene's first entry in SceneDev.cell_start (n[0] n[1] n[2] + 1 entries)
+};
+constexpr int SCENE_LARGE_MAX_PRIMS = 65536;       // SDFNMPC_SCENE_LARGE_MAX_PRIMS
+constexpr int SCENE_GRID_MAX_AXIS = 1024;          // SDFNMPC_SCENE_GRID_MAX_AXIS
+constexpr long long SCENE_GRID_MAX_CELLS = 1 << 22;  // SDFNMPC_SCENE_GRID_MAX_CELLS, per scene
+constexpr long long SCENE_GRID_MAX_ITEMS = 1 << 26;  // SDFNMPC_SCENE_GRID_MAX_ITEMS, per set (cells + list entries)
+
+// S scenes in both precisions on the device: up to SCENE_MAX_PRIMS primitives each at a stride of SCENE_MAX_PRIMS, or
+// (ghdr != nullptr: an indexed set) up to SCENE_LARGE_MAX_PRIMS each, packed scene after scene, with a grid
 struct SceneDev {
     int S;
     const int* count;        // [S]
-    const ScenePrimF* pf;    // [S][SCENE_MAX_PRIMS]
-    const ScenePrimD* pd;    // [S][SCENE_MAX_PRIMS]
+    const ScenePrimF* pf;    // [S][SCENE_MAX_PRIMS]; indexed: [sum of count]
+    const ScenePrimD* pd;    // [S][SCENE_MAX_PRIMS]; indexed: [sum of count]
+    const SceneGridHdr* ghdr;  // [S], or nullptr: not indexed (the brute-force kernels)
+    const int* cell_start;
+    const int* cell_items;
 };
 
 struct SceneRenderArgs {
@@ -113,5 +135,9 @@ hipError_t launch_scene_distance(const SceneDistArgs& a, hipStream_t s);
 hipError_t launch_scene_render_dyn(const SceneRenderDynArgs& a, hipStream_t s);
 hipError_t launch_scene_distance_dyn(const SceneDistDynArgs& a, hipStream_t s);
 hipError_t launch_scene_sdf_rows(const SceneSdfArgs& a, hipStream_t s);
+// scene_grid.hip: the three queries of an indexed set (a.sc.ghdr != nullptr), the bits of the brute-force kernels
+hipError_t launch_scene_render_grid(const SceneRenderArgs& a, hipStream_t s);
+hipError_t launch_scene_distance_grid(const SceneDistArgs& a, hipStream_t s);
+hipError_t launch_scene_sdf_rows_grid(const SceneSdfArgs& a, hipStream_t s);
 
 }  // namespace sdfn

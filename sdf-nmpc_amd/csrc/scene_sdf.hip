@@ -11,63 +11,13 @@
 // kernel evaluates; its gradient g in the primitive's frame is taken on the same excesses, and the world gradient is
 // R(t) g of the primitive that attains the minimum (the lowest index on a tie).  Truncated as the network's training
 // target is (df_train.py:50): d >= max_df, and an empty scene, give df = max_df with a zero gradient.  No atomics, no
-// cross-lane traffic: a row depends on its position, its flag, its instance's scene and its time only.
+// cross-lane traffic: a row depends on its position, its flag, its instance's scene and its time only.  shape_sd and
+// prim_sd_grad are in scene_dev.h, shared with scene_sdf_rows_grid_kernel (scene_grid.hip).
 #include "scene_dev.h"
 
 namespace sdfn {
 
 namespace {
-
-__device__ __forceinline__ double sgn1(double v) { return v < 0.0 ? -1.0 : 1.0; }  // sign(0) = +1
-
-// distance and gradient of the canonical centred shape at the point q of its frame (sphere: radius h0; box: half
-// extents h0, h1, hz; capped cylinder along z: radius h0, half height hz).  The distance is sd_excess3 of scene.hip on
-// the per-axis excesses; at a kink the gradient is one of the one-sided values, finite and of norm <= 1.
-__device__ __forceinline__ double shape_sd(int kind, double qx, double qy, double qz, double h0, double h1, double hz,
-                                           double& gx, double& gy, double& gz) {
-    if (kind == 0) {
-        const double n = sqrt(qx * qx + qy * qy + qz * qz);
-        const bool z = n == 0.0;
-        gx = z ? 0.0 : qx / n;
-        gy = z ? 0.0 : qy / n;
-        gz = z ? 1.0 : qz / n;
-        return n - h0;
-    }
-    if (kind == 1) {
-        const double ax = fabs(qx) - h0, ay = fabs(qy) - h1, az = fabs(qz) - hz;
-        const double px = fmax(ax, 0.0), py = fmax(ay, 0.0), pz = fmax(az, 0.0);
-        const double len = sqrt(px * px + py * py + pz * pz);
-        const double amax = fmax(ax, fmax(ay, az));
-        if (amax > 0.0) {
-            gx = sgn1(qx) * px / len;
-            gy = sgn1(qy) * py / len;
-            gz = sgn1(qz) * pz / len;
-        } else {  // inside: the nearest face, the lowest axis on a tie
-            const bool mx = ax >= ay && ax >= az, my = !mx && ay >= az;
-            gx = mx ? sgn1(qx) : 0.0;
-            gy = my ? sgn1(qy) : 0.0;
-            gz = (!mx && !my) ? sgn1(qz) : 0.0;
-        }
-        return len + fmin(amax, 0.0);
-    }
-    const double rho = sqrt(qx * qx + qy * qy);
-    const bool z = rho == 0.0;
-    const double ex = z ? 1.0 : qx / rho, ey = z ? 0.0 : qy / rho;
-    const double a0 = rho - h0, a1 = fabs(qz) - hz;
-    const double p0 = fmax(a0, 0.0), p1 = fmax(a1, 0.0);
-    const double len = sqrt(p0 * p0 + p1 * p1 + 0.0);  // sd_excess3's third component is -inf: its positive part 0
-    const double amax = fmax(a0, a1);
-    if (amax > 0.0) {
-        gx = p0 * ex / len;
-        gy = p0 * ey / len;
-        gz = p1 * sgn1(qz) / len;
-    } else if (a0 >= a1) {
-        gx = ex; gy = ey; gz = 0.0;
-    } else {
-        gx = 0.0; gy = 0.0; gz = sgn1(qz);
-    }
-    return len + fmin(amax, 0.0);
-}
 
 template <bool DYN>
 __global__ __launch_bounds__(SCENE_BLOCK) void scene_sdf_rows_kernel(SceneSdfArgs A) {
@@ -102,21 +52,8 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_sdf_rows_kernel(SceneSdfArg
     } else {
         const ScenePrimD* P = A.sc.pd + s * SCENE_MAX_PRIMS;
         for (int i = 0; i < cnt; ++i) {
-            const double* a = P[i].a;
-            const int kind = P[i].kind;
-            double qx, qy, qz, h0, h1 = 0.0, hz = 0.0;
-            if (kind == 0) {
-                qx = px - a[0]; qy = py - a[1]; qz = pz - a[2];
-                h0 = a[3];
-            } else if (kind == 1) {
-                qx = px - 0.5 * (a[0] + a[3]); qy = py - 0.5 * (a[1] + a[4]); qz = pz - 0.5 * (a[2] + a[5]);
-                h0 = 0.5 * (a[3] - a[0]); h1 = 0.5 * (a[4] - a[1]); hz = 0.5 * (a[5] - a[2]);
-            } else {
-                qx = px - a[0]; qy = py - a[1]; qz = pz - 0.5 * (a[3] + a[4]);
-                h0 = a[2]; hz = 0.5 * (a[4] - a[3]);
-            }
             double gx, gy, gz;
-            const double d = shape_sd(kind, qx, qy, qz, h0, h1, hz, gx, gy, gz);
+            const double d = prim_sd_grad(P[i], px, py, pz, gx, gy, gz);
             if (d < best) {
                 best = d;
                 bx = gx; by = gy; bz = gz;

@@ -18,6 +18,10 @@ point c0 (sphere: centre; box: (lo + hi) / 2; cylinder: (cx, cy, (z0 + z1) / 2))
 oriented box, a sphere with v a moving obstacle.  ``render(..., t=)``, ``render_from_state(..., t=)`` and
 ``distance(..., t=)`` then show the scene at time t; a scene without such primitives is the static scene whatever t.
 
+A scene of more than 32 primitives takes a grid index: ``Scene(ctx, Scene.forest(1024, lo, hi), grid=True)`` holds up
+to 65536 static primitives per scene, and every call above -- and every consumer of a scene -- returns what the plain
+scene would return, bit for bit, from kernels that visit only the grid cells along a ray or around a point.
+
 World frame z up; camera frame x forward, y left, z up, the pixel grid of ``ColChecker``.  There is no CPU path.
 """
 from __future__ import annotations
@@ -38,9 +42,11 @@ def _three(a, name):
 
 class Scene:
     """One scene (a list of primitives) or several (a list of lists) with ``scene_of`` [B], the scene of each
-    instance; without ``scene_of`` every instance sees scene 0.  At most 32 primitives per scene.  The primitives
-    are checked by the library when the scene is created (SdfnmpcError: more than 32, an unknown kind, a radius
-    <= 0, lo >= hi); ``scene_of`` is checked here."""
+    instance; without ``scene_of`` every instance sees scene 0.  At most 32 primitives per scene; with ``grid=True``
+    at most 65536 static ones, indexed by a uniform grid of cell edge ``cell`` [m] (None: the library's default, a
+    function of the primitives) -- ``is_indexed``.  The primitives are checked by the library when the scene is
+    created (SdfnmpcError: too many, an unknown kind, a radius <= 0, lo >= hi, a grid too fine); ``scene_of``, ``cell``
+    and a moving primitive in an indexed scene (ValueError) are checked here."""
 
     @staticmethod
     def sphere(center, radius):
@@ -73,7 +79,31 @@ class Scene:
             raise ValueError("Scene.moving: q = (w, x, y, z)")
         return (prim[0], list(prim[1]), m)
 
-    def __init__(self, ctx: "_lib.Context", prims, scene_of=None):
+    @staticmethod
+    def forest(n, lo, hi, radius=(0.15, 0.4), seed=0, keep_clear=None):
+        """A list of n upright cylinders in the box lo .. hi (three components each): axes uniform in xy, radii uniform
+        in radius = (r0, r1), every cylinder from lo[2] to hi[2].  keep_clear = (centre_xy, radius): a cylinder whose
+        axis lies within that circle is moved radially out of it, onto its rim (one on the centre: along +x).  A pure
+        function of its arguments through numpy.random.default_rng(seed)."""
+        lo, hi = _three(lo, "lo"), _three(hi, "hi")
+        r0, r1 = (float(v) for v in radius)
+        n = int(n)
+        if n < 0 or not (lo[0] < hi[0] and lo[1] < hi[1] and lo[2] < hi[2]) or not 0.0 < r0 <= r1:
+            raise ValueError("Scene.forest: n >= 0, lo < hi and 0 < r0 <= r1 required")
+        rng = np.random.default_rng(seed)
+        xy = rng.uniform(lo[:2], hi[:2], size=(n, 2))
+        rad = rng.uniform(r0, r1, size=n)
+        if keep_clear is not None:
+            c, rc = np.asarray(keep_clear[0], dtype=np.float64).reshape(2), float(keep_clear[1])
+            e = xy - c
+            dist = np.hypot(e[:, 0], e[:, 1])
+            inside = dist < rc
+            e[dist == 0.0] = (1.0, 0.0)
+            dist = np.where(dist == 0.0, 1.0, dist)
+            xy = np.where(inside[:, None], c + e * (rc * (1.0 + 1e-9) / dist)[:, None], xy)
+        return [Scene.cylinder(xy[i], rad[i], lo[2], hi[2]) for i in range(n)]
+
+    def __init__(self, ctx: "_lib.Context", prims, scene_of=None, grid=False, cell=None):
         is_prim = lambda p: isinstance(p, tuple) and len(p) in (2, 3) and isinstance(p[0], (str, int))
         scenes = [list(prims)] if all(is_prim(p) for p in prims) else [list(s) for s in prims]
         flat, motion = [], []
@@ -87,10 +117,20 @@ class Scene:
                 motion.append(mo[0] if mo else None)
         self.ctx, self.S = ctx, len(scenes)
         self._sdf_users = weakref.WeakSet()  # controllers whose SDF source this scene is (Nmpc.set_sdf_scene)
-        # plain primitives only: the call a scene has always made
-        self.h = _lib.scene_create(ctx, [len(s) for s in scenes], flat,
-                                   motion if any(m is not None for m in motion) else None)
+        if grid:
+            if any(m is not None for m in motion):
+                raise ValueError("Scene: an indexed scene (grid=True) holds static primitives only, no Scene.moving")
+            if cell is not None and not (np.isfinite(float(cell)) and float(cell) > 0.0):
+                raise ValueError("Scene: cell must be positive and finite (None: the default)")
+            self.h = _lib.scene_create_large(ctx, [len(s) for s in scenes], flat, 0.0 if cell is None else float(cell))
+        else:
+            if cell is not None:
+                raise ValueError("Scene: cell needs grid=True")
+            # plain primitives only: the call a scene has always made
+            self.h = _lib.scene_create(ctx, [len(s) for s in scenes], flat,
+                                       motion if any(m is not None for m in motion) else None)
         self.is_dynamic = bool(_lib.load().sdfnmpc_scene_is_dynamic(self.h))
+        self.is_indexed = bool(_lib.load().sdfnmpc_scene_is_indexed(self.h))
         self.scene_of = self._scene_of = None
         if scene_of is not None:
             so = np.ascontiguousarray(scene_of, dtype=np.int32).ravel()
