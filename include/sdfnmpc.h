@@ -761,6 +761,27 @@ int sdfnmpc_scene_create_large(sdfnmpc_ctx* ctx, int S, const int* count, const 
                                sdfnmpc_scene** out);
 int sdfnmpc_scene_is_indexed(const sdfnmpc_scene* scene);
 
+/* ---- a large static world with a few moving obstacles: mixed sets (csrc/scene_grid.hip) ----
+ * sdfnmpc_scene_create_mixed is sdfnmpc_scene_create_large (count, prims, cell: the same arguments, checks and grid,
+ * which covers these static primitives only) with a mover set beside every scene: mcount [S] primitives per scene,
+ * 0..SDFNMPC_SCENE_MAX_PRIMS, mprims [sum of mcount] and mmotion [sum of mcount] as sdfnmpc_scene_create_moving takes
+ * and checks them (mmotion == NULL: no motion; such movers still take the mover path).  The movers are not in the
+ * grid: they may leave its box, overlap static primitives, or be all a scene has (count[s] == 0).
+ * Every query of such a handle is the minimum over both sets at the query's time, bit for bit the elementwise minimum
+ * of the indexed static set's result and of the movers' as a dynamic set of their own: sdfnmpc_scene_render(_at),
+ * sdfnmpc_scene_distance(_at) (times [j] per point), sdfnmpc_scene_sdf_rows, sdfnmpc_lin_args.sdf_scene,
+ * sdfnmpc_solver_set_sdf_scene (predict as for a dynamic set) and every rollout that takes a scene.  In the SDF row
+ * the gradient is that of the nearest primitive; on a tie a static primitive comes before a mover, and within each
+ * set the lowest index wins.  The kernels are "scene_render_mixed", "scene_dist_mixed" and "scene_sdf_rows_mixed" in
+ * sdfnmpc_ctx_kernel_stats: they evaluate the movers first and start the grid's search from that bound.
+ * With a mover in some scene both sdfnmpc_scene_is_indexed and sdfnmpc_scene_is_dynamic are 1.  With every mcount[s]
+ * == 0 the handle is what sdfnmpc_scene_create_large returns (not dynamic, the grid kernels).
+ * SDFNMPC_E_ARG (nothing is allocated): what sdfnmpc_scene_create_large refuses of count, prims and cell, what
+ * sdfnmpc_scene_create_moving refuses of the movers, an mcount[s] outside 0..SDFNMPC_SCENE_MAX_PRIMS, NULL mcount. */
+int sdfnmpc_scene_create_mixed(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims, double cell,
+                               const int* mcount, const sdfnmpc_prim* mprims, const sdfnmpc_prim_motion* mmotion,
+                               sdfnmpc_scene** out);
+
 /* sdfnmpc_solver_rollout with perception inside the loop.  Before step k with (k + phase) % every == 0 it enqueues, on the
  * solver's stream and in this order: (a) sdfnmpc_scene_pose from the solver's x0 field; (b) sdfnmpc_scene_render of
  * every instance's scene from that camera pose; (c) sdfnmpc_vae_encode of the images; (d) sdfnmpc_pack_refs in mode -1

@@ -46,7 +46,7 @@ SYMBOLS = [
     "sdfnmpc_solver_rollout_scene_sdf",
     "sdfnmpc_img_sdf_rows", "sdfnmpc_img_sdf_pool", "sdfnmpc_solver_set_sdf_image", "sdfnmpc_solver_rollout_image_sdf",
     "sdfnmpc_solver_rollout_image_recon",
-    "sdfnmpc_scene_create_large", "sdfnmpc_scene_is_indexed",
+    "sdfnmpc_scene_create_large", "sdfnmpc_scene_is_indexed", "sdfnmpc_scene_create_mixed",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -282,6 +282,7 @@ def load():
         "sdfnmpc_scene_is_dynamic": (i, [vp]),
         "sdfnmpc_scene_create_large": (i, [vp, i, P(i), P(PrimC), d, P(vp)]),
         "sdfnmpc_scene_is_indexed": (i, [vp]),
+        "sdfnmpc_scene_create_mixed": (i, [vp, i, P(i), P(PrimC), d, P(i), P(PrimC), P(PrimMotionC), P(vp)]),
         "sdfnmpc_scene_render_at": (i, [vp, vp, vp, P(ImgOptsC), i, i, f, i, vp, vp, d, vp]),
         "sdfnmpc_scene_distance_at": (i, [vp, vp, vp, vp, vp, ll, vp]),
         "sdfnmpc_solver_rollout_perceive_at": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d]),
@@ -808,28 +809,51 @@ def sdf_truth(ctx: Context, opts: ImgOptsC, min_df: float, max_df: float, grid, 
 
 
 # ---- analytic scenes (csrc/scene.hip); the user-facing object is sdf_nmpc_amd.scene.Scene ----
-def scene_create(ctx: "Context", counts, prims, motion=None):
-    """sdfnmpc_scene_create: counts [S] primitives per scene, prims a flat list of (kind, values) scene after
-    scene.  Returns the handle; the C entry point refuses malformed scenes.  motion: one dict per primitive (keys
-    q, yaw_rate, v, amp, omega, phase; None: no motion) -- sdfnmpc_scene_create_moving."""
-    cn = (C.c_int * len(counts))(*[int(c) for c in counts])
+def _prims_c(prims):
+    """a flat list of (kind, values) -> PrimC array (one unused entry for an empty list)"""
     pr = (PrimC * max(len(prims), 1))()
     for k, (kind, vals) in enumerate(prims):
         pr[k].kind = int(kind)
         for j, v in enumerate(vals):
             pr[k].a[j] = float(v)
-    h = C.c_void_p()
-    if motion is None:
-        _check(load().sdfnmpc_scene_create(ctx.h, len(counts), cn, pr, C.byref(h)))
-        return h
-    mo = (PrimMotionC * max(len(prims), 1))()
+    return pr
+
+
+def _motion_c(motion, n):
+    """one dict per primitive (keys q, yaw_rate, v, amp, omega, phase; None: no motion) -> PrimMotionC array"""
+    mo = (PrimMotionC * max(n, 1))()
     for k, m in enumerate(motion):
         m = m or {}
         mo[k].q[:] = [float(v) for v in m.get("q", (1.0, 0.0, 0.0, 0.0))]
         mo[k].v[:] = [float(v) for v in m.get("v", (0.0, 0.0, 0.0))]
         mo[k].amp[:] = [float(v) for v in m.get("amp", (0.0, 0.0, 0.0))]
         mo[k].yaw_rate, mo[k].omega, mo[k].phase = (float(m.get(n, 0.0)) for n in ("yaw_rate", "omega", "phase"))
+    return mo
+
+
+def scene_create(ctx: "Context", counts, prims, motion=None):
+    """sdfnmpc_scene_create: counts [S] primitives per scene, prims a flat list of (kind, values) scene after
+    scene.  Returns the handle; the C entry point refuses malformed scenes.  motion: one dict per primitive (keys
+    q, yaw_rate, v, amp, omega, phase; None: no motion) -- sdfnmpc_scene_create_moving."""
+    cn = (C.c_int * len(counts))(*[int(c) for c in counts])
+    pr = _prims_c(prims)
+    h = C.c_void_p()
+    if motion is None:
+        _check(load().sdfnmpc_scene_create(ctx.h, len(counts), cn, pr, C.byref(h)))
+        return h
+    mo = _motion_c(motion, len(prims))
     _check(load().sdfnmpc_scene_create_moving(ctx.h, len(counts), cn, pr, mo, C.byref(h)))
+    return h
+
+
+def scene_create_mixed(ctx: "Context", counts, prims, cell, mcounts, mprims, mmotion):
+    """sdfnmpc_scene_create_mixed: scene_create_large's static primitives plus mcounts [S] movers per scene (at most
+    32 each), mprims / mmotion as scene_create takes prims / motion (mmotion None: no motion records)."""
+    cn = (C.c_int * len(counts))(*[int(c) for c in counts])
+    mc = (C.c_int * len(mcounts))(*[int(c) for c in mcounts])
+    h = C.c_void_p()
+    _check(load().sdfnmpc_scene_create_mixed(ctx.h, len(counts), cn, _prims_c(prims), float(cell), mc, _prims_c(mprims),
+                                             None if mmotion is None else _motion_c(mmotion, len(mprims)), C.byref(h)))
     return h
 
 
@@ -837,11 +861,7 @@ def scene_create_large(ctx: "Context", counts, prims, cell: float = 0.0):
     """sdfnmpc_scene_create_large: scene_create for scenes of up to 65536 static primitives each, with a uniform grid
     of cell edge `cell` [m] (<= 0: the library's default)."""
     cn = (C.c_int * len(counts))(*[int(c) for c in counts])
-    pr = (PrimC * max(len(prims), 1))()
-    for k, (kind, vals) in enumerate(prims):
-        pr[k].kind = int(kind)
-        for j, v in enumerate(vals):
-            pr[k].a[j] = float(v)
+    pr = _prims_c(prims)
     h = C.c_void_p()
     _check(load().sdfnmpc_scene_create_large(ctx.h, len(counts), cn, pr, float(cell), C.byref(h)))
     return h

@@ -1299,6 +1299,8 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
 
 // the scene's rows kernel: an indexed set takes the grid kernel, everything else the launch it has always taken
 static hipError_t scene_sdf_rows_enqueue(sdfnmpc_ctx* ctx, const SceneSdfArgs& a) {
+    if (a.sc.ghdr && a.dyn)  // a mixed set: the grid plus movers
+        return timed(ctx, "scene_sdf_rows_mixed", [&] { return launch_scene_sdf_rows_mixed(a, ctx->stream); });
     if (a.sc.ghdr) return timed(ctx, "scene_sdf_rows_grid", [&] { return launch_scene_sdf_rows_grid(a, ctx->stream); });
     return timed(ctx, "scene_sdf_rows", [&] { return launch_scene_sdf_rows(a, ctx->stream); });
 }
@@ -2502,9 +2504,76 @@ struct sdfnmpc_scene {
     void* dmem = nullptr;  // count [S] | ScenePrimD [S][32] | ScenePrimF [S][32] | dynamic: ScenePrimDyn [S][32]
     SceneDev dev{};
     const ScenePrimDyn* dyn = nullptr;  // non-NULL: a dynamic set (some primitive is oriented or moves)
+    const int* mcount = nullptr;        // [S]: with dev.ghdr and dyn, the movers per scene of a mixed set
     // an indexed set (sdfnmpc_scene_create_large; dev.ghdr != nullptr): count [S] | SceneGridHdr [S] | ScenePrimD [total]
-    // | ScenePrimF [total] | cell_start | cell_items, every block at a multiple of 16 bytes
+    // | ScenePrimF [total] | cell_start | cell_items, every block at a multiple of 16 bytes; a mixed set
+    // (sdfnmpc_scene_create_mixed; dev.ghdr and dyn both non-NULL) appends mcount [S] | ScenePrimDyn [S][32]
 };
+
+// kind, values and ranges of one primitive, as sdfnmpc_scene_create checks them; na = the number of values read
+static int scene_prim_check(const sdfnmpc_prim* p, int* na) {
+    const double* a = p->a;
+    bool ok = false;
+    if (p->kind == SDFNMPC_PRIM_SPHERE) { *na = 4; ok = a[3] > 0.0; }
+    else if (p->kind == SDFNMPC_PRIM_BOX) { *na = 6; ok = a[0] < a[3] && a[1] < a[4] && a[2] < a[5]; }
+    else if (p->kind == SDFNMPC_PRIM_CYLINDER) { *na = 5; ok = a[2] > 0.0 && a[3] < a[4]; }
+    else return fail(SDFNMPC_E_ARG, "scene: unknown primitive kind (0 sphere, 1 box, 2 cylinder)");
+    for (int k = 0; k < *na; ++k) ok = ok && std::isfinite(a[k]);
+    if (!ok) return fail(SDFNMPC_E_ARG, "scene: a primitive needs finite values, a radius > 0 and lo < hi");
+    return SDFNMPC_OK;
+}
+
+// the motion records of `total` primitives, as sdfnmpc_scene_create_moving checks them; *dynamic: whether some record
+// has a rotation other than the identity or a non-zero yaw_rate, v or amp
+static int scene_motion_check(const sdfnmpc_prim_motion* motion, long long total, bool* dynamic) {
+    *dynamic = false;
+    for (long long i = 0; motion && i < total; ++i) {
+        const sdfnmpc_prim_motion& m = motion[i];
+        bool fin = std::isfinite(m.yaw_rate) && std::isfinite(m.omega) && std::isfinite(m.phase);
+        for (int k = 0; k < 4; ++k) fin = fin && std::isfinite(m.q[k]);
+        for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(m.v[k]) && std::isfinite(m.amp[k]);
+        if (!fin) return fail(SDFNMPC_E_ARG, "scene: a motion record needs finite values");
+        if (m.q[0] == 0.0 && m.q[1] == 0.0 && m.q[2] == 0.0 && m.q[3] == 0.0)
+            return fail(SDFNMPC_E_ARG, "scene: a motion record needs a non-zero quaternion");
+        *dynamic = *dynamic || m.q[1] != 0.0 || m.q[2] != 0.0 || m.q[3] != 0.0 || m.yaw_rate != 0.0;
+        for (int k = 0; k < 3; ++k) *dynamic = *dynamic || m.v[k] != 0.0 || m.amp[k] != 0.0;
+    }
+    return SDFNMPC_OK;
+}
+
+// the device record of a checked primitive with its motion (mo == NULL: none): the canonical centred shape and its
+// frame at t = 0, R(q / |q|) of utils/math.py:7-23 in fp64
+static void scene_dyn_fill(ScenePrimDyn& y, const sdfnmpc_prim* p, const sdfnmpc_prim_motion* mo) {
+    static const sdfnmpc_prim_motion identity = {{1.0, 0.0, 0.0, 0.0}, 0.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, 0.0, 0.0};
+    const sdfnmpc_prim_motion& m = mo ? *mo : identity;
+    const double* a = p->a;
+    y.kind = p->kind;
+    if (p->kind == SDFNMPC_PRIM_SPHERE) {
+        for (int k = 0; k < 3; ++k) { y.c0[k] = a[k]; y.h[k] = a[3]; }
+    } else if (p->kind == SDFNMPC_PRIM_BOX) {
+        for (int k = 0; k < 3; ++k) { y.c0[k] = 0.5 * (a[k] + a[3 + k]); y.h[k] = 0.5 * (a[3 + k] - a[k]); }
+    } else {
+        y.c0[0] = a[0]; y.c0[1] = a[1]; y.c0[2] = 0.5 * (a[3] + a[4]);
+        y.h[0] = y.h[1] = a[2]; y.h[2] = 0.5 * (a[4] - a[3]);
+    }
+    const double qs = std::max(std::max(std::fabs(m.q[0]), std::fabs(m.q[1])),
+                               std::max(std::fabs(m.q[2]), std::fabs(m.q[3])));  // no overflow in the norm
+    double q[4];
+    for (int k = 0; k < 4; ++k) q[k] = m.q[k] / qs;
+    const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double q0 = q[0] / qn, q1 = q[1] / qn, q2 = q[2] / qn, q3 = q[3] / qn;
+    y.R0[0] = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3;
+    y.R0[1] = 2 * (q1 * q2 - q0 * q3);
+    y.R0[2] = 2 * (q1 * q3 + q0 * q2);
+    y.R0[3] = 2 * (q1 * q2 + q0 * q3);
+    y.R0[4] = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3;
+    y.R0[5] = 2 * (q2 * q3 - q0 * q1);
+    y.R0[6] = 2 * (q1 * q3 - q0 * q2);
+    y.R0[7] = 2 * (q2 * q3 + q0 * q1);
+    y.R0[8] = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3;
+    for (int k = 0; k < 3; ++k) { y.v[k] = m.v[k]; y.amp[k] = m.amp[k]; }
+    y.yaw_rate = m.yaw_rate; y.omega = m.omega; y.phase = m.phase;
+}
 
 extern "C" int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
                                     sdfnmpc_scene** out) {
@@ -2528,17 +2597,7 @@ extern "C" int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* c
     const size_t n = (size_t)S * SCENE_MAX_PRIMS;
     // a set is dynamic when some primitive has a rotation other than the identity or a non-zero yaw_rate, v or amp
     bool dynamic = false;
-    for (long long i = 0; motion && i < total; ++i) {
-        const sdfnmpc_prim_motion& m = motion[i];
-        bool fin = std::isfinite(m.yaw_rate) && std::isfinite(m.omega) && std::isfinite(m.phase);
-        for (int k = 0; k < 4; ++k) fin = fin && std::isfinite(m.q[k]);
-        for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(m.v[k]) && std::isfinite(m.amp[k]);
-        if (!fin) return fail(SDFNMPC_E_ARG, "scene: a motion record needs finite values");
-        if (m.q[0] == 0.0 && m.q[1] == 0.0 && m.q[2] == 0.0 && m.q[3] == 0.0)
-            return fail(SDFNMPC_E_ARG, "scene: a motion record needs a non-zero quaternion");
-        dynamic = dynamic || m.q[1] != 0.0 || m.q[2] != 0.0 || m.q[3] != 0.0 || m.yaw_rate != 0.0;
-        for (int k = 0; k < 3; ++k) dynamic = dynamic || m.v[k] != 0.0 || m.amp[k] != 0.0;
-    }
+    if (int rc = scene_motion_check(motion, total, &dynamic)) return rc;
     const size_t static_bytes = cnt_bytes + n * (sizeof(ScenePrimD) + sizeof(ScenePrimF));
     std::vector<char> host(static_bytes + (dynamic ? n * sizeof(ScenePrimDyn) : 0), 0);
     ScenePrimDyn* hm = dynamic ? (ScenePrimDyn*)(host.data() + static_bytes) : nullptr;
@@ -2552,13 +2611,7 @@ extern "C" int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* c
         for (int i = 0; i < count[s]; ++i, ++p) {
             const double* a = p->a;
             int na = 0;
-            bool ok = false;
-            if (p->kind == SDFNMPC_PRIM_SPHERE) { na = 4; ok = a[3] > 0.0; }
-            else if (p->kind == SDFNMPC_PRIM_BOX) { na = 6; ok = a[0] < a[3] && a[1] < a[4] && a[2] < a[5]; }
-            else if (p->kind == SDFNMPC_PRIM_CYLINDER) { na = 5; ok = a[2] > 0.0 && a[3] < a[4]; }
-            else return fail(SDFNMPC_E_ARG, "scene: unknown primitive kind (0 sphere, 1 box, 2 cylinder)");
-            for (int k = 0; k < na; ++k) ok = ok && std::isfinite(a[k]);
-            if (!ok) return fail(SDFNMPC_E_ARG, "scene: a primitive needs finite values, a radius > 0 and lo < hi");
+            if (int rc = scene_prim_check(p, &na)) return rc;
             ScenePrimD& d = hd[(size_t)s * SCENE_MAX_PRIMS + i];
             ScenePrimF& f = hf[(size_t)s * SCENE_MAX_PRIMS + i];
             d.kind = f.kind = p->kind;
@@ -2566,36 +2619,7 @@ extern "C" int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* c
                 d.a[k] = a[k];
                 f.a[k] = (float)a[k];
             }
-            if (!hm) continue;
-            // the canonical centred shape and its frame at t = 0: R(q / |q|) of utils/math.py:7-23 in fp64
-            ScenePrimDyn& y = hm[(size_t)s * SCENE_MAX_PRIMS + i];
-            const sdfnmpc_prim_motion& m = motion[p - prims];
-            y.kind = p->kind;
-            if (p->kind == SDFNMPC_PRIM_SPHERE) {
-                for (int k = 0; k < 3; ++k) { y.c0[k] = a[k]; y.h[k] = a[3]; }
-            } else if (p->kind == SDFNMPC_PRIM_BOX) {
-                for (int k = 0; k < 3; ++k) { y.c0[k] = 0.5 * (a[k] + a[3 + k]); y.h[k] = 0.5 * (a[3 + k] - a[k]); }
-            } else {
-                y.c0[0] = a[0]; y.c0[1] = a[1]; y.c0[2] = 0.5 * (a[3] + a[4]);
-                y.h[0] = y.h[1] = a[2]; y.h[2] = 0.5 * (a[4] - a[3]);
-            }
-            const double qs = std::max(std::max(std::fabs(m.q[0]), std::fabs(m.q[1])),
-                                       std::max(std::fabs(m.q[2]), std::fabs(m.q[3])));  // no overflow in the norm
-            double q[4];
-            for (int k = 0; k < 4; ++k) q[k] = m.q[k] / qs;
-            const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-            const double q0 = q[0] / qn, q1 = q[1] / qn, q2 = q[2] / qn, q3 = q[3] / qn;
-            y.R0[0] = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3;
-            y.R0[1] = 2 * (q1 * q2 - q0 * q3);
-            y.R0[2] = 2 * (q1 * q3 + q0 * q2);
-            y.R0[3] = 2 * (q1 * q2 + q0 * q3);
-            y.R0[4] = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3;
-            y.R0[5] = 2 * (q2 * q3 - q0 * q1);
-            y.R0[6] = 2 * (q1 * q3 - q0 * q2);
-            y.R0[7] = 2 * (q2 * q3 + q0 * q1);
-            y.R0[8] = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3;
-            for (int k = 0; k < 3; ++k) { y.v[k] = m.v[k]; y.amp[k] = m.amp[k]; }
-            y.yaw_rate = m.yaw_rate; y.omega = m.omega; y.phase = m.phase;
+            if (hm) scene_dyn_fill(hm[(size_t)s * SCENE_MAX_PRIMS + i], p, motion + (p - prims));
         }
     }
     ScopedDevice sd(ctx->device);
@@ -2616,19 +2640,6 @@ extern "C" int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* c
     return SDFNMPC_OK;
 }
 
-// kind, values and ranges of one primitive, as sdfnmpc_scene_create checks them; na = the number of values read
-static int scene_prim_check(const sdfnmpc_prim* p, int* na) {
-    const double* a = p->a;
-    bool ok = false;
-    if (p->kind == SDFNMPC_PRIM_SPHERE) { *na = 4; ok = a[3] > 0.0; }
-    else if (p->kind == SDFNMPC_PRIM_BOX) { *na = 6; ok = a[0] < a[3] && a[1] < a[4] && a[2] < a[5]; }
-    else if (p->kind == SDFNMPC_PRIM_CYLINDER) { *na = 5; ok = a[2] > 0.0 && a[3] < a[4]; }
-    else return fail(SDFNMPC_E_ARG, "scene: unknown primitive kind (0 sphere, 1 box, 2 cylinder)");
-    for (int k = 0; k < *na; ++k) ok = ok && std::isfinite(a[k]);
-    if (!ok) return fail(SDFNMPC_E_ARG, "scene: a primitive needs finite values, a radius > 0 and lo < hi");
-    return SDFNMPC_OK;
-}
-
 static void scene_prim_bbox(const sdfnmpc_prim& p, double* lo, double* hi) {
     const double* a = p.a;
     if (p.kind == SDFNMPC_PRIM_SPHERE) {
@@ -2643,8 +2654,12 @@ static void scene_prim_bbox(const sdfnmpc_prim& p, double* lo, double* hi) {
 
 // Static scenes of up to SDFNMPC_SCENE_LARGE_MAX_PRIMS primitives with a uniform grid each, built here on the host
 // (the layout: SceneGridHdr, scene_kernels.h; why the inflation and the padding: scene_grid.hip)
-extern "C" int sdfnmpc_scene_create_large(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
-                                          double cell, sdfnmpc_scene** out) {
+// mcount == NULL: the indexed set of sdfnmpc_scene_create_large.  Otherwise mcount [S] in 0..32, mprims and mmotion
+// (or NULL) already checked by the caller: the movers of a mixed set (sdfnmpc_scene_create_mixed), appended to the
+// device image as mcount [S] | ScenePrimDyn [S][32]; the grid covers the static primitives only
+static int scene_create_indexed(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims, double cell,
+                                const int* mcount, const sdfnmpc_prim* mprims, const sdfnmpc_prim_motion* mmotion,
+                                sdfnmpc_scene** out) {
     if (!ctx || !count || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create_large");
     *out = nullptr;
     if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "scene: S must be 1..2^20");
@@ -2754,7 +2769,17 @@ extern "C" int sdfnmpc_scene_create_large(sdfnmpc_ctx* ctx, int S, const int* co
     const size_t o_pf = up16(o_pd + (size_t)total * sizeof(ScenePrimD));
     const size_t o_cs = up16(o_pf + (size_t)total * sizeof(ScenePrimF));
     const size_t o_ci = up16(o_cs + cell_start.size() * sizeof(int));
-    std::vector<char> host(up16(o_ci + cell_items.size() * sizeof(int)) + 16, 0);
+    const size_t o_mc = up16(o_ci + cell_items.size() * sizeof(int)) + 16;  // the indexed set's image ends here
+    const size_t o_dyn = up16(o_mc + (size_t)S * sizeof(int));
+    std::vector<char> host(mcount ? o_dyn + (size_t)S * SCENE_MAX_PRIMS * sizeof(ScenePrimDyn) : o_mc, 0);
+    if (mcount) {
+        std::memcpy(host.data() + o_mc, mcount, (size_t)S * sizeof(int));
+        ScenePrimDyn* hm = (ScenePrimDyn*)(host.data() + o_dyn);
+        const sdfnmpc_prim* q = mprims;
+        for (int s = 0; s < S; ++s)
+            for (int i = 0; i < mcount[s]; ++i, ++q)
+                scene_dyn_fill(hm[(size_t)s * SCENE_MAX_PRIMS + i], q, mmotion ? mmotion + (q - mprims) : nullptr);
+    }
     std::memcpy(host.data(), count, (size_t)S * sizeof(int));
     std::memcpy(host.data() + o_hdr, hdr.data(), (size_t)S * sizeof(SceneGridHdr));
     ScenePrimD* hd = (ScenePrimD*)(host.data() + o_pd);
@@ -2783,8 +2808,44 @@ extern "C" int sdfnmpc_scene_create_large(sdfnmpc_ctx* ctx, int S, const int* co
     char* d = (char*)sc->dmem;
     sc->dev = SceneDev{S, (const int*)d, (const ScenePrimF*)(d + o_pf), (const ScenePrimD*)(d + o_pd),
                        (const SceneGridHdr*)(d + o_hdr), (const int*)(d + o_cs), (const int*)(d + o_ci)};
+    if (mcount) {
+        sc->mcount = (const int*)(d + o_mc);
+        sc->dyn = (const ScenePrimDyn*)(d + o_dyn);
+    }
     *out = sc;
     return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_create_large(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
+                                          double cell, sdfnmpc_scene** out) {
+    return scene_create_indexed(ctx, S, count, prims, cell, nullptr, nullptr, nullptr, out);
+}
+
+// An indexed static set plus up to 32 movers per scene (scene_grid.hip's *_mixed kernels).  The movers are checked
+// here as sdfnmpc_scene_create_moving checks its primitives, the static set by the builder of
+// sdfnmpc_scene_create_large; without a mover in any scene the handle is that function's
+extern "C" int sdfnmpc_scene_create_mixed(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
+                                          double cell, const int* mcount, const sdfnmpc_prim* mprims,
+                                          const sdfnmpc_prim_motion* mmotion, sdfnmpc_scene** out) {
+    if (!ctx || !count || !mcount || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create_mixed");
+    *out = nullptr;
+    if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "scene: S must be 1..2^20");
+    long long mtotal = 0;
+    for (int s = 0; s < S; ++s) {
+        if (mcount[s] < 0 || mcount[s] > SCENE_MAX_PRIMS)
+            return fail(SDFNMPC_E_ARG, "scene: at most 32 movers per scene (and no negative count)");
+        mtotal += mcount[s];
+    }
+    if (mtotal > 0 && !mprims) return fail(SDFNMPC_E_ARG, "scene: NULL movers");
+    bool dynamic = false;
+    if (int rc = scene_motion_check(mmotion, mtotal, &dynamic)) return rc;
+    for (long long i = 0; i < mtotal; ++i) {
+        int na;
+        if (int rc = scene_prim_check(mprims + i, &na)) return rc;
+    }
+    // a mover without motion still takes the mover path: the set is mixed as soon as it holds one
+    const bool mixed = mtotal > 0;
+    return scene_create_indexed(ctx, S, count, prims, cell, mixed ? mcount : nullptr, mprims, mmotion, out);
 }
 
 extern "C" int sdfnmpc_scene_is_indexed(const sdfnmpc_scene* sc) { return sc && sc->dev.ghdr; }
@@ -2847,8 +2908,12 @@ extern "C" int sdfnmpc_scene_render_launch_(sdfnmpc_ctx* ctx, const SceneRenderA
 extern "C" int sdfnmpc_scene_render_launch_at_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const SceneRenderArgs* a,
                                                double t) {
     if (!sc->dyn) return sdfnmpc_scene_render_launch_(ctx, a);
-    const SceneRenderDynArgs da{*a, sc->dyn, t};
+    const SceneRenderDynArgs da{*a, sc->dyn, t, sc->mcount};
     ScopedDevice sd(ctx->device);
+    if (a->sc.ghdr) {  // a mixed set: the grid plus movers
+        HIPCHK(timed(ctx, "scene_render_mixed", [&] { return launch_scene_render_mixed(da, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     HIPCHK(timed(ctx, "scene_render_dyn", [&] { return launch_scene_render_dyn(da, ctx->stream); }));
     return SDFNMPC_OK;
 }
@@ -2914,12 +2979,17 @@ extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* 
     if (!points || !out) return fail(SDFNMPC_E_ARG, "scene_distance: NULL points or output");
     SceneDistArgs a{sc->dev, points, p_to_scene, n, std::max(1LL, n / sc->S), out};
     ScopedDevice sd(ctx->device);
+    if (a.sc.ghdr && sc->dyn) {  // a mixed set: the grid plus movers at the points' times
+        const SceneDistDynArgs da{a, sc->dyn, times, sc->mcount};
+        HIPCHK(timed(ctx, "scene_dist_mixed", [&] { return launch_scene_distance_mixed(da, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (a.sc.ghdr) {  // an indexed set is static: the times do not matter
         HIPCHK(timed(ctx, "scene_dist_grid", [&] { return launch_scene_distance_grid(a, ctx->stream); }));
         return SDFNMPC_OK;
     }
     if (sc->dyn) {
-        const SceneDistDynArgs da{a, sc->dyn, times};
+        const SceneDistDynArgs da{a, sc->dyn, times, nullptr};
         HIPCHK(timed(ctx, "scene_dist_dyn", [&] { return launch_scene_distance_dyn(da, ctx->stream); }));
         return SDFNMPC_OK;
     }
@@ -2939,7 +3009,7 @@ extern "C" int sdfnmpc_scene_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf
     if (o->scene->ctx != ctx) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: the scene lives on another context");
     if (B > 0 && (!x || !p || !h || !Jh)) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: NULL x, p, h or Jh");
     SceneSdfArgs a{};
-    a.sc = o->scene->dev; a.dyn = o->scene->dyn; a.scene_of = o->scene_of;
+    a.sc = o->scene->dev; a.dyn = o->scene->dyn; a.mcount = o->scene->mcount; a.scene_of = o->scene_of;
     a.rows = (long long)B * (N + 1); a.N1 = N + 1; a.np = np;
     a.x = x; a.p = p; a.h = h; a.Jh = Jh;
     a.max_df = o->max_df; a.t0 = o->t0; a.tau = o->tau;

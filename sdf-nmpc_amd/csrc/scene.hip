@@ -141,27 +141,9 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_render_dyn_kernel(SceneRend
     const int b = blockIdx.y, tid = threadIdx.x;
     const int s = A.scene_of ? min(max(A.scene_of[b], 0), A.sc.S - 1) : 0;
     const int cnt = min(A.sc.count[s], SCENE_MAX_PRIMS);
-    if (tid < cnt) {
-        const ScenePrimDyn& P = D.dyn[(size_t)s * SCENE_MAX_PRIMS + tid];
-        double c[3], R[9], e[3];
-        prim_frame(P, D.t, c, R);
-        const double* Wp = A.W_p_C + (size_t)b * 3;
-        const double* WR = A.W_R_C + (size_t)b * 9;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) e[j] = Wp[j] - c[j];
-        ScenePrimFrame F;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            F.o[j] = (float)(R[j] * e[0] + R[3 + j] * e[1] + R[6 + j] * e[2]);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) F.M[j * 3 + k] = (float)(R[j] * WR[k] + R[3 + j] * WR[3 + k] + R[6 + j] * WR[6 + k]);
-        }
-        F.h0 = (float)P.h[0];
-        F.h1 = (float)P.h[1];
-        F.hz = (float)P.h[2];
-        F.kind = P.kind;
-        fr[tid] = F;
-    }
+    if (tid < cnt)
+        fr[tid] = prim_camera_frame(D.dyn[(size_t)s * SCENE_MAX_PRIMS + tid], D.t, A.W_p_C + (size_t)b * 3,
+                                    A.W_R_C + (size_t)b * 9);
     const int w = A.W, h = A.H;
     if (A.is_spherical) {
         for (int t = tid; t < w + h; t += SCENE_BLOCK) {
@@ -194,42 +176,7 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_render_dyn_kernel(SceneRend
 
     float best = INFINITY;
     for (int i = 0; i < cnt; ++i) {  // wave-uniform: one scene per block
-        const float4* q = (const float4*)&fr[i];
-        const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-        const float ox = q0.x, oy = q0.y, oz = q0.z, h0 = q0.w, h2z = q3.z, h1 = q3.w;
-        const float dx = fmaf(q1.x, cx, fmaf(q1.y, cy, q1.z * cz));  // d' = M d_cam
-        const float dy = fmaf(q1.w, cx, fmaf(q2.x, cy, q2.y * cz));
-        const float dz = fmaf(q2.z, cx, fmaf(q2.w, cy, q3.x * cz));
-        const int kind = __builtin_amdgcn_readfirstlane(__float_as_int(q3.y));  // one scene per block: uniform
-        float tn = -INFINITY, tf = INFINITY;
-        if (kind == 0) {  // sphere of radius h0 about the origin
-            const float ex = -ox, ey = -oy, ez = -oz;
-            const float bb = fmaf(ex, dx, fmaf(ey, dy, ez * dz));
-            const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey), wz = fmaf(-bb, dz, ez);
-            const float hh = fmaf(h0, h0, -fmaf(wx, wx, fmaf(wy, wy, wz * wz)));  // r^2 - |w|^2
-            const float cc = fmaf(ex, ex, fmaf(ey, ey, ez * ez)) - h0 * h0;
-            if (hh >= 0.f) root_interval(bb, cc, fsqrt(hh), tn, tf);
-            else tf = -INFINITY;
-        } else if (kind == 1) {  // box of half extents h0, h1, h2z
-            slab(-h0, h0, ox, frcp(dx), tn, tf);
-            slab(-h1, h1, oy, frcp(dy), tn, tf);
-            slab(-h2z, h2z, oz, frcp(dz), tn, tf);
-        } else {  // capped cylinder along its own z: radius h0, half height h2z
-            const float ex = -ox, ey = -oy;
-            const float aa = fmaf(dx, dx, dy * dy), e2 = fmaf(ex, ex, ey * ey);
-            if (aa > 1e-12f) {
-                const float k = frcp(aa);
-                const float bb = fmaf(ex, dx, ey * dy) * k;
-                const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey);
-                const float hh = fmaf(h0, h0, -fmaf(wx, wx, wy * wy));
-                if (hh >= 0.f) root_interval(bb, (e2 - h0 * h0) * k, fsqrt(hh * k), tn, tf);
-                else tf = -INFINITY;
-            } else if (e2 > h0 * h0) {
-                tf = -INFINITY;
-            }
-            slab(-h2z, h2z, oz, frcp(dz), tn, tf);  // the caps
-        }
-        if (tn <= tf && tf >= 0.f) best = fminf(best, fmaxf(tn, 0.f));
+        best = frame_ray_hit(best, fr[i], cx, cy, cz);
     }
     float val = A.dmax;  // a miss
     if (best < INFINITY) val = fminf(A.is_depth ? best * cx : best, A.dmax);
@@ -248,20 +195,7 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_distance_dyn_kernel(SceneDi
     const double t = D.times ? D.times[j] : 0.0;
     const double px = A.points[j * 3], py = A.points[j * 3 + 1], pz = A.points[j * 3 + 2];
     double best = INFINITY;
-    for (int i = 0; i < cnt; ++i) {
-        double c[3], R[9];
-        prim_frame(P[i], t, c, R);
-        const double ex = px - c[0], ey = py - c[1], ez = pz - c[2];
-        const double qx = R[0] * ex + R[3] * ey + R[6] * ez;
-        const double qy = R[1] * ex + R[4] * ey + R[7] * ez;
-        const double qz = R[2] * ex + R[5] * ey + R[8] * ez;
-        const double* h = P[i].h;
-        double d;
-        if (P[i].kind == 0) d = sqrt(qx * qx + qy * qy + qz * qz) - h[0];
-        else if (P[i].kind == 1) d = sd_excess3(fabs(qx) - h[0], fabs(qy) - h[1], fabs(qz) - h[2]);
-        else d = sd_excess3(sqrt(qx * qx + qy * qy) - h[0], fabs(qz) - h[2], -INFINITY);
-        best = fmin(best, d);
-    }
+    for (int i = 0; i < cnt; ++i) best = fmin(best, frame_distance(P[i], t, px, py, pz));
     A.out[j] = best;
 }
 

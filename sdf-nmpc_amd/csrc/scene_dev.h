@@ -1,7 +1,9 @@
 // Device code shared by the scene kernels (scene.hip, scene_sdf.hip, scene_grid.hip): a primitive's frame, and the
 // per-primitive work of the three queries -- the ray's hit, the signed distance, the distance with its gradient.  The
 // brute-force kernels and the grid kernels call the same functions, so that a query over a subset of the primitives
-// that holds the minimiser returns the bits of the query over all of them.
+// that holds the minimiser returns the bits of the query over all of them.  The same holds for a primitive with a
+// frame (frame_ray_hit, frame_distance, frame_sd_grad): the dynamic kernels and the mixed kernels of scene_grid.hip
+// (a grid of static primitives plus up to 32 movers) call one function each.
 #pragma once
 #include "scene_kernels.h"
 
@@ -79,6 +81,74 @@ __device__ __forceinline__ float prim_ray_hit(float best, int kind, float a0, fl
     }
     if (tn <= tf && tf >= 0.f) best = fminf(best, fmaxf(tn, 0.f));
     return best;
+}
+
+// best = min(best, the hit of the camera-frame unit direction (cx, cy, cz) with a staged primitive frame F): the ray
+// is taken into the primitive's frame, o' = F.o, d' = F.M d_cam, and meets the canonical centred shape (sphere of
+// radius h0, box of half extents h0, h1, hz, capped cylinder of radius h0 and half height hz along its own z) in one
+// interval, as in prim_ray_hit.  F.kind must be uniform over the wave (one scene per block).  The loop body of
+// scene_render_dyn_kernel, shared with scene_render_mixed_kernel.
+__device__ __forceinline__ float frame_ray_hit(float best, const ScenePrimFrame& F, float cx, float cy, float cz) {
+    const float4* q = (const float4*)&F;
+    const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+    const float ox = q0.x, oy = q0.y, oz = q0.z, h0 = q0.w, h2z = q3.z, h1 = q3.w;
+    const float dx = fmaf(q1.x, cx, fmaf(q1.y, cy, q1.z * cz));  // d' = M d_cam
+    const float dy = fmaf(q1.w, cx, fmaf(q2.x, cy, q2.y * cz));
+    const float dz = fmaf(q2.z, cx, fmaf(q2.w, cy, q3.x * cz));
+    const int kind = __builtin_amdgcn_readfirstlane(__float_as_int(q3.y));  // one scene per block: uniform
+    float tn = -INFINITY, tf = INFINITY;
+    if (kind == 0) {  // sphere of radius h0 about the origin
+        const float ex = -ox, ey = -oy, ez = -oz;
+        const float bb = fmaf(ex, dx, fmaf(ey, dy, ez * dz));
+        const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey), wz = fmaf(-bb, dz, ez);
+        const float hh = fmaf(h0, h0, -fmaf(wx, wx, fmaf(wy, wy, wz * wz)));  // r^2 - |w|^2
+        const float cc = fmaf(ex, ex, fmaf(ey, ey, ez * ez)) - h0 * h0;
+        if (hh >= 0.f) root_interval(bb, cc, fsqrt(hh), tn, tf);
+        else tf = -INFINITY;
+    } else if (kind == 1) {  // box of half extents h0, h1, h2z
+        slab(-h0, h0, ox, frcp(dx), tn, tf);
+        slab(-h1, h1, oy, frcp(dy), tn, tf);
+        slab(-h2z, h2z, oz, frcp(dz), tn, tf);
+    } else {  // capped cylinder along its own z: radius h0, half height h2z
+        const float ex = -ox, ey = -oy;
+        const float aa = fmaf(dx, dx, dy * dy), e2 = fmaf(ex, ex, ey * ey);
+        if (aa > 1e-12f) {
+            const float k = frcp(aa);
+            const float bb = fmaf(ex, dx, ey * dy) * k;
+            const float wx = fmaf(-bb, dx, ex), wy = fmaf(-bb, dy, ey);
+            const float hh = fmaf(h0, h0, -fmaf(wx, wx, wy * wy));
+            if (hh >= 0.f) root_interval(bb, (e2 - h0 * h0) * k, fsqrt(hh * k), tn, tf);
+            else tf = -INFINITY;
+        } else if (e2 > h0 * h0) {
+            tf = -INFINITY;
+        }
+        slab(-h2z, h2z, oz, frcp(dz), tn, tf);  // the caps
+    }
+    if (tn <= tf && tf >= 0.f) best = fminf(best, fmaxf(tn, 0.f));
+    return best;
+}
+
+// what lane i < count of a block stages for primitive P of a dynamic set: the camera (W_p_C, W_R_C) in the
+// primitive's frame at time t, o' = R(t)^T (W_p_C - c(t)) and M = R(t)^T W_R_C, formed in fp64 and rounded to fp32
+// once (world-scale coordinates cancel in fp64, before the rounding)
+__device__ __forceinline__ ScenePrimFrame prim_camera_frame(const ScenePrimDyn& P, double t, const double* Wp,
+                                                            const double* WR) {
+    double c[3], R[9], e[3];
+    prim_frame(P, t, c, R);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) e[j] = Wp[j] - c[j];
+    ScenePrimFrame F;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        F.o[j] = (float)(R[j] * e[0] + R[3 + j] * e[1] + R[6 + j] * e[2]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) F.M[j * 3 + k] = (float)(R[j] * WR[k] + R[3 + j] * WR[3 + k] + R[6 + j] * WR[6 + k]);
+    }
+    F.h0 = (float)P.h[0];
+    F.h1 = (float)P.h[1];
+    F.hz = (float)P.h[2];
+    F.kind = P.kind;
+    return F;
 }
 
 // ---- the signed distance (fp64)
@@ -174,6 +244,52 @@ __device__ __forceinline__ double prim_sd_grad(const ScenePrimD& P, double px, d
         h0 = a[2]; hz = 0.5 * (a[4] - a[3]);
     }
     return shape_sd(kind, qx, qy, qz, h0, h1, hz, gx, gy, gz);
+}
+
+// ---- a primitive with a frame, at a point and a time (fp64): shared by the dynamic kernels and the mixed ones
+// a0 b0 + a1 b1 + a2 b2 with the fused operations written out.  Left to the compiler, which product of such a sum
+// stays a multiplication depends on the code around it: the same source line gave the mixed rows kernel a last bit
+// that the dynamic one did not have.  This is the form the dynamic kernels have always compiled to.
+__device__ __forceinline__ double dot3_pinned(double a0, double b0, double a1, double b1, double a2, double b2) {
+    return fma(a2, b2, fma(a0, b0, a1 * b1));
+}
+
+// the point in the primitive's frame at time t, q = R(t)^T (p - c(t)); R is left to the caller for the gradient
+__device__ __forceinline__ void frame_point(const ScenePrimDyn& P, double t, double px, double py, double pz, double* R,
+                                            double& qx, double& qy, double& qz) {
+    double c[3];
+    prim_frame(P, t, c, R);
+    const double ex = px - c[0], ey = py - c[1], ez = pz - c[2];
+    qx = dot3_pinned(R[0], ex, R[3], ey, R[6], ez);
+    qy = dot3_pinned(R[1], ex, R[4], ey, R[7], ez);
+    qz = dot3_pinned(R[2], ex, R[5], ey, R[8], ez);
+}
+
+// the signed distance from (px, py, pz) to the primitive at time t: scene_distance_kernel's closed forms on the
+// canonical shape
+__device__ __forceinline__ double frame_distance(const ScenePrimDyn& P, double t, double px, double py, double pz) {
+    double R[9], qx, qy, qz;
+    frame_point(P, t, px, py, pz, R, qx, qy, qz);
+    const double* h = P.h;
+    if (P.kind == 0) return sqrt(qx * qx + qy * qy + qz * qz) - h[0];
+    if (P.kind == 1) return sd_excess3(fabs(qx) - h[0], fabs(qy) - h[1], fabs(qz) - h[2]);
+    return sd_excess3(sqrt(qx * qx + qy * qy) - h[0], fabs(qz) - h[2], -INFINITY);
+}
+
+// the same distance through shape_sd with its gradient (gx, gy, gz) in the primitive's frame; the world gradient is
+// R g (frame_grad_world) with the R returned here
+__device__ __forceinline__ double frame_sd_grad(const ScenePrimDyn& P, double t, double px, double py, double pz,
+                                                double* R, double& gx, double& gy, double& gz) {
+    double qx, qy, qz;
+    frame_point(P, t, px, py, pz, R, qx, qy, qz);
+    return shape_sd(P.kind, qx, qy, qz, P.h[0], P.h[1], P.h[2], gx, gy, gz);
+}
+
+__device__ __forceinline__ void frame_grad_world(const double* R, double gx, double gy, double gz, double& bx,
+                                                 double& by, double& bz) {
+    bx = dot3_pinned(R[0], gx, R[1], gy, R[2], gz);
+    by = dot3_pinned(R[3], gx, R[4], gy, R[5], gz);
+    bz = dot3_pinned(R[6], gx, R[7], gy, R[8], gz);
 }
 
 // ---- the uniform grid of an indexed scene set (scene_grid.hip)

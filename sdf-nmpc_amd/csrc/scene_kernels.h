@@ -87,6 +87,10 @@ struct SceneRenderDynArgs {
     SceneRenderArgs r;
     const ScenePrimDyn* dyn; // [S][SCENE_MAX_PRIMS]
     double t;
+    // a mixed set (sdfnmpc_scene_create_mixed; r.sc.ghdr != nullptr): dyn holds mcount[s] <= SCENE_MAX_PRIMS movers per
+    // scene beside the indexed static primitives that r.sc.count counts.  Last, here and below: the dynamic kernels'
+    // arguments stay where they were
+    const int* mcount;       // [S], or nullptr: a dynamic set
 };
 
 struct ScenePoseArgs {
@@ -108,6 +112,7 @@ struct SceneDistDynArgs {
     SceneDistArgs d;
     const ScenePrimDyn* dyn; // [S][SCENE_MAX_PRIMS]
     const double* times;     // [n] or nullptr (t = 0)
+    const int* mcount;       // [S]: the movers of a mixed set (SceneRenderDynArgs), or nullptr
 };
 
 // scene_sdf.hip: the scene's exact distance written as the SDF row of h / J_h for rows = B (N+1) node rows
@@ -123,6 +128,7 @@ struct SceneSdfArgs {
     double* Jh;              // [rows][10][3]: column 2 is written
     double max_df, t0;
     const double* tau;       // [N1] or nullptr: node k at time t0 + tau[k] (dynamic sets)
+    const int* mcount;       // [S]: the movers of a mixed set (SceneRenderDynArgs), or nullptr
 };
 
 inline size_t scene_render_lds_bytes(int h, int w, int is_spherical) {
@@ -139,5 +145,10 @@ hipError_t launch_scene_sdf_rows(const SceneSdfArgs& a, hipStream_t s);
 hipError_t launch_scene_render_grid(const SceneRenderArgs& a, hipStream_t s);
 hipError_t launch_scene_distance_grid(const SceneDistArgs& a, hipStream_t s);
 hipError_t launch_scene_sdf_rows_grid(const SceneSdfArgs& a, hipStream_t s);
+// scene_grid.hip: the same queries of a mixed set (a.sc.ghdr, dyn and mcount all non-null): the minimum over the
+// indexed static primitives and the movers at the query's time
+hipError_t launch_scene_render_mixed(const SceneRenderDynArgs& a, hipStream_t s);
+hipError_t launch_scene_distance_mixed(const SceneDistDynArgs& a, hipStream_t s);
+hipError_t launch_scene_sdf_rows_mixed(const SceneSdfArgs& a, hipStream_t s);
 
 }  // namespace sdfn

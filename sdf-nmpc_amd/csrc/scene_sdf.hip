@@ -34,19 +34,11 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_sdf_rows_kernel(SceneSdfArg
         const ScenePrimDyn* P = A.dyn + s * SCENE_MAX_PRIMS;
         const double t = A.tau ? A.t0 + A.tau[k] : A.t0;
         for (int i = 0; i < cnt; ++i) {
-            double c[3], R[9];
-            prim_frame(P[i], t, c, R);
-            const double ex = px - c[0], ey = py - c[1], ez = pz - c[2];
-            const double qx = R[0] * ex + R[3] * ey + R[6] * ez;
-            const double qy = R[1] * ex + R[4] * ey + R[7] * ez;
-            const double qz = R[2] * ex + R[5] * ey + R[8] * ez;
-            double gx, gy, gz;
-            const double d = shape_sd(P[i].kind, qx, qy, qz, P[i].h[0], P[i].h[1], P[i].h[2], gx, gy, gz);
+            double R[9], gx, gy, gz;
+            const double d = frame_sd_grad(P[i], t, px, py, pz, R, gx, gy, gz);
             if (d < best) {  // the lowest index on a tie
                 best = d;
-                bx = R[0] * gx + R[1] * gy + R[2] * gz;
-                by = R[3] * gx + R[4] * gy + R[5] * gz;
-                bz = R[6] * gx + R[7] * gy + R[8] * gz;
+                frame_grad_world(R, gx, gy, gz, bx, by, bz);
             }
         }
     } else {

@@ -20,7 +20,8 @@ oriented box, a sphere with v a moving obstacle.  ``render(..., t=)``, ``render_
 
 A scene of more than 32 primitives takes a grid index: ``Scene(ctx, Scene.forest(1024, lo, hi), grid=True)`` holds up
 to 65536 static primitives per scene, and every call above -- and every consumer of a scene -- returns what the plain
-scene would return, bit for bit, from kernels that visit only the grid cells along a ray or around a point.
+scene would return, bit for bit, from kernels that visit only the grid cells along a ray or around a point.  A few
+moving obstacles go beside it: ``Scene(ctx, forest, grid=True, movers=Scene.crowd(8, lo, hi))``.
 
 World frame z up; camera frame x forward, y left, z up, the pixel grid of ``ColChecker``.  There is no CPU path.
 """
@@ -44,9 +45,13 @@ class Scene:
     """One scene (a list of primitives) or several (a list of lists) with ``scene_of`` [B], the scene of each
     instance; without ``scene_of`` every instance sees scene 0.  At most 32 primitives per scene; with ``grid=True``
     at most 65536 static ones, indexed by a uniform grid of cell edge ``cell`` [m] (None: the library's default, a
-    function of the primitives) -- ``is_indexed``.  The primitives are checked by the library when the scene is
-    created (SdfnmpcError: too many, an unknown kind, a radius <= 0, lo >= hi, a grid too fine); ``scene_of``, ``cell``
-    and a moving primitive in an indexed scene (ValueError) are checked here."""
+    function of the primitives) -- ``is_indexed``.  An indexed scene may also hold ``movers``: a list of at most 32
+    plain or ``Scene.moving`` primitives (a list of lists, one per scene, for several scenes) that are not in the grid
+    and may move anywhere; every query then is the minimum over both sets at its time, and the scene is both
+    ``is_indexed`` and ``is_dynamic``.  The primitives are checked by the library when the scene is
+    created (SdfnmpcError: too many, an unknown kind, a radius <= 0, lo >= hi, a grid too fine); ``scene_of``, ``cell``,
+    ``movers`` without ``grid`` or of another number of scenes, and a moving primitive among ``prims`` of an indexed
+    scene (ValueError) are checked here."""
 
     @staticmethod
     def sphere(center, radius):
@@ -103,26 +108,81 @@ class Scene:
             xy = np.where(inside[:, None], c + e * (rc * (1.0 + 1e-9) / dist)[:, None], xy)
         return [Scene.cylinder(xy[i], rad[i], lo[2], hi[2]) for i in range(n)]
 
-    def __init__(self, ctx: "_lib.Context", prims, scene_of=None, grid=False, cell=None):
+    @staticmethod
+    def crowd(n, lo, hi, radius=(0.2, 0.35), height=1.8, speed=(0.5, 1.5), seed=0):
+        """A list of n moving upright cylinders in the box lo .. hi, the mover counterpart of ``forest``: radii uniform
+        in radius = (r0, r1), every cylinder from lo[2] to lo[2] + height, each swinging as amp sin(omega t + phase)
+        along a random horizontal direction about a centre uniform in the box.  amp is 0.5 to 0.95 of the largest
+        amplitude that keeps the cylinder inside lo .. hi for every t, the peak speed amp omega is uniform in speed =
+        (s0, s1) [m/s], the phase uniform in [0, 2 pi).  A pure function of its arguments through
+        numpy.random.default_rng(seed)."""
+        lo, hi = _three(lo, "lo"), _three(hi, "hi")
+        r0, r1 = (float(v) for v in radius)
+        s0, s1 = (float(v) for v in speed)
+        n, height = int(n), float(height)
+        if n < 0 or not (lo[0] < hi[0] and lo[1] < hi[1] and lo[2] < hi[2]) or not 0.0 < r0 <= r1 or not 0.0 < s0 <= s1:
+            raise ValueError("Scene.crowd: n >= 0, lo < hi, 0 < r0 <= r1 and 0 < s0 <= s1 required")
+        if not 0.0 < height <= hi[2] - lo[2] or not (hi[0] - lo[0] > 2.0 * r1 and hi[1] - lo[1] > 2.0 * r1):
+            raise ValueError("Scene.crowd: 0 < height <= hi[2] - lo[2] and a box wider than 2 r1 required")
+        rng = np.random.default_rng(seed)
+        rad = rng.uniform(r0, r1, size=n)
+        u = rng.uniform(0.0, 1.0, size=(n, 2))
+        ang = rng.uniform(0.0, 2.0 * np.pi, size=n)
+        frac = rng.uniform(0.5, 0.95, size=n)
+        peak = rng.uniform(s0, s1, size=n)
+        phase = rng.uniform(0.0, 2.0 * np.pi, size=n)
+        out = []
+        for i in range(n):
+            room_lo, room_hi = np.array(lo[:2]) + rad[i], np.array(hi[:2]) - rad[i]
+            c = room_lo + u[i] * (room_hi - room_lo)
+            d = np.array([np.cos(ang[i]), np.sin(ang[i])])
+            with np.errstate(divide="ignore"):  # a direction along an axis: no limit from the other one
+                amax = float(np.min(np.minimum(c - room_lo, room_hi - c) / np.abs(d)))
+            a = frac[i] * max(amax, 0.0)
+            omega = peak[i] / a if a > 0.0 else 0.0
+            out.append(Scene.moving(Scene.cylinder(c, rad[i], lo[2], lo[2] + height), amp=(a * d[0], a * d[1], 0.0),
+                                    omega=omega, phase=phase[i]))
+        return out
+
+    def __init__(self, ctx: "_lib.Context", prims, scene_of=None, grid=False, cell=None, movers=None):
         is_prim = lambda p: isinstance(p, tuple) and len(p) in (2, 3) and isinstance(p[0], (str, int))
+
+        def flatten(scenes):
+            flat, motion = [], []
+            for s in scenes:
+                for kind, vals, *mo in s:
+                    vals = list(vals)
+                    if len(vals) > 6:
+                        raise ValueError(f"primitive {kind!r}: at most 6 values, got {len(vals)}")
+                    # an unknown kind goes to the library as it is (it refuses it)
+                    flat.append((_lib.PRIM_KINDS.get(kind, kind if isinstance(kind, int) else -1), vals))
+                    motion.append(mo[0] if mo else None)
+            return flat, motion
+
         scenes = [list(prims)] if all(is_prim(p) for p in prims) else [list(s) for s in prims]
-        flat, motion = [], []
-        for s in scenes:
-            for kind, vals, *mo in s:
-                vals = list(vals)
-                if len(vals) > 6:
-                    raise ValueError(f"primitive {kind!r}: at most 6 values, got {len(vals)}")
-                # an unknown kind goes to the library as it is (it refuses it)
-                flat.append((_lib.PRIM_KINDS.get(kind, kind if isinstance(kind, int) else -1), vals))
-                motion.append(mo[0] if mo else None)
+        flat, motion = flatten(scenes)
         self.ctx, self.S = ctx, len(scenes)
         self._sdf_users = weakref.WeakSet()  # controllers whose SDF source this scene is (Nmpc.set_sdf_scene)
+        if movers is not None and not grid:
+            raise ValueError("Scene: movers need grid=True (a plain scene takes Scene.moving primitives in prims)")
         if grid:
             if any(m is not None for m in motion):
-                raise ValueError("Scene: an indexed scene (grid=True) holds static primitives only, no Scene.moving")
+                raise ValueError("Scene: an indexed scene (grid=True) holds static primitives only, no Scene.moving "
+                                 "(moving primitives go into movers=)")
             if cell is not None and not (np.isfinite(float(cell)) and float(cell) > 0.0):
                 raise ValueError("Scene: cell must be positive and finite (None: the default)")
-            self.h = _lib.scene_create_large(ctx, [len(s) for s in scenes], flat, 0.0 if cell is None else float(cell))
+            cell = 0.0 if cell is None else float(cell)
+            if movers is None:  # the call an indexed scene has always made
+                self.h = _lib.scene_create_large(ctx, [len(s) for s in scenes], flat, cell)
+            else:
+                movers = list(movers)
+                mlists = [[] for _ in scenes] if not movers else \
+                    [movers] if all(is_prim(p) for p in movers) else [list(m) for m in movers]
+                if len(mlists) != len(scenes):
+                    raise ValueError(f"Scene: movers holds {len(mlists)} lists for {len(scenes)} scenes")
+                mflat, mmotion = flatten(mlists)
+                self.h = _lib.scene_create_mixed(ctx, [len(s) for s in scenes], flat, cell, [len(m) for m in mlists],
+                                                 mflat, mmotion if any(m is not None for m in mmotion) else None)
         else:
             if cell is not None:
                 raise ValueError("Scene: cell needs grid=True")
