@@ -42,6 +42,11 @@
  *   sdfnmpc_solver_rollout             K iterations of the loop a user of Nmpc writes around it (controller.py:
  *                                      65-81 set_x0 + solve, with RefGen before and the simulator after), enqueued
  *                                      without a host round trip: references from x0, shift, RTI step, plant
+ *   sdfnmpc_vehicle_* / sdfnmpc_plant_step_vehicle
+ *                                      (no reference interface) an imperfect vehicle and estimator around the plant:
+ *                                      input delay, thrust lag, rotor drag, gusts, bias and noise on the state
+ *                                      estimate, reproducible per (seed, instance, frame); sdfnmpc_rollout_args.vehicle
+ *                                      carries it through every rollout
  *
  *   sdfnmpc_colcheck                   ColChecker.check_image_points (utils/collision_checker.py:23-125)
  *   sdfnmpc_udf / sdfnmpc_sdf_truth    DfComputer.get_udf / get_sdf (utils/df_computer.py:85-221): the distance
@@ -85,7 +90,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 14
+#define SDFNMPC_ABI_VERSION 15
 
 enum {
     SDFNMPC_OK = 0,
@@ -341,7 +346,8 @@ int sdfnmpc_ctx_set_tile_rows(sdfnmpc_ctx* ctx, int rows);
 /* per-kernel HIP-event timing on the context stream (off by default) */
 int sdfnmpc_ctx_enable_timing(sdfnmpc_ctx* ctx, int on);
 /* kernel: "sdf_mlp", "sdf_hoist", "linearize", "rti_qp", "plant", "scene_render", "scene_pose", "scene_dist",
- * "scene_render_dyn", "scene_dist_dyn", "scene_render_grid", "scene_dist_grid", "scene_sdf_rows_grid", "morph", "outlier_rm", "sensor_degrade", ...; synchronizes the stream(s) */
+ * "scene_render_dyn", "scene_dist_dyn", "scene_render_grid", "scene_dist_grid", "scene_sdf_rows_grid", "morph", "outlier_rm", "sensor_degrade",
+ * "plant_vehicle", "vehicle_begin", "vehicle_reset", ...; synchronizes the stream(s) */
 int sdfnmpc_ctx_kernel_stats(sdfnmpc_ctx* ctx, const char* kernel, double* total_ms, long long* launches);
 int sdfnmpc_ctx_reset_stats(sdfnmpc_ctx* ctx);
 
@@ -615,6 +621,56 @@ typedef struct {
 int sdfnmpc_plant_step(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* opts, int B, const double* x, const double* u,
                        double* x_next);
 
+/* ---- the vehicle model of a closed loop (csrc/vehicle.hip) ----
+ * What stands between the controller's command and the state it is told about.  The vehicle object owns, per instance,
+ * the true state x_true [10], the actual specific thrust gamma_act, the gust acceleration w [3] and a ring of the last
+ * d commands.  One plant call at frame f with the command u_cmd does, in this order:
+ *   1. input delay: u_app = ring[f % d], ring[f % d] <- u_cmd (d = 0: u_app = u_cmd);
+ *   2. gust: w <- phi w + gust_std sqrt(1 - phi^2) xi(f), phi = exp(-dt / gust_tau) (gust_tau = 0: phi = 0), held over
+ *      the period and added to dv/dt beside acc_dist;
+ *   3. thrust lag: d(gamma_act)/dt = (gamma_cmd - gamma_act) / tau_m, gamma_cmd = u_app[0] gamma gamma_scale, an 11th
+ *      RK4 state whose stage value is the thrust of f_expl (tau_m = 0: the thrust is gamma_cmd);
+ *   4. rotor drag: dv/dt gains -R diag(drag) R^T v, R the body rotation the model's thrust uses;
+ *   5. RK4 with the plant's substeps, tableau and accumulation order: x_true, gamma_act;
+ *   6. the estimate of frame f + 1: p + bias_p + est_std_p n_p, v + bias_v + est_std_v n_v, the attitude turned about
+ *      world z by bias_yaw + est_std_yaw n_yaw (no noise and no bias: a copy of x_true).
+ * Random numbers: Philox4x32-10 under the key seed with the counter (j, frame, stream, 1), j = 0..4, stream =
+ * stream_id[b] or b; call j gives the normals n[2j] = N(w0, w1), n[2j+1] = N(w2, w3), Box-Muller's cosine branch on
+ * the 24-bit uniforms ((w >> 8) + 1) 2^-24 in fp64; n[0..2] -> xi, n[3..5] -> n_p, n[6..8] -> n_v, n[9] -> n_yaw.
+ * A model with everything off (d = 0, gust_std = 0, tau_m = 0, no drag, no estimate error) runs the plant's own
+ * kernel: the bits of sdfnmpc_plant_step. */
+typedef struct {
+    uint64_t seed;
+    int d;                         /* input delay in control periods, 0..8 */
+    double tau_m;                  /* thrust lag, s (0: none) */
+    double drag[3];                /* rotor drag coefficients in the body frame, 1/s */
+    double gust_std, gust_tau;     /* stationary standard deviation (m/s^2) and correlation time (s) of the gust */
+    double est_std_p, est_std_v, est_std_yaw; /* estimate noise: m, m/s, rad */
+    const double* est_bias;        /* device [B][7] (p, v, yaw) or NULL */
+    const int* stream_id;          /* device [B] or NULL: the instance index */
+    double g, gamma;               /* what a reset writes: gamma_act = g, every ring slot the hover input (g / gamma, 0, 0,
+                                      0); g > 0, gamma > 0 */
+} sdfnmpc_vehicle_opts;
+typedef struct sdfnmpc_vehicle sdfnmpc_vehicle;
+
+/* SDFNMPC_E_ARG: NULL arguments, B < 0, d outside 0..8, a negative or non-finite tau, std or drag coefficient, g or
+ * gamma not positive and finite.  The new vehicle is reset and its true state is zero until _begin. */
+int sdfnmpc_vehicle_create(sdfnmpc_ctx* ctx, const sdfnmpc_vehicle_opts* opts, int B, sdfnmpc_vehicle** out);
+void sdfnmpc_vehicle_destroy(sdfnmpc_vehicle* v);
+/* ring <- hover, gamma_act <- g, w <- 0 (asynchronous on the context stream) */
+int sdfnmpc_vehicle_reset(sdfnmpc_vehicle* v);
+/* x_true <- x0; x0 <- est(x_true, frame): the one launch before a loop's first step.  x0: device [B][10], in the
+ * truth, out the estimate.  est is a pure function, so the begin of a second chunk writes what the first chunk's last
+ * plant call wrote. */
+int sdfnmpc_vehicle_begin(sdfnmpc_ctx* ctx, sdfnmpc_vehicle* v, double* x0, int frame);
+/* the vehicle's true state, device [B][10] (owned by the vehicle) */
+double* sdfnmpc_vehicle_x_true(sdfnmpc_vehicle* v);
+/* one plant call (above) on the vehicle's own true state under the command u [B][4] at `frame`; x_est_out [B][10]
+ * receives the estimate of frame + 1.  SDFNMPC_E_ARG: the plant's refusals, a vehicle of another context or batch
+ * size, frame < 0 or frame + 1 overflowing.  B == 0 is a no-op. */
+int sdfnmpc_plant_step_vehicle(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* opts, sdfnmpc_vehicle* v, int B,
+                               const double* u, int frame, double* x_est_out);
+
 /* K closed-loop steps of the solver's B instances without a host round trip.  Per step, in the order Nmpc.solve
  * uses: (1) with ref: sdfnmpc_pack_refs from the current x0 into the solver's p / yref / W / yNref / WN; (2) with
  * shift > 0: sdfnmpc_solver_shift(shift); (3) the SQP-RTI step of sdfnmpc_solver_step; (4) the plant on the solver's
@@ -639,6 +695,16 @@ typedef struct {
     int *status_log, *iters_log;   /* device [B][K], each may be NULL */
     float* pts_log;                /* device [B][K+1][3] or NULL: the fp32 camera-frame position W_R_Co^T (x[:3] -
                                       W_p_Co) of every logged state, the pose from node 0 of the instance's p row */
+    /* ---- the vehicle model (all NULL / 0: the plant on x0, as above).  With a vehicle (after sdfnmpc_vehicle_begin on
+     * the solver's x0 field) step (4) is sdfnmpc_plant_step_vehicle at frame frame0 + k: the true state lives in the
+     * vehicle, x0 receives the estimate; x_log and pts_log log the true state, u_log the command.  In the rollouts
+     * that render, the camera pose comes from the true state and the body pose written into p from the estimate;
+     * references and sdfnmpc_solver_rollout_scene_sdf's pose refresh read the estimate.  SDFNMPC_E_ARG: a vehicle of
+     * another context or batch size, frame0 < 0 or frame0 + steps overflowing, xhat_log / uapp_log without a vehicle. */
+    sdfnmpc_vehicle* vehicle;
+    int frame0;
+    double* xhat_log;              /* device [B][K+1][10] or NULL: the estimates; row 0 = what _begin wrote */
+    double* uapp_log;              /* device [B][K][4] or NULL: the applied (delayed) inputs */
 } sdfnmpc_rollout_args;
 
 int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args);

@@ -47,6 +47,8 @@ SYMBOLS = [
     "sdfnmpc_img_sdf_rows", "sdfnmpc_img_sdf_pool", "sdfnmpc_solver_set_sdf_image", "sdfnmpc_solver_rollout_image_sdf",
     "sdfnmpc_solver_rollout_image_recon",
     "sdfnmpc_scene_create_large", "sdfnmpc_scene_is_indexed", "sdfnmpc_scene_create_mixed",
+    "sdfnmpc_vehicle_create", "sdfnmpc_vehicle_destroy", "sdfnmpc_vehicle_reset", "sdfnmpc_vehicle_begin",
+    "sdfnmpc_vehicle_x_true", "sdfnmpc_plant_step_vehicle",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -153,7 +155,14 @@ class PlantOptsC(C.Structure):
 class RolloutArgsC(C.Structure):
     _fields_ = [("steps", C.c_int), ("shift", C.c_int), ("ref", C.POINTER(RefOptsC))] + [
         (n, C.c_void_p) for n in ("wp_p", "wp_q", "vw", "wrow")] + [("n_wp", C.c_int), ("plant", PlantOptsC)] + [
-        (n, C.c_void_p) for n in ("x_log", "u_log", "status_log", "iters_log", "pts_log")]
+        (n, C.c_void_p) for n in ("x_log", "u_log", "status_log", "iters_log", "pts_log")] + [
+        ("vehicle", C.c_void_p), ("frame0", C.c_int), ("xhat_log", C.c_void_p), ("uapp_log", C.c_void_p)]
+
+
+class VehicleOptsC(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("d", C.c_int), ("tau_m", C.c_double), ("drag", C.c_double * 3)] + [
+        (n, C.c_double) for n in ("gust_std", "gust_tau", "est_std_p", "est_std_v", "est_std_yaw")] + [
+        ("est_bias", C.c_void_p), ("stream_id", C.c_void_p), ("g", C.c_double), ("gamma", C.c_double)]
 
 
 SCENE_MAX_PRIMS = 32  # SDFNMPC_SCENE_MAX_PRIMS
@@ -299,11 +308,17 @@ def load():
         "sdfnmpc_solver_set_sdf_image": (i, [vp, P(ImgSdfOptsC)]),
         "sdfnmpc_solver_rollout_image_sdf": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d, P(SensorOptsC), vp]),
         "sdfnmpc_solver_rollout_image_recon": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d, P(SensorOptsC), vp, vp]),
+        "sdfnmpc_vehicle_create": (i, [vp, P(VehicleOptsC), i, P(vp)]),
+        "sdfnmpc_vehicle_destroy": (None, [vp]),
+        "sdfnmpc_vehicle_reset": (i, [vp]),
+        "sdfnmpc_vehicle_begin": (i, [vp, vp, vp, i]),
+        "sdfnmpc_vehicle_x_true": (vp, [vp]),
+        "sdfnmpc_plant_step_vehicle": (i, [vp, P(PlantOptsC), vp, i, vp, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 14:
+    if lib.sdfnmpc_abi_version() != 15:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -1055,6 +1070,14 @@ class FieldView:
         return out
 
 
+def _vehicle_fields(vehicle):
+    """The trailing fields of sdfnmpc_rollout_args: (handle, frame0, xhat_log, uapp_log) or None."""
+    if vehicle is None:
+        return None, 0, None, None
+    h, frame0, xhat_log, uapp_log = vehicle
+    return h, int(frame0), _ptr(xhat_log), _ptr(uapp_log)
+
+
 class Solver:
     """sdfnmpc_solver: B instances' SQP-RTI workspace on one context, driven with host arrays."""
 
@@ -1121,7 +1144,7 @@ class Solver:
 
     def rollout(self, steps: int, plant: PlantOpts, x_log, u_log, status_log=None, iters_log=None, pts_log=None,
                 shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0,
-                perceive: "PerceiveArgsC" = None, scene_clock=None, sensor=None):
+                perceive: "PerceiveArgsC" = None, scene_clock=None, sensor=None, vehicle=None):
         """Enqueue sdfnmpc_solver_rollout: `steps` closed-loop steps (references from x0 when ref is given,
         shift, RTI step, plant) from the x0 field, logged into the device arrays x_log [B][K+1][10], u_log
         [B][K][4], status_log / iters_log [B][K] int32 and pts_log [B][K+1][3] float32.  Asynchronous: `wait`
@@ -1129,11 +1152,13 @@ class Solver:
         pose before every `every`-th step (sdfnmpc_solver_rollout_perceive); the caller keeps what it names alive.
         scene_clock: (t0, dt) -- the image before step k shows the scene at t0 + (phase + k) dt
         (sdfnmpc_solver_rollout_perceive_at).  sensor: (SensorOptsC, scratch [B][h][w] float32 or None) -- the
-        degradation of every new image before it is encoded (sdfnmpc_solver_rollout_perceive_sensor)."""
+        degradation of every new image before it is encoded (sdfnmpc_solver_rollout_perceive_sensor).  vehicle:
+        (handle, frame0, xhat_log [B][K+1][10] or None, uapp_log [B][K][4] or None) -- the vehicle model whose plant
+        call replaces the plant's (sdfnmpc_rollout_args.vehicle), after sdfnmpc_vehicle_begin on the x0 field."""
         a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
                          _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
-                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
-        self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log)
+                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log), *_vehicle_fields(vehicle))
+        self._rollout_keep = (vehicle, a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log)
         if sensor is not None:
             self._rollout_keep += (perceive, sensor)
             t0, dt = (0.0, 0.0) if scene_clock is None else scene_clock
@@ -1162,14 +1187,14 @@ class Solver:
 
     def rollout_scene_sdf(self, steps: int, plant: PlantOpts, x_log, u_log, pose: "PoseRefreshArgsC" = None, phase: int = 0,
                           t0: float = 0.0, dt: float = 0.0, status_log=None, iters_log=None, pts_log=None, shift: int = 0,
-                          ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0):
+                          ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0, vehicle=None):
         """Enqueue sdfnmpc_solver_rollout_scene_sdf: `rollout` for a solver with a scene source -- before step k the
         scene time t0 + (phase + k) dt, and with pose (a PoseRefreshArgsC) the camera pose of p refreshed from the
         plant state before every `every`-th step."""
         a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
                          _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
-                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
-        self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, pose)
+                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log), *_vehicle_fields(vehicle))
+        self._rollout_keep = (vehicle, a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, pose)
         _check(load().sdfnmpc_solver_rollout_scene_sdf(self.h, C.byref(a), None if pose is None else C.byref(pose),
                                                        int(phase), float(t0), float(dt)))
 
@@ -1183,7 +1208,7 @@ class Solver:
     def rollout_image_sdf(self, steps: int, plant: PlantOpts, x_log, u_log, perceive: "PerceiveArgsC" = None,
                           t0: float = 0.0, dt: float = 0.0, sensor=None, status_log=None, iters_log=None, pts_log=None,
                           shift: int = 0, ref: RefOptsC = None, wp_p=None, wp_q=None, vw=None, wrow=None, n_wp: int = 0,
-                          dec: "VaeDec" = None):
+                          dec: "VaeDec" = None, vehicle=None):
         """Enqueue sdfnmpc_solver_rollout_image_sdf: `rollout` for a solver with an image source -- with perceive (a
         PerceiveArgsC without an encoder) a new normalised image rendered into the source, degraded by sensor
         ((SensorOptsC, scratch), normalised units), pooled in unsigned mode, and the camera pose of p refreshed, before
@@ -1191,8 +1216,8 @@ class Solver:
         the camera buffer perceive names, encoded by perceive's encoder, and its reconstruction goes into the source."""
         a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
                          _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
-                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log))
-        self._rollout_keep = (a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, perceive,
+                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log), *_vehicle_fields(vehicle))
+        self._rollout_keep = (vehicle, a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, perceive,
                               sensor, dec)
         if dec is not None:
             _check(load().sdfnmpc_solver_rollout_image_recon(

@@ -34,11 +34,15 @@ class Rollout:
     and pts [B, K+1, 3] the camera-frame positions they were taken at (else None); with a scene clearance [B, K+1],
     the exact signed distance of every logged position to the instance's scene at the time of that row, t [K+1]
     (the scene's clock at every log row), and with keep_img img [B, h, w] float32, the last images rendered (raw
-    sensor values)."""
+    sensor values).  With a vehicle model x, col, pts and clearance are the true vehicle's, u the commands, and
+    xhat [B, K+1, 10] the state estimates the controller was given (row 0 the one it started from), u_applied [B, K, 4]
+    the inputs the vehicle applied (the delayed commands); else both None."""
 
-    def __init__(self, x, u, status, iters, col=None, pts=None, clearance=None, img=None, t=None):
+    def __init__(self, x, u, status, iters, col=None, pts=None, clearance=None, img=None, t=None, xhat=None,
+                 u_applied=None):
         self.x, self.u, self.status, self.iters, self.col, self.pts = x, u, status, iters, col, pts
         self.clearance, self.img, self.t = clearance, img, t
+        self.xhat, self.u_applied = xhat, u_applied
 
 
 class Nmpc:
@@ -319,7 +323,7 @@ class Nmpc:
 
     def rollout(self, steps, refs=None, wps=None, vw=None, weights=None, plant=None, imgs=None, safe_ball_size=0.0,
                 outside='col', scene=None, vae=None, perceive_every=1, img_shape=None, keep_img=False,
-                perceive_phase=0, scene_t0=0.0, scene_dt=None, sensor=None):
+                perceive_phase=0, scene_t0=0.0, scene_dt=None, sensor=None, vehicle=None):
         """``steps`` closed-loop control steps on the device, without a host round trip between them: per
         step the references from the current state (``refs``), the shift (mpc.shift), one SQP-RTI iteration
         and the plant advanced by u_0 -- the loop ``set_x0``; ``gen_refs_device``; ``solve``; simulate,
@@ -367,6 +371,17 @@ class Nmpc:
         and ``t`` are measured against the scene as above.  Without ``scene`` the image and the pose stay as set, and
         ``imgs`` labelling works as without a source.
 
+        vehicle: a ``vehicle.VehicleModel`` on the controller's context with ``batch`` instances -- the plant call of
+        every step is the model's (input delay, thrust lag, rotor drag, gusts) on its own true state, at frame
+        ``perceive_phase + k``, and the controller is given the model's estimate of that state
+        (sdfnmpc_rollout_args.vehicle): the loop ``vehicle.begin``; [``set_x0(estimate)``; ``gen_refs_device``;
+        ``solve``; ``vehicle.step``].  The rollout starts from the true state of the last ``set_x0``; ``x``, ``col``,
+        ``pts`` and ``clearance`` are the true vehicle's, ``u`` the commands, and the result gains ``xhat`` and
+        ``u_applied``.  With ``scene`` the camera sees from the true state while the body pose in p comes from the
+        estimate; references (and a scene source's pose refresh) read the estimate.  The model keeps its hidden states
+        from call to call (``vehicle.reset()`` starts afresh), so chunks with ``perceive_phase`` carried equal the uncut
+        rollout.  Afterwards ``self.x0`` is the true final state.
+
         Returns a ``Rollout`` of numpy arrays, batch-leading also for one instance: x [B, K+1, 10] (row 0 the
         start), u [B, K, 4], status / iters [B, K]; with imgs also col [B, K+1] bool and pts [B, K+1, 3] float32.
         Afterwards ``self.x0`` is the final plant state and ``ocp.u`` / ``ocp.status`` / ``ocp.iters`` are the last
@@ -384,6 +399,13 @@ class Nmpc:
         K, Bn, ctx, solver = int(steps), max(self.B, 1), self.ocp.ctx, self.ocp.parts[0].solver
         if K < 1:
             raise ValueError(f"rollout of {K} steps: at least one")
+        if vehicle is not None:
+            if vehicle.ctx is not ctx:
+                raise ValueError("rollout(): the VehicleModel must be built on the controller's context (ctx=nmpc.ocp.ctx)")
+            if vehicle.B != Bn:
+                raise ValueError(f"rollout(): the VehicleModel has {vehicle.B} instances, the batch has {Bn}")
+            if int(perceive_phase) < 0:
+                raise ValueError(f"perceive_phase {perceive_phase}: the vehicle's first frame, at least 0")
         src = self._sdf_scene
         if src is not None:  # a scene source: the exact distance, no perception (every refusal before any upload)
             if scene is not None or vae is not None or sensor is not None:
@@ -495,6 +517,10 @@ class Nmpc:
                "iters_log": _lib.DeviceArray(ctx, (Bn, max(K, 1)), np.int32)}
         if dimg is not None:
             log["pts_log"] = _lib.DeviceArray(ctx, (Bn, K + 1, 3), np.float32)
+        if vehicle is not None:  # x0 holds the truth: the model takes it and leaves its estimate there
+            vehicle.begin(solver.field("x0"), int(perceive_phase))
+            vlog = (_lib.DeviceArray(ctx, (Bn, K + 1, 10)), _lib.DeviceArray(ctx, (Bn, max(K, 1), 4)))
+            kw["vehicle"] = (vehicle.h, int(perceive_phase)) + vlog
         if src is not None:  # the pose the FOV rows read is refreshed from the plant state, the scene's clock per step
             ws = _pose_workspaces(ctx, Bn)
             pose = _lib.PoseRefreshArgsC(int(perceive_every), *_extrinsics(self.cfg), *[ws[k].data_ptr() for k in POSE_WS])
@@ -514,6 +540,8 @@ class Nmpc:
             solver.rollout(K, plant, shift=int(self.cfg.mpc.shift), **kw, **log)
         u0 = solver.wait().copy()
         out = Rollout(log["x_log"].numpy(), log["u_log"].numpy(), log["status_log"].numpy(), log["iters_log"].numpy())
+        if vehicle is not None:
+            out.xhat, out.u_applied = vlog[0].numpy(), vlog[1].numpy()
         if dimg is not None:
             s = self.cfg.sensor
             pts = _lib.FieldView(log["pts_log"].data_ptr(), (Bn * (K + 1), 3), np.float32, ctx)

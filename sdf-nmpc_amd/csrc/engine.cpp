@@ -28,6 +28,7 @@
 #include "plant_kernels.h"
 #include "scene_kernels.h"
 #include "sensor_kernels.h"
+#include "vehicle_kernels.h"
 
 using namespace sdfn;
 
@@ -1839,6 +1840,167 @@ extern "C" int sdfnmpc_plant_step(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* o,
     PlantArgs a{};
     if (int rc = sdfnmpc_plant_args_(o, B, x, u, x_next, &a)) return rc;
     return sdfnmpc_plant_launch_(ctx, &a);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the vehicle model around the plant (vehicle.hip).  The object owns the hidden states of B instances in one device
+// block; a model with everything off is `neutral` and every entry point runs the plant's own kernel (or a copy) for it.
+struct sdfnmpc_vehicle {
+    sdfnmpc_ctx* ctx = nullptr;
+    int device = 0;
+    int B = 0;
+    sdfnmpc_vehicle_opts o{};
+    bool neutral = false;
+    double* block = nullptr;  // [x_true B*10 | gamma_act B | w B*3 | ring B*d*4 | pose scratch B*12]
+    double *x_true = nullptr, *gamma_act = nullptr, *w = nullptr, *ring = nullptr, *scratch = nullptr;
+};
+
+// the option half of a VehicleArgs block (the plant's block, the frame, x_est and the logs are the caller's)
+static VehicleArgs vehicle_block(const sdfnmpc_vehicle* v, double dt) {
+    const sdfnmpc_vehicle_opts& o = v->o;
+    VehicleArgs a{};
+    a.P.B = v->B;
+    a.P.x_next = v->x_true;
+    a.key0 = (unsigned)(o.seed & 0xffffffffull); a.key1 = (unsigned)(o.seed >> 32);
+    a.delay = o.d;
+    a.itau_m = o.tau_m > 0.0 ? 1.0 / o.tau_m : 0.0;
+    for (int i = 0; i < 3; ++i) a.drag[i] = o.drag[i];
+    a.has_drag = o.drag[0] > 0.0 || o.drag[1] > 0.0 || o.drag[2] > 0.0;
+    a.has_gust = o.gust_std > 0.0;
+    if (a.has_gust) {
+        a.gust_phi = o.gust_tau > 0.0 ? std::exp(-dt / o.gust_tau) : 0.0;
+        a.gust_amp = o.gust_std * std::sqrt(1.0 - a.gust_phi * a.gust_phi);
+    }
+    a.est_std_p = o.est_std_p; a.est_std_v = o.est_std_v; a.est_std_yaw = o.est_std_yaw;
+    a.est_noise = o.est_std_p > 0.0 || o.est_std_v > 0.0 || o.est_std_yaw > 0.0;
+    a.est_bias = o.est_bias; a.stream_id = o.stream_id;
+    a.gamma_act = v->gamma_act; a.w = v->w; a.ring = v->ring;
+    a.g = o.g; a.hover_u0 = o.g / o.gamma;
+    return a;
+}
+
+extern "C" int sdfnmpc_vehicle_create(sdfnmpc_ctx* ctx, const sdfnmpc_vehicle_opts* o, int B, sdfnmpc_vehicle** out) {
+    if (!ctx || !o || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_vehicle_create");
+    *out = nullptr;
+    if (B < 0) return fail(SDFNMPC_E_ARG, "vehicle: B < 0");
+    if (o->d < 0 || o->d > VEHICLE_MAX_DELAY) return fail(SDFNMPC_E_ARG, "vehicle opts: d (the input delay) must be 0..8");
+    auto ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    if (!ok(o->tau_m) || !ok(o->gust_std) || !ok(o->gust_tau) || !ok(o->est_std_p) || !ok(o->est_std_v) ||
+        !ok(o->est_std_yaw) || !ok(o->drag[0]) || !ok(o->drag[1]) || !ok(o->drag[2]))
+        return fail(SDFNMPC_E_ARG, "vehicle opts: tau_m, drag, gust_std, gust_tau and est_std_* must be finite and not negative");
+    if (!(o->g > 0.0) || !std::isfinite(o->g) || !(o->gamma > 0.0) || !std::isfinite(o->gamma))
+        return fail(SDFNMPC_E_ARG, "vehicle opts: g and gamma must be positive and finite");
+    auto* v = new sdfnmpc_vehicle();
+    v->ctx = ctx; v->device = ctx->device; v->B = B; v->o = *o;
+    v->neutral = o->d == 0 && o->tau_m == 0.0 && o->gust_std == 0.0 && o->drag[0] == 0.0 && o->drag[1] == 0.0 &&
+                 o->drag[2] == 0.0 && o->est_std_p == 0.0 && o->est_std_v == 0.0 && o->est_std_yaw == 0.0 && !o->est_bias;
+    ScopedDevice sd(ctx->device);
+    const size_t n = (size_t)B * (10 + 1 + 3 + 4 * (size_t)o->d + 12);
+    hipError_t e = hipMalloc((void**)&v->block, n * sizeof(double) + 16);
+    if (e == hipSuccess) e = hipMemsetAsync(v->block, 0, n * sizeof(double) + 16, ctx->stream);
+    if (e != hipSuccess) {
+        if (v->block) (void)hipFree(v->block);
+        delete v;
+        return fail(SDFNMPC_E_HIP, std::string("vehicle buffers: ") + hipGetErrorString(e));
+    }
+    v->x_true = v->block;
+    v->gamma_act = v->x_true + (size_t)B * 10;
+    v->w = v->gamma_act + B;
+    v->ring = v->w + (size_t)B * 3;
+    v->scratch = v->ring + (size_t)B * 4 * o->d;
+    if (int rc = sdfnmpc_vehicle_reset(v)) {
+        sdfnmpc_vehicle_destroy(v);
+        return rc;
+    }
+    *out = v;
+    return SDFNMPC_OK;
+}
+
+extern "C" void sdfnmpc_vehicle_destroy(sdfnmpc_vehicle* v) {
+    if (!v) return;
+    ScopedDevice sd(v->device);  // the context may be gone already: hipFree waits for the device
+    if (v->block) (void)hipFree(v->block);
+    delete v;
+}
+
+extern "C" int sdfnmpc_vehicle_reset(sdfnmpc_vehicle* v) {
+    if (!v) return fail(SDFNMPC_E_ARG, "NULL vehicle");
+    const VehicleArgs a = vehicle_block(v, 1.0);
+    ScopedDevice sd(v->ctx->device);
+    HIPCHK(timed(v->ctx, "vehicle_reset", [&] { return launch_vehicle_reset(a, v->ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+extern "C" double* sdfnmpc_vehicle_x_true(sdfnmpc_vehicle* v) { return v ? v->x_true : nullptr; }
+
+extern "C" int sdfnmpc_vehicle_begin(sdfnmpc_ctx* ctx, sdfnmpc_vehicle* v, double* x0, int frame) {
+    if (!ctx || !v) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_vehicle_begin");
+    if (v->ctx != ctx) return fail(SDFNMPC_E_ARG, "vehicle_begin: the vehicle lives on another context");
+    if (frame < 0) return fail(SDFNMPC_E_ARG, "vehicle_begin: frame must be >= 0");
+    if (v->B == 0) return SDFNMPC_OK;
+    if (!x0) return fail(SDFNMPC_E_ARG, "vehicle_begin: NULL x0");
+    ScopedDevice sd(ctx->device);
+    if (v->neutral || (!v->o.est_bias && v->o.est_std_p == 0.0 && v->o.est_std_v == 0.0 && v->o.est_std_yaw == 0.0)) {
+        HIPCHK(hipMemcpyAsync(v->x_true, x0, (size_t)v->B * 80, hipMemcpyDeviceToDevice, ctx->stream));  // est = identity
+        return SDFNMPC_OK;
+    }
+    VehicleArgs a = vehicle_block(v, 1.0);
+    a.x_est = x0;
+    a.frame = (unsigned)frame;
+    HIPCHK(timed(ctx, "vehicle_begin", [&] { return launch_vehicle_begin(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+// for solver.hip: refuse a vehicle a rollout cannot use; *neutral, and where its true state and pose scratch live
+extern "C" int sdfnmpc_vehicle_info_(const sdfnmpc_vehicle* v, const sdfnmpc_ctx* ctx, int B, int* neutral,
+                                     double** x_true, double** scratch) {
+    if (!v) return fail(SDFNMPC_E_ARG, "NULL vehicle");
+    if (v->ctx != ctx) return fail(SDFNMPC_E_ARG, "vehicle: it lives on another context");
+    if (v->B != B) return fail(SDFNMPC_E_ARG, "vehicle: built for " + std::to_string(v->B) + " instances, not " + std::to_string(B));
+    if (neutral) *neutral = v->neutral ? 1 : 0;
+    if (x_true) *x_true = v->x_true;
+    if (scratch) *scratch = v->scratch;
+    return SDFNMPC_OK;
+}
+
+// the vehicle's kernel block around a filled plant block (whose x / x_next become the vehicle's true state); frame and
+// the log pointers are the caller's.  Nothing is launched.
+extern "C" int sdfnmpc_vehicle_args_(const sdfnmpc_vehicle* v, const PlantArgs* pa, double* x_est, VehicleArgs* out) {
+    if (!v || !pa || !out || (v->B > 0 && !x_est)) return fail(SDFNMPC_E_ARG, "vehicle: NULL argument");
+    if (x_est == v->x_true) return fail(SDFNMPC_E_ARG, "vehicle: the estimate must not be written into the true state");
+    VehicleArgs a = vehicle_block(v, pa->dt);
+    a.P = *pa;
+    a.P.x = a.P.x_next = v->x_true;
+    a.x_est = x_est;
+    *out = a;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_vehicle_launch_(sdfnmpc_ctx* ctx, const VehicleArgs* a) {
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "plant_vehicle", [&] { return launch_vehicle(*a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_plant_step_vehicle(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* o, sdfnmpc_vehicle* v, int B,
+                                          const double* u, int frame, double* x_est_out) {
+    if (!ctx) return fail(SDFNMPC_E_ARG, "NULL context");
+    if (int rc = sdfnmpc_vehicle_info_(v, ctx, B, nullptr, nullptr, nullptr)) return rc;
+    if (frame < 0 || frame == 2147483647) return fail(SDFNMPC_E_ARG, "plant_step_vehicle: frame must be >= 0 and frame + 1 must not overflow");
+    if (B > 0 && !x_est_out) return fail(SDFNMPC_E_ARG, "plant_step_vehicle: NULL x_est_out");
+    PlantArgs pa{};
+    if (int rc = sdfnmpc_plant_args_(o, B, v->x_true, u, v->x_true, &pa)) return rc;
+    if (B == 0) return SDFNMPC_OK;
+    if (v->neutral) {  // the plant's own kernel, and the estimate a copy of the truth
+        if (int rc = sdfnmpc_plant_launch_(ctx, &pa)) return rc;
+        ScopedDevice sd(ctx->device);
+        HIPCHK(hipMemcpyAsync(x_est_out, v->x_true, (size_t)B * 80, hipMemcpyDeviceToDevice, ctx->stream));
+        return SDFNMPC_OK;
+    }
+    VehicleArgs va{};
+    if (int rc = sdfnmpc_vehicle_args_(v, &pa, x_est_out, &va)) return rc;
+    va.frame = (unsigned)frame;
+    return sdfnmpc_vehicle_launch_(ctx, &va);
 }
 
 // ------------------------------------------------------------------------------------------------

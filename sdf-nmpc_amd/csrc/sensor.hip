@@ -2,24 +2,12 @@
 // image scene.hip renders -- no-return pixels, range noise that grows with range, dropped pixels, erased boxes -- the
 // reference's training augmentation (utils/data.py:11-108: additive Gaussian noise on the valid pixels, erased
 // pixels and RandomErasing boxes, 0 the invalid value) as a reproducible function of (seed, stream, frame, pixel).
+#include "philox.h"
 #include "sensor_kernels.h"
 
 namespace sdfn {
 
 namespace {
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123)
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // One pixel per lane, in place, no atomics and no state: one Philox call with the counter (pixel, frame, stream, 0)
 // under the key seed.  Words 0 / 1 -> the Box-Muller uniforms in (0, 1], word 2 -> the dropout decision, an unsigned

@@ -20,12 +20,20 @@
 #include "ref_kernels.h"
 #include "scene_kernels.h"
 #include "sensor_kernels.h"
+#include "vehicle_kernels.h"
 
 extern "C" int sdfnmpc_solver_fail_(int code, const char* msg);  // engine.cpp: sets sdfnmpc_last_error
 // engine.cpp: the plant's option check + argument block, and its launch on the context stream (timed as "plant")
 extern "C" int sdfnmpc_plant_args_(const sdfnmpc_plant_opts* o, int B, const double* x, const double* u, double* x_next,
                                    sdfn::PlantArgs* out);
 extern "C" int sdfnmpc_plant_launch_(sdfnmpc_ctx* ctx, const sdfn::PlantArgs* a);
+// engine.cpp: the vehicle model around the plant -- what a rollout refuses about it, its argument block around a
+// filled plant block, and its launch (timed as "plant_vehicle")
+extern "C" int sdfnmpc_vehicle_info_(const sdfnmpc_vehicle* v, const sdfnmpc_ctx* ctx, int B, int* neutral, double** x_true,
+                                     double** scratch);
+extern "C" int sdfnmpc_vehicle_args_(const sdfnmpc_vehicle* v, const sdfn::PlantArgs* pa, double* x_est,
+                                     sdfn::VehicleArgs* out);
+extern "C" int sdfnmpc_vehicle_launch_(sdfnmpc_ctx* ctx, const sdfn::VehicleArgs* a);
 // engine.cpp: the same split for the scene kernels a perceiving rollout repeats, and where an encoder / a scene lives
 extern "C" int sdfnmpc_scene_render_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of,
                                           const sdfnmpc_img_opts* o, int H, int W, float scale, int B,
@@ -406,12 +414,35 @@ extern "C" int sdfnmpc_solver_step(sdfnmpc_solver* s) {
     return SDFNMPC_OK;
 }
 
+// The vehicle model of a rollout (sdfnmpc_rollout_args.vehicle).  on: the plant call of every step is the vehicle's,
+// on its own true state, and x0 receives the estimate.  neutral: a model with everything off -- the plant runs on x0
+// as without a vehicle, and the end of the rollout copies the logs and the final state the vehicle would have written.
+struct VehicleRun {
+    bool on = false, neutral = false;
+    sdfn::VehicleArgs va{};
+    double *x_true = nullptr, *scratch = nullptr;
+};
+
 // what every rollout refuses before its first launch: the step count and logs, the plant's options (pa is filled),
 // then what sdfnmpc_pack_refs would refuse (ra is filled when args->ref is set)
-static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, sdfn::PlantArgs& pa, sdfnmpc_ref_args& ra) {
+static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, sdfn::PlantArgs& pa, sdfnmpc_ref_args& ra,
+                        VehicleRun& vr) {
     if (a->steps < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
     if (!a->x_log || !a->u_log) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: x_log and u_log are required");
     if (int rc = sdfnmpc_plant_args_(&a->plant, s->B, s->x0, s->u0, s->x0, &pa)) return rc;
+    if (!a->vehicle) {
+        if (a->xhat_log || a->uapp_log)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: xhat_log and uapp_log need a vehicle");
+    } else {
+        int neutral = 0;
+        if (int rc = sdfnmpc_vehicle_info_(a->vehicle, s->ctx, s->B, &neutral, &vr.x_true, &vr.scratch)) return rc;
+        if (a->frame0 < 0 || (long long)a->frame0 + a->steps > 2147483647LL)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the vehicle's frame counter (frame0 + steps) overflows or frame0 < 0");
+        vr.neutral = neutral != 0;
+        vr.on = !vr.neutral;
+        if (vr.on)
+            if (int rc = sdfnmpc_vehicle_args_(a->vehicle, &pa, s->x0, &vr.va)) return rc;
+    }
     if (a->ref) {
         const int mode = a->ref->mode;
         if (mode < 0 || mode > 2) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref->mode must be 0, 1 or 2");
@@ -424,6 +455,40 @@ static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, sdfn::
         ra.wp_p = a->wp_p; ra.wp_q = a->wp_q; ra.vw = a->vw; ra.wrow = a->wrow;
         ra.p = s->p; ra.yref = s->yref; ra.W = s->W; ra.yNref = s->yNref; ra.WN = s->WN; ra.nyN = s->nyN;
     }
+    return SDFNMPC_OK;
+}
+
+// step k's plant call: the plant on x0, or the vehicle at frame frame0 + k (pa carries the log pointers either way)
+static int rollout_plant(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, sdfn::PlantArgs& pa, const VehicleRun& vr, int k) {
+    pa.k = k;
+    if (!vr.on) return sdfnmpc_plant_launch_(s->ctx, &pa);
+    sdfn::VehicleArgs va = vr.va;
+    va.P = pa;
+    va.P.x = va.P.x_next = vr.x_true;
+    va.frame = (unsigned)(a->frame0 + k);
+    va.xhat_log = a->xhat_log;
+    va.uapp_log = a->uapp_log;
+    return sdfnmpc_vehicle_launch_(s->ctx, &va);
+}
+
+// the poses of a perceiving step: the camera sees from where the vehicle is (its true state), the body pose the
+// controller is given comes from its estimate in x0 -- two launches, the unused pair of each into the vehicle's scratch
+static int rollout_pose(sdfnmpc_solver* s, const sdfn::ScenePoseArgs& spa, const VehicleRun& vr) {
+    if (!vr.on) return sdfnmpc_scene_pose_launch_(s->ctx, &spa);
+    sdfn::ScenePoseArgs cam = spa, body = spa;
+    cam.x = vr.x_true; cam.W_p_Bo = vr.scratch; cam.W_R_Bo = vr.scratch + (size_t)s->B * 3;
+    if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &cam)) return rc;
+    body.W_p_C = vr.scratch; body.W_R_C = vr.scratch + (size_t)s->B * 3;
+    return sdfnmpc_scene_pose_launch_(s->ctx, &body);
+}
+
+// after the last step: a neutral vehicle receives what its own kernel would have written
+static int rollout_end(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, const VehicleRun& vr) {
+    if (!vr.neutral) return SDFNMPC_OK;
+    const size_t B = s->B, K = a->steps;
+    SCHK(hipMemcpyAsync(vr.x_true, s->x0, B * 80, hipMemcpyDeviceToDevice, s->stream));
+    if (a->xhat_log) SCHK(hipMemcpyAsync(a->xhat_log, a->x_log, B * (K + 1) * 80, hipMemcpyDeviceToDevice, s->stream));
+    if (a->uapp_log) SCHK(hipMemcpyAsync(a->uapp_log, a->u_log, B * K * 32, hipMemcpyDeviceToDevice, s->stream));
     return SDFNMPC_OK;
 }
 
@@ -450,7 +515,8 @@ extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const s
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
     sdfn::PlantArgs pa{};
     sdfnmpc_ref_args ra{};
-    if (int rc = rollout_args(s, a, pa, ra)) return rc;
+    VehicleRun vr{};
+    if (int rc = rollout_args(s, a, pa, ra, vr)) return rc;
     // perception: the pose and render blocks, and what sdfnmpc_vae_encode / sdfnmpc_pack_refs (mode -1) would refuse
     sdfn::ScenePoseArgs spa{};
     sdfn::SceneRenderArgs sra{};
@@ -498,7 +564,7 @@ extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const s
     SolverDevice sd(s->device);
     for (int k = 0; k < a->steps; ++k) {
         if (pc && (k + pc->phase) % pc->every == 0) {  // a new image from the current state: pose, render, encode, set_latent
-            if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
+            if (int rc = rollout_pose(s, spa, vr)) return rc;
             // the scene's time at step k, t0 + (phase + k) dt: the product is rounded on its own (a volatile
             // temporary keeps the compiler from contracting it into a fused multiply-add), as a host loop forms it
             volatile double steps_dt = (double)(pc->phase + k) * dt;
@@ -513,9 +579,9 @@ extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const s
             if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
         if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
         if (int rc = step_enqueue(s)) return rc;
-        pa.k = k;
-        if (int rc = sdfnmpc_plant_launch_(s->ctx, &pa)) return rc;
+        if (int rc = rollout_plant(s, a, pa, vr, k)) return rc;
     }
+    if (int rc = rollout_end(s, a, vr)) return rc;
     SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
     s->pending = true;
     return SDFNMPC_OK;
@@ -581,7 +647,8 @@ extern "C" int sdfnmpc_solver_rollout_scene_sdf(sdfnmpc_solver* s, const sdfnmpc
     if (phase < 0) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: phase must be >= 0");
     sdfn::PlantArgs pa{};
     sdfnmpc_ref_args ra{};
-    if (int rc = rollout_args(s, a, pa, ra)) return rc;
+    VehicleRun vr{};
+    if (int rc = rollout_args(s, a, pa, ra, vr)) return rc;
     // the pose refresh: the pose block, and what sdfnmpc_pack_refs (mode -2) would refuse
     sdfn::ScenePoseArgs spa{};
     sdfnmpc_ref_opts po{};
@@ -617,9 +684,9 @@ extern "C" int sdfnmpc_solver_rollout_scene_sdf(sdfnmpc_solver* s, const sdfnmpc
             if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
         if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
         if (int rc = step_enqueue(s)) return rc;
-        pa.k = k;
-        if (int rc = sdfnmpc_plant_launch_(s->ctx, &pa)) return rc;
+        if (int rc = rollout_plant(s, a, pa, vr, k)) return rc;
     }
+    if (int rc = rollout_end(s, a, vr)) return rc;
     SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
     s->pending = true;
     return SDFNMPC_OK;
@@ -636,7 +703,8 @@ extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
     sdfn::PlantArgs pa{};
     sdfnmpc_ref_args ra{};
-    if (int rc = rollout_args(s, a, pa, ra)) return rc;
+    VehicleRun vr{};
+    if (int rc = rollout_args(s, a, pa, ra, vr)) return rc;
     // re-imaging: the pose and render blocks, the sensor's, and what sdfnmpc_pack_refs (mode -2) would refuse
     const sdfnmpc_img_sdf_opts& src = s->img_src;
     sdfn::ScenePoseArgs spa{};
@@ -682,7 +750,7 @@ extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc
     SolverDevice sd(s->device);
     for (int k = 0; k < a->steps; ++k) {
         if (pc && (k + pc->phase) % pc->every == 0) {  // a new image from the current state: pose, render, sensor, pool, pose into p
-            if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
+            if (int rc = rollout_pose(s, spa, vr)) return rc;
             // the scene's time at step k, the product rounded on its own as in sdfnmpc_solver_rollout_perceive_at
             volatile double steps_dt = (double)(pc->phase + k) * dt;
             const double t = t0 + steps_dt;
@@ -697,9 +765,9 @@ extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc
             if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
         if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
         if (int rc = step_enqueue(s)) return rc;
-        pa.k = k;
-        if (int rc = sdfnmpc_plant_launch_(s->ctx, &pa)) return rc;
+        if (int rc = rollout_plant(s, a, pa, vr, k)) return rc;
     }
+    if (int rc = rollout_end(s, a, vr)) return rc;
     SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
     s->pending = true;
     return SDFNMPC_OK;
@@ -717,7 +785,8 @@ extern "C" int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnm
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
     sdfn::PlantArgs pa{};
     sdfnmpc_ref_args ra{};
-    if (int rc = rollout_args(s, a, pa, ra)) return rc;
+    VehicleRun vr{};
+    if (int rc = rollout_args(s, a, pa, ra, vr)) return rc;
     const sdfnmpc_img_sdf_opts& src = s->img_src;
     sdfn::ScenePoseArgs spa{};
     sdfn::SceneRenderArgs sra{};
@@ -769,7 +838,7 @@ extern "C" int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnm
     SolverDevice sd(s->device);
     for (int k = 0; k < a->steps; ++k) {
         if ((k + pc->phase) % pc->every == 0) {  // pose, render into the camera buffer, sensor, encode, decode into the source, pool, pose into p
-            if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
+            if (int rc = rollout_pose(s, spa, vr)) return rc;
             // the scene's time at step k, the product rounded on its own as in sdfnmpc_solver_rollout_perceive_at
             volatile double steps_dt = (double)(pc->phase + k) * dt;
             const double t = t0 + steps_dt;
@@ -787,9 +856,9 @@ extern "C" int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnm
             if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
         if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
         if (int rc = step_enqueue(s)) return rc;
-        pa.k = k;
-        if (int rc = sdfnmpc_plant_launch_(s->ctx, &pa)) return rc;
+        if (int rc = rollout_plant(s, a, pa, vr, k)) return rc;
     }
+    if (int rc = rollout_end(s, a, vr)) return rc;
     SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
     s->pending = true;
     return SDFNMPC_OK;

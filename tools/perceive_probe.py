@@ -11,12 +11,16 @@ those motions (the host-driven loop renders at t = k * dt, the device loop runs 
 calls SensorModel.apply between the render and the encoder (same bits, checked), the distribution of the minimum
 clearance over the batch with and without the sensor model, and per launch the sensor stage's kernels next to
 scene_render and the encoder's from one timed rollout, plus the general morphology kernel with the radius-10 disc.
+--vehicle runs the device loop with and without a vehicle model of moderate size (rollout_probe.VEHICLE: two periods of
+input delay, thrust lag, rotor drag, gusts, noise on the state estimate) and prints the distribution of the minimum
+clearance of the true vehicle over the batch for both, and the rollout's ms per step.
 
 One configuration per run (give every run its own time limit):
     timeout 600 python tools/perceive_probe.py --B 1024 --N 40 --every 1
     timeout 600 python tools/perceive_probe.py --B 1024 --N 40 --every 5
     timeout 200 python tools/perceive_probe.py --B 1 --N 40 --every 1
     timeout 600 python tools/perceive_probe.py --B 256 --N 40 --every 1 --sensor
+    timeout 600 python tools/perceive_probe.py --B 256 --N 40 --every 1 --vehicle
 Prints ms per control step of both loops (best of --reps repetitions after a warm-up) and a JSON line.  Diagnostic."""
 import argparse
 import json
@@ -34,7 +38,8 @@ from sdf_nmpc_amd.config import Config
 from sdf_nmpc_amd.scene import Scene
 from sdf_nmpc_amd.sensor import SensorModel
 from sdf_nmpc_amd.vae import VaeWrapper
-from rollout_probe import controller
+from sdf_nmpc_amd.vehicle import VehicleModel
+from rollout_probe import VEHICLE, controller
 
 # vector instructions executed per ray-primitive test, from the loop body in the -save-temps assembly: 38 (box), 39
 # (sphere), 51 (cylinder); the probe's forest is one box, ten cylinders and five spheres
@@ -195,6 +200,45 @@ def sensor_probe(cfg, a, res):
     print(json.dumps(res))
 
 
+def vehicle_probe(cfg, a, res):
+    """The perceiving device loop under an imperfect vehicle and estimator, and the clearance it costs."""
+    def run(name):
+        n, x0, wps = controller(cfg, a.B, 1)
+        ctx = n.ocp.ctx
+        scene, vae = Scene(ctx, forest(16)), VaeWrapper(cfg, batch=a.B, ctx=ctx)
+        plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]))
+        m = VehicleModel(cfg, ctx, max(a.B, 1), seed=2024, **VEHICLE) if name == "vehicle" else None
+        n.set_x0(x0)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        r = n.rollout(a.K, refs="wps", wps=wps, plant=plant, scene=scene, vae=vae, perceive_every=a.every, vehicle=m)
+        ms = (time.perf_counter() - t0) / a.K * 1e3
+        if m is not None:
+            m.close()
+        vae.vae.close()
+        n.ocp.close()
+        return r, ms
+
+    run("vehicle")  # warms up (workspaces, code objects) and is not timed
+    runs = {}
+    for name in ("perfect", "vehicle"):
+        runs[name], res[f"rollout_ms_per_step_{name}"] = run(name)
+    q = (0, 5, 25, 50, 75, 95, 100)
+    for name in ("perfect", "vehicle"):
+        mc = runs[name].clearance.min(axis=1)
+        res[f"min_clearance_{name}_percentiles"] = dict(zip(map(str, q), np.percentile(mc, q).round(4).tolist()))
+        res[f"collided_{name}"] = int((mc < 0).sum())
+    err = runs["vehicle"].xhat - runs["vehicle"].x
+    res["est_pos_err_std"] = float(err[..., :3].std())
+    print(f"B={a.B} N={a.N} K={a.K} every={a.every} with the vehicle model {VEHICLE}: rollout "
+          f"{res['rollout_ms_per_step_perfect']:.3f} ms/step without it, {res['rollout_ms_per_step_vehicle']:.3f} ms/step "
+          f"with it; std of the position estimate's error {res['est_pos_err_std']:.4f} m")
+    print("min clearance of the true vehicle over the batch, percentiles", q)
+    for name in ("perfect", "vehicle"):
+        print(f"  {name:8s}", list(res[f"min_clearance_{name}_percentiles"].values()), "collided:", res[f"collided_{name}"])
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=1024)
@@ -205,12 +249,16 @@ def main():
     ap.add_argument("--moving", action="store_true", help="the loops' scene moves (moving_forest)")
     ap.add_argument("--kernels-only", action="store_true", help="only the scene kernels' own times")
     ap.add_argument("--sensor", action="store_true", help="the loops under SensorModel.reference_augment")
+    ap.add_argument("--vehicle", action="store_true", help="the device loop with and without a vehicle model")
     a = ap.parse_args()
     warnings.simplefilter("ignore")
     cfg = Config(mpc__N=a.N)
     res = {"B": a.B, "N": a.N, "K": a.K, "every": a.every, "moving": a.moving}
     if a.sensor:
         sensor_probe(cfg, a, res)
+        return
+    if a.vehicle:
+        vehicle_probe(cfg, a, res)
         return
     if a.kernels_only:
         ctx = _lib.Context(0)

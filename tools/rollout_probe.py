@@ -3,11 +3,14 @@
 configuration: as Nmpc.rollout (one launch sequence, one wait), and as the host-driven loop a user writes without
 it (set_x0 -> gen_refs_device -> solve -> plant_step -> download the state), which pays two synchronisations and
 three copies per step.  Both use the plant kernel, so the loops compute the same bits (checked) and the difference
-is the host's.  Also the plant kernel's own time (HIP events) at substeps 1 and 10.
+is the host's.  Also the plant kernel's own time (HIP events) at substeps 1 and 10.  With --vehicle: the same for
+the vehicle model's kernel ("plant_vehicle": delay, thrust lag, drag, gusts, estimate noise all on) beside "plant",
+and the rollout's ms per step with and without the model.
 
 One configuration per run (give every run its own time limit):
     timeout 300 python tools/rollout_probe.py --B 1024 --N 40      # C3
     timeout 120 python tools/rollout_probe.py --B 1 --N 40
+    timeout 300 python tools/rollout_probe.py --B 1024 --N 40 --vehicle
 Prints ms per control step of both loops (best of --reps repetitions after a warm-up) and a JSON line.  Diagnostic."""
 import argparse
 import json
@@ -24,6 +27,11 @@ from sdf_nmpc_amd import _lib
 from sdf_nmpc_amd.config import Config
 from sdf_nmpc_amd.controller import Nmpc
 from sdf_nmpc_amd.reference import yaw2quat
+from sdf_nmpc_amd.vehicle import VehicleModel
+
+# a model of moderate size with every term on: what the "plant_vehicle" figures are measured under
+VEHICLE = dict(delay=2, thrust_tau=0.05, drag=(0.3, 0.3, 0.1), gust_std=0.5, gust_tau=1.0, est_std_pos=0.03,
+               est_std_vel=0.05, est_std_yaw=0.01)
 
 
 def controller(cfg, B, seed):
@@ -61,6 +69,7 @@ def main():
     ap.add_argument("--N", type=int, default=40)
     ap.add_argument("--K", type=int, default=50)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--vehicle", action="store_true", help="also time the vehicle model's kernel and a rollout with it")
     a = ap.parse_args()
     warnings.simplefilter("ignore")
     cfg = Config(mpc__N=a.N)
@@ -107,10 +116,51 @@ def main():
         ctx.enable_timing(False)
         ctx.reset_stats()
         res[f"plant_us_substeps{sub}"] = ms / cnt * 1e3
+    if a.vehicle:
+        m = VehicleModel(cfg, ctx, B, seed=1, **VEHICLE)
+        est = _lib.DeviceArray.from_numpy(ctx, xh[:, -1])
+        m.begin(est, 0)
+        for sub in (1, 10):
+            o = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]), substeps=sub)
+            for f in range(20):
+                m.step(o, du, f, est)
+            ctx.synchronize()
+            ctx.reset_stats()
+            ctx.enable_timing(True)
+            for f in range(200):
+                m.step(o, du, 20 + f, est)
+            ms, cnt = ctx.kernel_stats("plant_vehicle")
+            ctx.enable_timing(False)
+            ctx.reset_stats()
+            res[f"plant_vehicle_us_substeps{sub}"] = ms / cnt * 1e3
+        m.close()
     n.ocp.close()
+    if a.vehicle:  # the rollout of the first part again, alternating without and with the model
+        t_off, t_on = [], []
+        for rep in range(a.reps + 1):
+            for with_model in (False, True):
+                n, x0, wps = controller(cfg, a.B, 1)
+                plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]))
+                m = VehicleModel(cfg, n.ocp.ctx, max(a.B, 1), seed=1, **VEHICLE) if with_model else None
+                n.set_x0(x0)
+                n.ocp.ctx.synchronize()
+                t0 = time.perf_counter()
+                n.rollout(a.K, refs="wps", wps=wps, plant=plant, vehicle=m)
+                t1 = time.perf_counter()
+                if rep:
+                    (t_on if with_model else t_off).append((t1 - t0) / a.K * 1e3)
+                if m is not None:
+                    m.close()
+                n.ocp.close()
+        res["rollout_ms_per_step_no_vehicle"], res["rollout_ms_per_step_vehicle"] = min(t_off), min(t_on)
     print(f"B={a.B} N={a.N} K={a.K}: rollout {res['rollout_ms_per_step']:.3f} ms/step, host-driven loop "
           f"{res['host_loop_ms_per_step']:.3f} ms/step (same bits: {res['same_bits']}); plant kernel "
           f"{res['plant_us_substeps1']:.1f} us at substeps 1, {res['plant_us_substeps10']:.1f} us at substeps 10")
+    if a.vehicle:
+        print(f"vehicle model: plant_vehicle kernel {res['plant_vehicle_us_substeps1']:.1f} us at substeps 1, "
+              f"{res['plant_vehicle_us_substeps10']:.1f} us at substeps 10; rollout "
+              f"{res['rollout_ms_per_step_no_vehicle']:.3f} ms/step without the model, "
+              f"{res['rollout_ms_per_step_vehicle']:.3f} ms/step with it")
     print(json.dumps(res))
     if res["rollout_ms_per_step"] > res["host_loop_ms_per_step"]:
         print("NOTE: the rollout was not faster than the host-driven loop in this run")
