@@ -1078,6 +1078,11 @@ def _vehicle_fields(vehicle):
     return h, int(frame0), _ptr(xhat_log), _ptr(uapp_log)
 
 
+def _sensor_args(sensor):
+    """The (sensor options, scratch) pair the sensing rollouts end with, from (SensorOptsC, scratch or None) or None."""
+    return (None, None) if sensor is None else (C.byref(sensor[0]), _ptr(sensor[1]))
+
+
 class Solver:
     """sdfnmpc_solver: B instances' SQP-RTI workspace on one context, driven with host arrays."""
 
@@ -1155,25 +1160,30 @@ class Solver:
         degradation of every new image before it is encoded (sdfnmpc_solver_rollout_perceive_sensor).  vehicle:
         (handle, frame0, xhat_log [B][K+1][10] or None, uapp_log [B][K][4] or None) -- the vehicle model whose plant
         call replaces the plant's (sdfnmpc_rollout_args.vehicle), after sdfnmpc_vehicle_begin on the x0 field."""
+        a = self._rollout_args(steps, plant, x_log, u_log, status_log, iters_log, pts_log, shift, ref, wp_p, wp_q, vw,
+                               wrow, n_wp, vehicle, perceive, sensor)
+        if sensor is not None:
+            t0, dt = (0.0, 0.0) if scene_clock is None else scene_clock
+            _check(load().sdfnmpc_solver_rollout_perceive_sensor(
+                self.h, a, None if perceive is None else C.byref(perceive), float(t0), float(dt), *_sensor_args(sensor)))
+        elif perceive is None:
+            _check(load().sdfnmpc_solver_rollout(self.h, a))
+        elif scene_clock is None:
+            _check(load().sdfnmpc_solver_rollout_perceive(self.h, a, C.byref(perceive)))
+        else:
+            _check(load().sdfnmpc_solver_rollout_perceive_at(self.h, a, C.byref(perceive),
+                                                             float(scene_clock[0]), float(scene_clock[1])))
+
+    def _rollout_args(self, steps, plant, x_log, u_log, status_log, iters_log, pts_log, shift, ref, wp_p, wp_q, vw, wrow,
+                      n_wp, vehicle, *keep):
+        """The sdfnmpc_rollout_args block every rollout method passes, by reference; it, what it names and ``keep``
+        (what the method's own arguments name) stay alive until ``wait``."""
         a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
                          _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
                          _ptr(status_log), _ptr(iters_log), _ptr(pts_log), *_vehicle_fields(vehicle))
-        self._rollout_keep = (vehicle, a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log)
-        if sensor is not None:
-            self._rollout_keep += (perceive, sensor)
-            t0, dt = (0.0, 0.0) if scene_clock is None else scene_clock
-            _check(load().sdfnmpc_solver_rollout_perceive_sensor(
-                self.h, C.byref(a), None if perceive is None else C.byref(perceive), float(t0), float(dt),
-                C.byref(sensor[0]), _ptr(sensor[1])))
-        elif perceive is None:
-            _check(load().sdfnmpc_solver_rollout(self.h, C.byref(a)))
-        elif scene_clock is None:
-            self._rollout_keep += (perceive,)
-            _check(load().sdfnmpc_solver_rollout_perceive(self.h, C.byref(a), C.byref(perceive)))
-        else:
-            self._rollout_keep += (perceive,)
-            _check(load().sdfnmpc_solver_rollout_perceive_at(self.h, C.byref(a), C.byref(perceive),
-                                                             float(scene_clock[0]), float(scene_clock[1])))
+        self._rollout_keep = (vehicle, a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log,
+                              pts_log) + keep
+        return C.byref(a)
 
     def set_sdf_scene(self, scene_h, scene_of=None, max_df: float = 1.0, predict: bool = False):
         """sdfnmpc_solver_set_sdf_scene: the scene's exact distance instead of the network from the next step on;
@@ -1191,11 +1201,9 @@ class Solver:
         """Enqueue sdfnmpc_solver_rollout_scene_sdf: `rollout` for a solver with a scene source -- before step k the
         scene time t0 + (phase + k) dt, and with pose (a PoseRefreshArgsC) the camera pose of p refreshed from the
         plant state before every `every`-th step."""
-        a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
-                         _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
-                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log), *_vehicle_fields(vehicle))
-        self._rollout_keep = (vehicle, a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, pose)
-        _check(load().sdfnmpc_solver_rollout_scene_sdf(self.h, C.byref(a), None if pose is None else C.byref(pose),
+        a = self._rollout_args(steps, plant, x_log, u_log, status_log, iters_log, pts_log, shift, ref, wp_p, wp_q, vw,
+                               wrow, n_wp, vehicle, pose)
+        _check(load().sdfnmpc_solver_rollout_scene_sdf(self.h, a, None if pose is None else C.byref(pose),
                                                        int(phase), float(t0), float(dt)))
 
     def set_sdf_image(self, opts: "ImgSdfOptsC" = None, keep=()):
@@ -1214,19 +1222,13 @@ class Solver:
         ((SensorOptsC, scratch), normalised units), pooled in unsigned mode, and the camera pose of p refreshed, before
         every `every`-th step.  dec: a VaeDec -- sdfnmpc_solver_rollout_image_recon: the image is rendered into
         the camera buffer perceive names, encoded by perceive's encoder, and its reconstruction goes into the source."""
-        a = RolloutArgsC(int(steps), int(shift), None if ref is None else C.pointer(ref), _ptr(wp_p), _ptr(wp_q),
-                         _ptr(vw), _ptr(wrow), int(n_wp), plant.c(self.ctx, self.B), _ptr(x_log), _ptr(u_log),
-                         _ptr(status_log), _ptr(iters_log), _ptr(pts_log), *_vehicle_fields(vehicle))
-        self._rollout_keep = (vehicle, a, ref, plant, wp_p, wp_q, vw, wrow, x_log, u_log, status_log, iters_log, pts_log, perceive,
-                              sensor, dec)
+        a = self._rollout_args(steps, plant, x_log, u_log, status_log, iters_log, pts_log, shift, ref, wp_p, wp_q, vw,
+                               wrow, n_wp, vehicle, perceive, sensor, dec)
+        args = (self.h, a, None if perceive is None else C.byref(perceive), float(t0), float(dt), *_sensor_args(sensor))
         if dec is not None:
-            _check(load().sdfnmpc_solver_rollout_image_recon(
-                self.h, C.byref(a), None if perceive is None else C.byref(perceive), float(t0), float(dt),
-                None if sensor is None else C.byref(sensor[0]), None if sensor is None else _ptr(sensor[1]), dec.h))
-            return
-        _check(load().sdfnmpc_solver_rollout_image_sdf(
-            self.h, C.byref(a), None if perceive is None else C.byref(perceive), float(t0), float(dt),
-            None if sensor is None else C.byref(sensor[0]), None if sensor is None else _ptr(sensor[1])))
+            _check(load().sdfnmpc_solver_rollout_image_recon(*args, dec.h))
+        else:
+            _check(load().sdfnmpc_solver_rollout_image_sdf(*args))
 
     def wait(self):
         _check(load().sdfnmpc_solver_wait(self.h, self.u0.ctypes.data, self.status.ctypes.data, self.iters.ctypes.data))

@@ -406,50 +406,46 @@ class Nmpc:
                 raise ValueError(f"rollout(): the VehicleModel has {vehicle.B} instances, the batch has {Bn}")
             if int(perceive_phase) < 0:
                 raise ValueError(f"perceive_phase {perceive_phase}: the vehicle's first frame, at least 0")
+        # every refusal before anything is uploaded or enqueued: what the SDF source admits, then what perception needs
         src = self._sdf_scene
-        if src is not None:  # a scene source: the exact distance, no perception (every refusal before any upload)
+        isrc = self._sdf_image if src is None else None
+        if src is not None:  # a scene source: the exact distance, no perception
             if scene is not None or vae is not None or sensor is not None:
                 raise ValueError("rollout(): scene, vae and sensor exclude a scene source (set_sdf_scene): the "
                                  "controller reads the scene's exact distance, not an image")
-            _check_schedule(perceive_every, perceive_phase, scene_t0, scene_dt)
-        elif self._sdf_image is not None:  # an image source: re-imaged from ``scene`` inside the loop, no encoder
-            isrc = self._sdf_image
+        elif isrc is not None:  # an image source: re-imaged from ``scene`` inside the loop, no encoder
             if vae is not None:
                 raise ValueError("rollout(): vae excludes an image source (set_sdf_image): the controller reads the "
                                  "image's own distance field, not a latent")
             if img_shape is not None and tuple(int(v) for v in img_shape) != isrc["shape"][1:]:
                 raise ValueError(f"rollout(): img_shape {tuple(img_shape)} is not the image source's {isrc['shape'][1:]}")
-            if scene is None:
-                if sensor is not None:
-                    raise ValueError("rollout(): sensor degrades a scene's images; give scene too")
-            else:
-                if imgs is not None:
-                    raise ValueError("rollout(): scene and imgs exclude each other (the image changes inside the loop)")
-                if scene.ctx is not ctx:
-                    raise ValueError("rollout(): the scene must be built on the controller's context (ctx=nmpc.ocp.ctx)")
-                if isrc["img_of"] is not None:
-                    raise ValueError("rollout(): re-imaging renders one image per instance; the source maps instances to "
-                                     "images (img_of)")
-                _check_schedule(perceive_every, perceive_phase, scene_t0, scene_dt)
-                scene._batch(Bn)
-                if sensor is not None and sensor.ctx is not ctx:
-                    raise ValueError("rollout(): the SensorModel must be built on the controller's context (ctx=nmpc.ocp.ctx)")
+            if scene is None and sensor is not None:
+                raise ValueError("rollout(): sensor degrades a scene's images; give scene too")
         elif scene is None:
             if vae is not None:
                 raise ValueError("rollout(): vae is the encoder of a scene's images; give scene too")
             if sensor is not None:
                 raise ValueError("rollout(): sensor degrades a scene's images; give scene (and vae) too")
-        else:  # every refusal before anything is uploaded or enqueued
-            if vae is None:
-                raise ValueError("rollout(): scene needs vae (a VaeWrapper on the controller's context)")
+        elif vae is None:
+            raise ValueError("rollout(): scene needs vae (a VaeWrapper on the controller's context)")
+        if scene is not None:  # perception inside the loop, into the latent (vae) or into the image source
             if imgs is not None:
                 raise ValueError("rollout(): scene and imgs exclude each other (the image changes inside the loop)")
-            if vae.ctx is not ctx or scene.ctx is not ctx:
-                raise ValueError("rollout(): the scene and the VaeWrapper must be built on the controller's context "
-                                 "(ctx=nmpc.ocp.ctx)")
-            if vae.B != Bn:
-                raise ValueError(f"rollout(): the VaeWrapper encodes {vae.B} images, the batch has {Bn}")
+            if vae is not None:
+                if vae.ctx is not ctx or scene.ctx is not ctx:
+                    raise ValueError("rollout(): the scene and the VaeWrapper must be built on the controller's context "
+                                     "(ctx=nmpc.ocp.ctx)")
+                if vae.B != Bn:
+                    raise ValueError(f"rollout(): the VaeWrapper encodes {vae.B} images, the batch has {Bn}")
+            else:
+                if scene.ctx is not ctx:
+                    raise ValueError("rollout(): the scene must be built on the controller's context (ctx=nmpc.ocp.ctx)")
+                if isrc["img_of"] is not None:
+                    raise ValueError("rollout(): re-imaging renders one image per instance; the source maps instances to "
+                                     "images (img_of)")
+        if scene is not None or src is not None:
             _check_schedule(perceive_every, perceive_phase, scene_t0, scene_dt)
+        if scene is not None:
             scene._batch(Bn)
             if sensor is not None and sensor.ctx is not ctx:
                 raise ValueError("rollout(): the SensorModel must be built on the controller's context (ctx=nmpc.ocp.ctx)")
@@ -470,41 +466,20 @@ class Nmpc:
                 kw["vw"] = self._dev(np.reshape(np.asarray(vw, float), (Bn, 4)))
         if plant is None:
             plant = _lib.plant_opts(self.cfg, dt=float(self.ocp.dt[0]))
-        perc = None
-        isrc = self._sdf_image if src is None else None
-        if isrc is not None:
-            if scene is not None:  # pose, render (normalised, into the source), sensor, pool, pose columns: no encoder
-                ih, iw = isrc["shape"][1:]
-                ws = _pose_workspaces(ctx, Bn)
-                rv = isrc.get("recon")
-                if rv is None:
-                    perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(self.cfg), ih, iw,
-                                              scene.scale(self.cfg, normalized=True), *_extrinsics(self.cfg), None,
-                                              _lib.VaeOptsC(), int(perceive_every), int(perceive_phase), None, None, None,
-                                              *[ws[k].data_ptr() for k in POSE_WS])
-                else:  # through the VAE: rendered into the camera buffer, encoded, the reconstruction into the source
-                    vo = _lib.VaeOptsC(Bn, ih, iw, 0, 1.0, _lib._ptr(rv.yz) if rv.depth2range else None)
-                    perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(self.cfg), ih, iw,
-                                              scene.scale(self.cfg, normalized=True), *_extrinsics(self.cfg), rv.vae.h,
-                                              vo, int(perceive_every), int(perceive_phase), isrc["camera"].data_ptr(),
-                                              rv.latent.data_ptr(), rv.latent64.data_ptr(),
-                                              *[ws[k].data_ptr() for k in POSE_WS])
-                perc._keep = ws
-                t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)
-        elif scene is not None:
-            ih, iw = (int(v) for v in (img_shape if img_shape is not None else self.cfg.sensor.shape_imgs[-2:]))
-            ws = dict(_pose_workspaces(ctx, Bn), images=_lib.DeviceArray(ctx, (Bn, ih, iw), np.float32))
-            vo = _lib.VaeOptsC(Bn, ih, iw, 0, float(vae.opts.clip), _lib._ptr(vae.yz) if vae.depth2range else None)
-            perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(self.cfg), ih, iw,
-                                      scene.scale(self.cfg, normalized=False), *_extrinsics(self.cfg),
-                                      vae.vae.h, vo, int(perceive_every), int(perceive_phase), ws["images"].data_ptr(), vae.latent.data_ptr(),
-                                      vae.latent64.data_ptr(), *[ws[k].data_ptr() for k in POSE_WS])
-            kw["perceive"] = perc
-            if sensor is not None:  # in the units of the raw image the renderer writes for the encoder
-                kw["sensor"] = sensor.opts(Bn, ih, iw, normalized=False)
-            t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)
-            if scene.is_dynamic:  # a static scene has no use for the clock: the call the method has always made
-                kw["scene_clock"] = (t0, dts)
+        t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)  # step k is at t0 + (phase + k) dts
+        perc = rv = sn = None
+        if scene is not None:  # pose, render, sensor, then into the latent, or (normalised) into the image source
+            ws = _pose_workspaces(ctx, Bn)
+            if isrc is None:  # a raw sensor image for ``vae``
+                shape = tuple(int(v) for v in (img_shape if img_shape is not None else self.cfg.sensor.shape_imgs[-2:]))
+                ws["images"] = _lib.DeviceArray(ctx, (Bn,) + shape, np.float32)
+                enc = (vae, float(vae.opts.clip), ws["images"])
+            else:  # into the source itself; with ``reconstruct=`` into its camera buffer, encoded, and decoded into it
+                shape, rv = isrc["shape"][1:], isrc.get("recon")
+                enc = None if rv is None else (rv, 1.0, isrc["camera"])
+            perc = _perceive_args(self.cfg, scene, Bn, shape, isrc is not None, perceive_every, perceive_phase, ws, enc)
+            if sensor is not None:  # in the units of the image the renderer writes
+                sn = sensor.opts(Bn, *shape, normalized=isrc is not None)
         dimg = None
         if imgs is not None:
             dimg, ishape = self._dev_imgs(imgs)
@@ -524,20 +499,18 @@ class Nmpc:
         if src is not None:  # the pose the FOV rows read is refreshed from the plant state, the scene's clock per step
             ws = _pose_workspaces(ctx, Bn)
             pose = _lib.PoseRefreshArgsC(int(perceive_every), *_extrinsics(self.cfg), *[ws[k].data_ptr() for k in POSE_WS])
-            t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)
             solver.rollout_scene_sdf(K, plant, pose=pose, phase=int(perceive_phase), t0=t0, dt=dts,
                                      shift=int(self.cfg.mpc.shift), **kw, **log)
             self._clean("pose")  # written on the device, as after set_pose_device
         elif isrc is not None:
-            sn = None if sensor is None else sensor.opts(Bn, ih, iw, normalized=True)  # the source's images are normalised
             clock = (t0, dts) if perc is not None else (0.0, 0.0)
-            dec = isrc["recon"].dec if perc is not None and isrc.get("recon") is not None else None
-            solver.rollout_image_sdf(K, plant, perceive=perc, t0=clock[0], dt=clock[1], sensor=sn, dec=dec,
-                                     shift=int(self.cfg.mpc.shift), **kw, **log)
+            solver.rollout_image_sdf(K, plant, perceive=perc, t0=clock[0], dt=clock[1], sensor=sn,
+                                     dec=None if rv is None else rv.dec, shift=int(self.cfg.mpc.shift), **kw, **log)
             if perc is not None:
                 self._clean("pose")
-        else:
-            solver.rollout(K, plant, shift=int(self.cfg.mpc.shift), **kw, **log)
+        else:  # a static scene has no use for the clock: the call the method has always made
+            solver.rollout(K, plant, perceive=perc, sensor=sn, shift=int(self.cfg.mpc.shift),
+                           scene_clock=(t0, dts) if perc is not None and scene.is_dynamic else None, **kw, **log)
         u0 = solver.wait().copy()
         out = Rollout(log["x_log"].numpy(), log["u_log"].numpy(), log["status_log"].numpy(), log["iters_log"].numpy())
         if vehicle is not None:
@@ -824,6 +797,24 @@ def _check_schedule(perceive_every, perceive_phase, scene_t0, scene_dt):
 def _pose_workspaces(ctx, Bn):
     from . import _lib
     return {k: _lib.DeviceArray(ctx, (Bn, 3 if "_p_" in k else 9)) for k in POSE_WS}
+
+
+def _perceive_args(cfg, scene, Bn, shape, normalized, every, phase, ws, enc=None):
+    """The sdfnmpc_perceive_args of ``rollout``: ``scene`` rendered as ``shape`` images (normalized: in units of
+    sensor.dmax, else raw) on the schedule, the pose into ``ws``.  enc: (VaeWrapper, clip, camera buffer) -- the image
+    goes into that buffer and through the wrapper's encoder; None: no encoder (the solver's image source is rendered
+    into).  The result keeps ``ws`` alive."""
+    from . import _lib
+    stage = (None, _lib.VaeOptsC(), None, None, None)
+    if enc is not None:
+        v, clip, cam = enc
+        vo = _lib.VaeOptsC(Bn, *shape, 0, clip, _lib._ptr(v.yz) if v.depth2range else None)
+        stage = (v.vae.h, vo, cam.data_ptr(), v.latent.data_ptr(), v.latent64.data_ptr())
+    perc = _lib.PerceiveArgsC(scene.h, _lib._ptr(scene._scene_of), scene.img_opts(cfg), *shape,
+                              scene.scale(cfg, normalized=normalized), *_extrinsics(cfg), *stage[:2], int(every),
+                              int(phase), *stage[2:], *[ws[k].data_ptr() for k in POSE_WS])
+    perc._keep = ws
+    return perc
 
 
 def _extrinsics(cfg):

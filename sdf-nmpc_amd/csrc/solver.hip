@@ -423,10 +423,67 @@ struct VehicleRun {
     double *x_true = nullptr, *scratch = nullptr;
 };
 
-// what every rollout refuses before its first launch: the step count and logs, the plant's options (pa is filled),
-// then what sdfnmpc_pack_refs would refuse (ra is filled when args->ref is set)
-static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, sdfn::PlantArgs& pa, sdfnmpc_ref_args& ra,
-                        VehicleRun& vr) {
+// What a rollout does around the bare step [ref pack, shift, step, plant], as data: every flavour of rollout fills one
+// plan and rollout_run is the only loop.  Before step k with (k + phase) % every == 0 the stages that are switched on
+// run in the order they are declared in, the pack always last:
+//   flavour (entry point)             scene clock  pose     render into    sensor  encode  decode  pool      pack
+//   plain (perc == NULL)              -            -        -              -       -       -       -         -
+//   latent (_perceive_sensor)         -            vehicle  camera buffer  if set  yes     -       -         mode -1
+//   scene source (_scene_sdf)         every step   x0       -              -       -       -       -         mode -2
+//   image source (_image_sdf)         -            vehicle  the source     if set  -       -       unsigned  mode -2
+//   reconstruction (_image_recon)     -            vehicle  camera buffer  if set  yes     source  unsigned  mode -2
+struct RolloutPlan {
+    // every step (rollout_args): the plant's block, the reference pack when args->ref is set, the vehicle
+    sdfn::PlantArgs pa{};
+    sdfnmpc_ref_args ra{};
+    VehicleRun vr{};
+    // schedule and clock: step k happens at t = t0 + (phase + k) dt; every == 0: no stage ever runs
+    int every = 0, phase = 0;
+    double t0 = 0.0, dt = 0.0;
+    bool scene_clock = false;  // the solver's own scene time (sdf_src.t0) is set to t before every step, and stays
+    // pose: one launch from x0 (the estimate, also under a vehicle), or rollout_pose (camera from the true state)
+    enum { POSE_NONE, POSE_X0, POSE_VEHICLE } pose = POSE_NONE;
+    sdfn::ScenePoseArgs spa{};
+    // render at t into sra's image, when scene is set
+    const sdfnmpc_scene* scene = nullptr;
+    sdfn::SceneRenderArgs sra{};
+    // sensor on that image as frame phase + k, when sensor is set
+    const sdfnmpc_sensor_opts* sensor = nullptr;
+    sdfn::SensorArgs sna{};
+    sdfn::OutlierArgs ora{};
+    // encode cam into latent / latent64, when vae is set
+    sdfnmpc_vae* vae = nullptr;
+    sdfnmpc_vae_opts vo{};
+    const float* cam = nullptr;
+    float* latent = nullptr;
+    double* latent64 = nullptr;
+    // decode latent into the image source's images when dec is set; min-pool the source when pool is
+    sdfnmpc_vae_dec* dec = nullptr;
+    const sdfnmpc_img_sdf_opts* src = nullptr;
+    bool pool = false;
+    // pack the pose (mode -2), or the latent and the pose (mode -1), into p
+    sdfnmpc_ref_opts po{};
+    sdfnmpc_ref_args pra{};
+};
+
+static int rollout_clock(double t0, double dt) {
+    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
+    return SDFNMPC_OK;
+}
+
+static int rollout_schedule(int every, int phase) {
+    if (every < 1 || phase < 0)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
+    return SDFNMPC_OK;
+}
+
+// what every rollout refuses before its first launch: the step count and logs, the plant's options (pl.pa is filled),
+// then what sdfnmpc_pack_refs would refuse (pl.ra is filled when args->ref is set)
+static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, RolloutPlan& pl) {
+    sdfn::PlantArgs& pa = pl.pa;
+    sdfnmpc_ref_args& ra = pl.ra;
+    VehicleRun& vr = pl.vr;
     if (a->steps < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
     if (!a->x_log || !a->u_log) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: x_log and u_log are required");
     if (int rc = sdfnmpc_plant_args_(&a->plant, s->B, s->x0, s->u0, s->x0, &pa)) return rc;
@@ -492,6 +549,89 @@ static int rollout_end(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, const V
     return SDFNMPC_OK;
 }
 
+// the pack stage: the extrinsics into the options, and what sdfnmpc_pack_refs (mode -1 / -2) needs of the solver
+static void rollout_pack(const sdfnmpc_solver* s, int mode, const double* B_p_C, const double* B_R_C, const double* W_p_Bo,
+                         const double* W_R_Bo, RolloutPlan& pl) {
+    pl.po.mode = mode;
+    for (int i = 0; i < 3; ++i) pl.po.B_p_C[i] = B_p_C[i];
+    for (int i = 0; i < 9; ++i) pl.po.B_R_C[i] = B_R_C[i];
+    sdfnmpc_ref_args& pra = pl.pra;
+    pra.B = s->B; pra.N = s->N; pra.np = s->np; pra.ny = s->ny; pra.nyN = s->nyN;
+    pra.W_p_Bo = W_p_Bo; pra.W_R_Bo = W_R_Bo; pra.p = s->p;
+}
+
+// the stages every perceiving flavour has: perc's schedule, the vehicle's pose pair, the render into img, the pack
+static int rollout_camera(sdfnmpc_solver* s, const sdfnmpc_perceive_args* pc, float* img, int mode, RolloutPlan& pl) {
+    if (int rc = sdfnmpc_scene_pose_args_(pc->B_p_C, pc->B_R_C, s->B, s->x0, pc->W_p_Bo, pc->W_R_Bo, pc->W_p_C, pc->W_R_C,
+                                          &pl.spa))
+        return rc;
+    if (int rc = sdfnmpc_scene_render_args_(s->ctx, pc->scene, pc->scene_of, &pc->img, pc->h, pc->w, pc->scale, s->B,
+                                            pc->W_p_C, pc->W_R_C, img, &pl.sra))
+        return rc;
+    pl.every = pc->every; pl.phase = pc->phase;
+    pl.pose = RolloutPlan::POSE_VEHICLE;
+    pl.scene = pc->scene;
+    rollout_pack(s, mode, pc->B_p_C, pc->B_R_C, pc->W_p_Bo, pc->W_R_Bo, pl);
+    return SDFNMPC_OK;
+}
+
+// the sensor stage on img [B][h][w]: frame = phase + k must not overflow
+static int rollout_sensor(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, const sdfnmpc_sensor_opts* sensor, float* img,
+                          int h, int w, float* scratch, RolloutPlan& pl) {
+    if ((long long)pl.phase + a->steps > 2147483647LL)
+        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the sensor's frame counter (phase + steps) overflows");
+    pl.sensor = sensor;
+    return sdfnmpc_sensor_args_(sensor, img, s->B, h, w, scratch, &pl.sna, &pl.ora);
+}
+
+// The one rollout loop: nothing in here refuses, the plan has been checked.  Per step [pose, render, sensor, encode,
+// decode, pool, pack] when the schedule says so, then ref pack, shift, step, plant; a plain launch sequence.
+static int rollout_run(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, RolloutPlan& pl) {
+    sdfn::PlantArgs& pa = pl.pa;
+    pa.K = a->steps;
+    pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
+    pa.pts_log = a->pts_log;
+    pa.status = s->status; pa.iters = s->iters;
+    pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
+    SolverDevice sd(s->device);
+    for (int k = 0; k < a->steps; ++k) {
+        // the time of step k, t0 + (phase + k) dt: the product is rounded on its own (a volatile temporary keeps the
+        // compiler from contracting it into a fused multiply-add), as a host loop forms it
+        volatile double steps_dt = (double)(pl.phase + k) * pl.dt;
+        const double t = pl.t0 + steps_dt;
+        if (pl.scene_clock) s->sdf_src.t0 = t;
+        if (pl.every > 0 && (k + pl.phase) % pl.every == 0) {  // a new view from the current state
+            if (pl.pose == RolloutPlan::POSE_X0)
+                if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &pl.spa)) return rc;
+            if (pl.pose == RolloutPlan::POSE_VEHICLE)
+                if (int rc = rollout_pose(s, pl.spa, pl.vr)) return rc;
+            if (pl.scene)
+                if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pl.scene, &pl.sra, t)) return rc;
+            if (pl.sensor)  // what the camera makes of the exact image: frame = phase + k, as a chunked or host loop counts
+                if (int rc = sdfnmpc_sensor_launch_(s->ctx, &pl.sna, &pl.ora, pl.sensor->outlier_rm != 0, pl.phase + k))
+                    return rc;
+            if (pl.vae)
+                if (int rc = sdfnmpc_vae_encode(s->ctx, pl.vae, &pl.vo, pl.cam, pl.latent, pl.latent64)) return rc;
+            if (pl.dec)
+                if (int rc = sdfnmpc_vae_decode(s->ctx, pl.dec, s->B, pl.latent, pl.src->H, pl.src->W,
+                                                const_cast<float*>(pl.src->images), nullptr))
+                    return rc;
+            if (pl.pool)
+                if (int rc = sdfnmpc_img_sdf_pool(s->ctx, pl.src, s->B)) return rc;
+            if (int rc = sdfnmpc_pack_refs(s->ctx, &pl.po, &pl.pra)) return rc;
+        }
+        if (a->ref)
+            if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &pl.ra)) return rc;
+        if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
+        if (int rc = step_enqueue(s)) return rc;
+        if (int rc = rollout_plant(s, a, pa, pl.vr, k)) return rc;
+    }
+    if (int rc = rollout_end(s, a, pl.vr)) return rc;
+    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
+    s->pending = true;
+    return SDFNMPC_OK;
+}
+
 extern "C" int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a) {
     return sdfnmpc_solver_rollout_perceive(s, a, nullptr);
 }
@@ -511,23 +651,12 @@ extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const s
                                                       const sdfnmpc_sensor_opts* sensor, float* scratch) {
     if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout");
     if (sensor && !pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: a sensor model needs perception (perc)");
-    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
-    sdfn::PlantArgs pa{};
-    sdfnmpc_ref_args ra{};
-    VehicleRun vr{};
-    if (int rc = rollout_args(s, a, pa, ra, vr)) return rc;
-    // perception: the pose and render blocks, and what sdfnmpc_vae_encode / sdfnmpc_pack_refs (mode -1) would refuse
-    sdfn::ScenePoseArgs spa{};
-    sdfn::SceneRenderArgs sra{};
-    sdfnmpc_vae_opts vo{};
-    sdfnmpc_ref_opts lo{};
-    sdfnmpc_ref_args lra{};
-    sdfn::SensorArgs sna{};
-    sdfn::OutlierArgs ora{};
-    if (pc) {
-        if (pc->every < 1 || pc->phase < 0)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
+    if (int rc = rollout_clock(t0, dt)) return rc;
+    RolloutPlan pl;
+    pl.t0 = t0; pl.dt = dt;
+    if (int rc = rollout_args(s, a, pl)) return rc;
+    if (pc) {  // what sdfnmpc_vae_encode / sdfnmpc_pack_refs (mode -1) would refuse; the image goes into the camera buffer
+        if (int rc = rollout_schedule(pc->every, pc->phase)) return rc;
         if (!pc->scene || !pc->vae) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perception needs a scene and an encoder");
         if (!sdfnmpc_scene_on_ctx_(pc->scene, s->ctx) || !sdfnmpc_vae_on_ctx_(pc->vae, s->ctx))
             return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene and the encoder must live on the solver's context");
@@ -537,54 +666,15 @@ extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const s
         if (L < 1 || 17 + L > s->np)
             return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the encoder's latent does not fit the parameter row");
         if (!(pc->vae_opts.clip > 0.f)) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: vae_opts.clip must be > 0");
-        if (int rc = sdfnmpc_scene_pose_args_(pc->B_p_C, pc->B_R_C, s->B, s->x0, pc->W_p_Bo, pc->W_R_Bo, pc->W_p_C,
-                                              pc->W_R_C, &spa))
-            return rc;
-        if (int rc = sdfnmpc_scene_render_args_(s->ctx, pc->scene, pc->scene_of, &pc->img, pc->h, pc->w, pc->scale, s->B,
-                                                pc->W_p_C, pc->W_R_C, pc->images, &sra))
-            return rc;
-        vo = pc->vae_opts;
-        vo.B = s->B; vo.in_h = pc->h; vo.in_w = pc->w; vo.dtype = 0;
-        lo.mode = -1;
-        for (int i = 0; i < 3; ++i) lo.B_p_C[i] = pc->B_p_C[i];
-        for (int i = 0; i < 9; ++i) lo.B_R_C[i] = pc->B_R_C[i];
-        lra.B = s->B; lra.N = s->N; lra.np = s->np; lra.ny = s->ny; lra.L = L; lra.nyN = s->nyN;
-        lra.latent = pc->latent64; lra.W_p_Bo = pc->W_p_Bo; lra.W_R_Bo = pc->W_R_Bo; lra.p = s->p;
-        if (sensor) {
-            if ((long long)pc->phase + a->steps > 2147483647LL)
-                return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the sensor's frame counter (phase + steps) overflows");
-            if (int rc = sdfnmpc_sensor_args_(sensor, pc->images, s->B, pc->h, pc->w, scratch, &sna, &ora)) return rc;
-        }
+        if (int rc = rollout_camera(s, pc, pc->images, -1, pl)) return rc;
+        pl.pra.L = L; pl.pra.latent = pc->latent64;
+        pl.vae = pc->vae; pl.cam = pc->images; pl.latent = pc->latent; pl.latent64 = pc->latent64;
+        pl.vo = pc->vae_opts;
+        pl.vo.B = s->B; pl.vo.in_h = pc->h; pl.vo.in_w = pc->w; pl.vo.dtype = 0;
+        if (sensor)
+            if (int rc = rollout_sensor(s, a, sensor, pc->images, pc->h, pc->w, scratch, pl)) return rc;
     }
-    pa.K = a->steps;
-    pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
-    pa.pts_log = a->pts_log;
-    pa.status = s->status; pa.iters = s->iters;
-    pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
-    SolverDevice sd(s->device);
-    for (int k = 0; k < a->steps; ++k) {
-        if (pc && (k + pc->phase) % pc->every == 0) {  // a new image from the current state: pose, render, encode, set_latent
-            if (int rc = rollout_pose(s, spa, vr)) return rc;
-            // the scene's time at step k, t0 + (phase + k) dt: the product is rounded on its own (a volatile
-            // temporary keeps the compiler from contracting it into a fused multiply-add), as a host loop forms it
-            volatile double steps_dt = (double)(pc->phase + k) * dt;
-            const double t = t0 + steps_dt;
-            if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pc->scene, &sra, t)) return rc;
-            if (sensor)  // what the camera makes of the exact image: frame = phase + k, as a chunked or host loop counts
-                if (int rc = sdfnmpc_sensor_launch_(s->ctx, &sna, &ora, sensor->outlier_rm != 0, pc->phase + k)) return rc;
-            if (int rc = sdfnmpc_vae_encode(s->ctx, pc->vae, &vo, pc->images, pc->latent, pc->latent64)) return rc;
-            if (int rc = sdfnmpc_pack_refs(s->ctx, &lo, &lra)) return rc;
-        }
-        if (a->ref)
-            if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
-        if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
-        if (int rc = step_enqueue(s)) return rc;
-        if (int rc = rollout_plant(s, a, pa, vr, k)) return rc;
-    }
-    if (int rc = rollout_end(s, a, vr)) return rc;
-    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
-    s->pending = true;
-    return SDFNMPC_OK;
+    return rollout_run(s, a, pl);
 }
 
 extern "C" int sdfnmpc_solver_set_sdf_scene(sdfnmpc_solver* s, const sdfnmpc_scene* scene, const int* scene_of,
@@ -642,54 +732,24 @@ extern "C" int sdfnmpc_solver_rollout_scene_sdf(sdfnmpc_solver* s, const sdfnmpc
     if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_scene_sdf");
     if (!s->sdf_src.scene)
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: no scene source set (sdfnmpc_solver_set_sdf_scene)");
-    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
+    if (int rc = rollout_clock(t0, dt)) return rc;
     if (phase < 0) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: phase must be >= 0");
-    sdfn::PlantArgs pa{};
-    sdfnmpc_ref_args ra{};
-    VehicleRun vr{};
-    if (int rc = rollout_args(s, a, pa, ra, vr)) return rc;
-    // the pose refresh: the pose block, and what sdfnmpc_pack_refs (mode -2) would refuse
-    sdfn::ScenePoseArgs spa{};
-    sdfnmpc_ref_opts po{};
-    sdfnmpc_ref_args pra{};
-    if (pose) {
+    RolloutPlan pl;
+    pl.t0 = t0; pl.dt = dt; pl.phase = phase;
+    pl.scene_clock = true;  // from the first step on, so after the last refusal
+    if (int rc = rollout_args(s, a, pl)) return rc;
+    if (pose) {  // the camera pose the FOV rows read, from x0: the pose block, and what sdfnmpc_pack_refs (mode -2) would refuse
         if (pose->every < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: pose->every must be >= 1");
         if (!pose->W_p_Bo || !pose->W_R_Bo || !pose->W_p_C || !pose->W_R_C)
             return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: the pose refresh needs its workspaces");
         if (int rc = sdfnmpc_scene_pose_args_(pose->B_p_C, pose->B_R_C, s->B, s->x0, pose->W_p_Bo, pose->W_R_Bo,
-                                              pose->W_p_C, pose->W_R_C, &spa))
+                                              pose->W_p_C, pose->W_R_C, &pl.spa))
             return rc;
-        po.mode = -2;
-        for (int i = 0; i < 3; ++i) po.B_p_C[i] = pose->B_p_C[i];
-        for (int i = 0; i < 9; ++i) po.B_R_C[i] = pose->B_R_C[i];
-        pra.B = s->B; pra.N = s->N; pra.np = s->np; pra.ny = s->ny; pra.nyN = s->nyN;
-        pra.W_p_Bo = pose->W_p_Bo; pra.W_R_Bo = pose->W_R_Bo; pra.p = s->p;
+        pl.every = pose->every;
+        pl.pose = RolloutPlan::POSE_X0;
+        rollout_pack(s, -2, pose->B_p_C, pose->B_R_C, pose->W_p_Bo, pose->W_R_Bo, pl);
     }
-    pa.K = a->steps;
-    pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
-    pa.pts_log = a->pts_log;
-    pa.status = s->status; pa.iters = s->iters;
-    pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
-    SolverDevice sd(s->device);
-    for (int k = 0; k < a->steps; ++k) {
-        // the scene's time at step k, the product rounded on its own as in sdfnmpc_solver_rollout_perceive_at
-        volatile double steps_dt = (double)(phase + k) * dt;
-        s->sdf_src.t0 = t0 + steps_dt;
-        if (pose && (k + phase) % pose->every == 0) {  // the camera pose the FOV rows read, from the current state
-            if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &spa)) return rc;
-            if (int rc = sdfnmpc_pack_refs(s->ctx, &po, &pra)) return rc;
-        }
-        if (a->ref)
-            if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
-        if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
-        if (int rc = step_enqueue(s)) return rc;
-        if (int rc = rollout_plant(s, a, pa, vr, k)) return rc;
-    }
-    if (int rc = rollout_end(s, a, vr)) return rc;
-    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
-    s->pending = true;
-    return SDFNMPC_OK;
+    return rollout_run(s, a, pl);
 }
 
 extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
@@ -699,23 +759,13 @@ extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc
     if (!s->has_img)
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: no image source set (sdfnmpc_solver_set_sdf_image)");
     if (sensor && !pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: a sensor model needs perception (perc)");
-    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
-    sdfn::PlantArgs pa{};
-    sdfnmpc_ref_args ra{};
-    VehicleRun vr{};
-    if (int rc = rollout_args(s, a, pa, ra, vr)) return rc;
-    // re-imaging: the pose and render blocks, the sensor's, and what sdfnmpc_pack_refs (mode -2) would refuse
+    if (int rc = rollout_clock(t0, dt)) return rc;
+    RolloutPlan pl;
+    pl.t0 = t0; pl.dt = dt;
+    if (int rc = rollout_args(s, a, pl)) return rc;
     const sdfnmpc_img_sdf_opts& src = s->img_src;
-    sdfn::ScenePoseArgs spa{};
-    sdfn::SceneRenderArgs sra{};
-    sdfnmpc_ref_opts po{};
-    sdfnmpc_ref_args pra{};
-    sdfn::SensorArgs sna{};
-    sdfn::OutlierArgs ora{};
-    if (pc) {
-        if (pc->every < 1 || pc->phase < 0)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
+    if (pc) {  // re-imaging: rendered into the source itself; NULL keeps the image and the pose as set
+        if (int rc = rollout_schedule(pc->every, pc->phase)) return rc;
         if (!pc->scene || !sdfnmpc_scene_on_ctx_(pc->scene, s->ctx))
             return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging needs a scene on the solver's context");
         if (pc->h != src.H || pc->w != src.W)
@@ -724,53 +774,13 @@ extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc
             return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging renders one image per instance (img_of must be NULL)");
         if (!pc->W_p_Bo || !pc->W_R_Bo || !pc->W_p_C || !pc->W_R_C)
             return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging needs the pose workspaces");
-        if (int rc = sdfnmpc_scene_pose_args_(pc->B_p_C, pc->B_R_C, s->B, s->x0, pc->W_p_Bo, pc->W_R_Bo, pc->W_p_C,
-                                              pc->W_R_C, &spa))
-            return rc;
-        if (int rc = sdfnmpc_scene_render_args_(s->ctx, pc->scene, pc->scene_of, &pc->img, pc->h, pc->w, pc->scale, s->B,
-                                                pc->W_p_C, pc->W_R_C, const_cast<float*>(src.images), &sra))
-            return rc;
-        po.mode = -2;
-        for (int i = 0; i < 3; ++i) po.B_p_C[i] = pc->B_p_C[i];
-        for (int i = 0; i < 9; ++i) po.B_R_C[i] = pc->B_R_C[i];
-        pra.B = s->B; pra.N = s->N; pra.np = s->np; pra.ny = s->ny; pra.nyN = s->nyN;
-        pra.W_p_Bo = pc->W_p_Bo; pra.W_R_Bo = pc->W_R_Bo; pra.p = s->p;
-        if (sensor) {
-            if ((long long)pc->phase + a->steps > 2147483647LL)
-                return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the sensor's frame counter (phase + steps) overflows");
-            if (int rc = sdfnmpc_sensor_args_(sensor, const_cast<float*>(src.images), s->B, pc->h, pc->w, scratch, &sna, &ora))
-                return rc;
-        }
+        float* img = const_cast<float*>(src.images);
+        if (int rc = rollout_camera(s, pc, img, -2, pl)) return rc;
+        pl.src = &src; pl.pool = !src.is_signed;
+        if (sensor)
+            if (int rc = rollout_sensor(s, a, sensor, img, pc->h, pc->w, scratch, pl)) return rc;
     }
-    pa.K = a->steps;
-    pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
-    pa.pts_log = a->pts_log;
-    pa.status = s->status; pa.iters = s->iters;
-    pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
-    SolverDevice sd(s->device);
-    for (int k = 0; k < a->steps; ++k) {
-        if (pc && (k + pc->phase) % pc->every == 0) {  // a new image from the current state: pose, render, sensor, pool, pose into p
-            if (int rc = rollout_pose(s, spa, vr)) return rc;
-            // the scene's time at step k, the product rounded on its own as in sdfnmpc_solver_rollout_perceive_at
-            volatile double steps_dt = (double)(pc->phase + k) * dt;
-            const double t = t0 + steps_dt;
-            if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pc->scene, &sra, t)) return rc;
-            if (sensor)
-                if (int rc = sdfnmpc_sensor_launch_(s->ctx, &sna, &ora, sensor->outlier_rm != 0, pc->phase + k)) return rc;
-            if (!src.is_signed)
-                if (int rc = sdfnmpc_img_sdf_pool(s->ctx, &src, s->B)) return rc;
-            if (int rc = sdfnmpc_pack_refs(s->ctx, &po, &pra)) return rc;
-        }
-        if (a->ref)
-            if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
-        if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
-        if (int rc = step_enqueue(s)) return rc;
-        if (int rc = rollout_plant(s, a, pa, vr, k)) return rc;
-    }
-    if (int rc = rollout_end(s, a, vr)) return rc;
-    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
-    s->pending = true;
-    return SDFNMPC_OK;
+    return rollout_run(s, a, pl);
 }
 
 extern "C" int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
@@ -781,21 +791,12 @@ extern "C" int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnm
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: no image source set (sdfnmpc_solver_set_sdf_image)");
     if (!pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: perception (perc) is required");
     if (!dec) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: no decoder");
-    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
-    sdfn::PlantArgs pa{};
-    sdfnmpc_ref_args ra{};
-    VehicleRun vr{};
-    if (int rc = rollout_args(s, a, pa, ra, vr)) return rc;
+    if (int rc = rollout_clock(t0, dt)) return rc;
+    RolloutPlan pl;
+    pl.t0 = t0; pl.dt = dt;
+    if (int rc = rollout_args(s, a, pl)) return rc;
     const sdfnmpc_img_sdf_opts& src = s->img_src;
-    sdfn::ScenePoseArgs spa{};
-    sdfn::SceneRenderArgs sra{};
-    sdfnmpc_ref_opts po{};
-    sdfnmpc_ref_args pra{};
-    sdfn::SensorArgs sna{};
-    sdfn::OutlierArgs ora{};
-    if (pc->every < 1 || pc->phase < 0)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
+    if (int rc = rollout_schedule(pc->every, pc->phase)) return rc;
     if (!pc->scene || !sdfnmpc_scene_on_ctx_(pc->scene, s->ctx))
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: re-imaging needs a scene on the solver's context");
     if (!pc->vae || !sdfnmpc_vae_on_ctx_(pc->vae, s->ctx) || !sdfnmpc_vae_dec_on_ctx_(dec, s->ctx))
@@ -812,56 +813,15 @@ extern "C" int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnm
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: the camera buffer must not be the source's images");
     if (pc->img.is_depth && !pc->vae_opts.yz)
         return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: a depth camera needs the Depth2Range table (vae_opts.yz)");
-    if (int rc = sdfnmpc_scene_pose_args_(pc->B_p_C, pc->B_R_C, s->B, s->x0, pc->W_p_Bo, pc->W_R_Bo, pc->W_p_C,
-                                          pc->W_R_C, &spa))
-        return rc;
-    if (int rc = sdfnmpc_scene_render_args_(s->ctx, pc->scene, pc->scene_of, &pc->img, pc->h, pc->w, pc->scale, s->B,
-                                            pc->W_p_C, pc->W_R_C, pc->images, &sra))
-        return rc;
+    // rendered into the camera buffer, encoded, the reconstruction decoded into the source
+    if (int rc = rollout_camera(s, pc, pc->images, -2, pl)) return rc;
+    pl.vae = pc->vae; pl.cam = pc->images; pl.latent = pc->latent; pl.latent64 = pc->latent64;
     // the images are normalised: clip = 1, and Depth2Range exactly when the camera measures depth
-    sdfnmpc_vae_opts vo{s->B, pc->h, pc->w, 0, 1.0f, pc->img.is_depth ? pc->vae_opts.yz : nullptr};
-    po.mode = -2;
-    for (int i = 0; i < 3; ++i) po.B_p_C[i] = pc->B_p_C[i];
-    for (int i = 0; i < 9; ++i) po.B_R_C[i] = pc->B_R_C[i];
-    pra.B = s->B; pra.N = s->N; pra.np = s->np; pra.ny = s->ny; pra.nyN = s->nyN;
-    pra.W_p_Bo = pc->W_p_Bo; pra.W_R_Bo = pc->W_R_Bo; pra.p = s->p;
-    if (sensor) {
-        if ((long long)pc->phase + a->steps > 2147483647LL)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the sensor's frame counter (phase + steps) overflows");
-        if (int rc = sdfnmpc_sensor_args_(sensor, pc->images, s->B, pc->h, pc->w, scratch, &sna, &ora)) return rc;
-    }
-    pa.K = a->steps;
-    pa.x_log = a->x_log; pa.u_log = a->u_log; pa.status_log = a->status_log; pa.iters_log = a->iters_log;
-    pa.pts_log = a->pts_log;
-    pa.status = s->status; pa.iters = s->iters;
-    pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
-    SolverDevice sd(s->device);
-    for (int k = 0; k < a->steps; ++k) {
-        if ((k + pc->phase) % pc->every == 0) {  // pose, render into the camera buffer, sensor, encode, decode into the source, pool, pose into p
-            if (int rc = rollout_pose(s, spa, vr)) return rc;
-            // the scene's time at step k, the product rounded on its own as in sdfnmpc_solver_rollout_perceive_at
-            volatile double steps_dt = (double)(pc->phase + k) * dt;
-            const double t = t0 + steps_dt;
-            if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pc->scene, &sra, t)) return rc;
-            if (sensor)
-                if (int rc = sdfnmpc_sensor_launch_(s->ctx, &sna, &ora, sensor->outlier_rm != 0, pc->phase + k)) return rc;
-            if (int rc = sdfnmpc_vae_encode(s->ctx, pc->vae, &vo, pc->images, pc->latent, pc->latent64)) return rc;
-            if (int rc = sdfnmpc_vae_decode(s->ctx, dec, s->B, pc->latent, src.H, src.W, const_cast<float*>(src.images), nullptr))
-                return rc;
-            if (!src.is_signed)
-                if (int rc = sdfnmpc_img_sdf_pool(s->ctx, &src, s->B)) return rc;
-            if (int rc = sdfnmpc_pack_refs(s->ctx, &po, &pra)) return rc;
-        }
-        if (a->ref)
-            if (int rc = sdfnmpc_pack_refs(s->ctx, a->ref, &ra)) return rc;
-        if (int rc = sdfnmpc_solver_shift(s, a->shift)) return rc;
-        if (int rc = step_enqueue(s)) return rc;
-        if (int rc = rollout_plant(s, a, pa, vr, k)) return rc;
-    }
-    if (int rc = rollout_end(s, a, vr)) return rc;
-    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
-    s->pending = true;
-    return SDFNMPC_OK;
+    pl.vo = sdfnmpc_vae_opts{s->B, pc->h, pc->w, 0, 1.0f, pc->img.is_depth ? pc->vae_opts.yz : nullptr};
+    pl.dec = dec; pl.src = &src; pl.pool = !src.is_signed;
+    if (sensor)
+        if (int rc = rollout_sensor(s, a, sensor, pc->images, pc->h, pc->w, scratch, pl)) return rc;
+    return rollout_run(s, a, pl);
 }
 
 extern "C" int sdfnmpc_solver_wait(sdfnmpc_solver* s, double* u0, int* status, int* iters) {
