@@ -48,6 +48,10 @@ def lin_close(got, want, rtol=LIN_RTOL):
 # its fp64 evaluation by 2.8e-7 x max|latent| on the golden images; the GPU kernels (exact-fp32 MFMA
 # products, BatchNorm folded into the convolutions, a different summation order) are held to the
 # north-star fp32 bar, 1e-5 relative to the latent's scale, against the fp64 reference outputs.
+# At the seven small shapes of tests/vae_shape_cases.py ((8, 8) .. (90, 30), L = 1 .. 200) the same gap is at most
+# 4.4e-7 (the reference's Encoder and the plain restatement tests/vae_enc_ref.py agree on it), and the pooled
+# features before the mean Linear are within 4.7e-7 of max |feature| per image (tests/test_vae_enc_ref.py): the
+# bar keeps its meaning there, also for the elementwise check of tests/test_gpu_vae_shapes.py.
 VAE_LATENT_RTOL = 1e-5
 # preprocessing: torch's vectorised fp32 sqrt (Depth2Range table) is within 1 ulp of the correctly
 # rounded one (values <= 1 after the clip: 1 ulp <= 1.2e-7); Reshape's bilinear resize in torch fp32
