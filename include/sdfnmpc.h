@@ -46,7 +46,9 @@
  *                                      (no reference interface) an imperfect vehicle and estimator around the plant:
  *                                      input delay, thrust lag, rotor drag, gusts, bias and noise on the state
  *                                      estimate, reproducible per (seed, instance, frame); sdfnmpc_rollout_args.vehicle
- *                                      carries it through every rollout
+ *                                      carries it through every rollout; sdfnmpc_vehicle_set_body makes it a rigid
+ *                                      body (model/quad_props.py:41-48) under an attitude and rate loop and rotors
+ *                                      with a speed lag
  *
  *   sdfnmpc_colcheck                   ColChecker.check_image_points (utils/collision_checker.py:23-125)
  *   sdfnmpc_udf / sdfnmpc_sdf_truth    DfComputer.get_udf / get_sdf (utils/df_computer.py:85-221): the distance
@@ -90,7 +92,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 15
+#define SDFNMPC_ABI_VERSION 16
 
 enum {
     SDFNMPC_OK = 0,
@@ -347,7 +349,7 @@ int sdfnmpc_ctx_set_tile_rows(sdfnmpc_ctx* ctx, int rows);
 int sdfnmpc_ctx_enable_timing(sdfnmpc_ctx* ctx, int on);
 /* kernel: "sdf_mlp", "sdf_hoist", "linearize", "rti_qp", "plant", "scene_render", "scene_pose", "scene_dist",
  * "scene_render_dyn", "scene_dist_dyn", "scene_render_grid", "scene_dist_grid", "scene_sdf_rows_grid", "morph", "outlier_rm", "sensor_degrade",
- * "plant_vehicle", "vehicle_begin", "vehicle_reset", ...; synchronizes the stream(s) */
+ * "plant_vehicle", "plant_vehicle_body", "vehicle_begin", "vehicle_reset", ...; synchronizes the stream(s) */
 int sdfnmpc_ctx_kernel_stats(sdfnmpc_ctx* ctx, const char* kernel, double* total_ms, long long* launches);
 int sdfnmpc_ctx_reset_stats(sdfnmpc_ctx* ctx);
 
@@ -671,6 +673,46 @@ double* sdfnmpc_vehicle_x_true(sdfnmpc_vehicle* v);
 int sdfnmpc_plant_step_vehicle(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* opts, sdfnmpc_vehicle* v, int B,
                                const double* u, int frame, double* x_est_out);
 
+/* ---- the rigid-body vehicle (csrc/vehicle_body.hip) ----
+ * With a body the command (thrust, roll, pitch, yaw rate) is the setpoint of an on-board attitude and rate controller
+ * that drives four rotors with a first-order speed lag, which move a rigid body by model/quad_props.py:41-48.  It
+ * replaces steps 3 and 5 of the plant call above; delay, gust, drag and the estimate stay.  The plant options' kind
+ * only supplies the limits.  Hidden state per instance: x_true [10] = (p, q, v) with the full attitude in q, the body
+ * rate omega [3] (body frame) and the rotor speeds Omega [4] (the reference's unit, u robot.limits.wp).  With the applied
+ * input u: F = mass u[0] gamma, roll_d = u[1] roll, pitch_d = u[2] pitch, wz_d = u[3] wz; at every RK4 stage (a
+ * continuous controller, no sample-and-hold), with q normalised:
+ *   psi = quat2yaw(q), q_d = q_z(psi) (x) q_y(pitch_d) (x) q_x(roll_d), q_e = q^-1 (x) q_d, negated if q_e[0] < 0
+ *   omega_sp = (2 q_e[1] / tau_att, 2 q_e[2] / tau_att, wz_d)
+ *   tau = J k_rate (omega_sp - omega) + omega x J omega
+ *   s = mixer [F; tau], each clipped to [wp_idle^2, wp_max^2];  Omega_cmd = sqrt(s)
+ *   dOmega/dt = (Omega_cmd - Omega) / tau_mot      (tau_mot = 0: Omega = Omega_cmd)
+ *   dp/dt = v;  dq/dt = q (x) (0, omega) / 2;  domega/dt = (Gt Omega^2 - omega x J omega) / J
+ *   dv/dt = R(q) Gf Omega^2 gamma_scale / mass - g e_z + acc_dist + gust - R diag(drag) R^T v
+ * integrated on the 17 states with the plant's substeps, tableau and accumulation order.  A reset writes omega = 0 and
+ * Omega = sqrt(mixer [mass g; 0; 0; 0]), the hover speeds.  The matrices come from the caller (vehicle.RigidBody forms
+ * them from the motor geometry as quad_props.py:20-27 does): the kernel knows nothing of motor geometry. */
+typedef struct {
+    double mass;                   /* kg */
+    double inertia[3];             /* the diagonal of J, kg m^2 */
+    double Gf[12], Gt[12];         /* [3][4] row-major: body force and torque = G Omega^2 */
+    double mixer[16];              /* [4][4] row-major: inv([Gf row z; Gt]) */
+    double wp_max, wp_idle;        /* the rotor speed's range, 0 < wp_idle < wp_max */
+    double tau_att;                /* attitude loop time constant, s */
+    double k_rate[3];              /* rate loop gains, 1/s */
+    double tau_mot;                /* rotor speed lag, s (0: none) */
+} sdfnmpc_body_opts;
+/* opts: the vehicle becomes a rigid body (and is never neutral), its omega and Omega reset; NULL: the plain vehicle
+ * again, with the bits it had.  SDFNMPC_E_ARG (nothing is launched or allocated, the vehicle stays as it was): a
+ * non-finite or non-positive mass, inertia, wp_max, tau_att or k_rate, wp_idle outside (0, wp_max), tau_mot < 0 or
+ * non-finite, a non-finite matrix entry, a vehicle with tau_m > 0 (the rotor lag replaces the thrust lag).  With a
+ * body sdfnmpc_plant_step_vehicle and the rollouts also refuse (SDFNMPC_E_ARG, nothing launched) a step with
+ * (dt / substeps) max(1 / tau_mot, max k_rate, 2 / tau_att) > 1: RK4's real-axis stability limit is 2.78, and a batch
+ * that silently blows up is worse than a refusal. */
+int sdfnmpc_vehicle_set_body(sdfnmpc_vehicle* v, const sdfnmpc_body_opts* opts);
+/* the body's hidden states, device [B][3] and [B][4] (owned by the vehicle; each out pointer may be NULL).
+ * SDFNMPC_E_ARG: a NULL vehicle or one without a body. */
+int sdfnmpc_vehicle_body_state(sdfnmpc_vehicle* v, double** omega, double** rotor);
+
 /* K closed-loop steps of the solver's B instances without a host round trip.  Per step, in the order Nmpc.solve
  * uses: (1) with ref: sdfnmpc_pack_refs from the current x0 into the solver's p / yref / W / yNref / WN; (2) with
  * shift > 0: sdfnmpc_solver_shift(shift); (3) the SQP-RTI step of sdfnmpc_solver_step; (4) the plant on the solver's
@@ -705,6 +747,9 @@ typedef struct {
     int frame0;
     double* xhat_log;              /* device [B][K+1][10] or NULL: the estimates; row 0 = what _begin wrote */
     double* uapp_log;              /* device [B][K][4] or NULL: the applied (delayed) inputs */
+    /* a vehicle with a body (else SDFNMPC_E_ARG): its body rates and rotor speeds, row 0 before the first step */
+    double* omega_log;             /* device [B][K+1][3] or NULL */
+    double* rotor_log;             /* device [B][K+1][4] or NULL */
 } sdfnmpc_rollout_args;
 
 int sdfnmpc_solver_rollout(sdfnmpc_solver* s, const sdfnmpc_rollout_args* args);

@@ -48,7 +48,7 @@ SYMBOLS = [
     "sdfnmpc_solver_rollout_image_recon",
     "sdfnmpc_scene_create_large", "sdfnmpc_scene_is_indexed", "sdfnmpc_scene_create_mixed",
     "sdfnmpc_vehicle_create", "sdfnmpc_vehicle_destroy", "sdfnmpc_vehicle_reset", "sdfnmpc_vehicle_begin",
-    "sdfnmpc_vehicle_x_true", "sdfnmpc_plant_step_vehicle",
+    "sdfnmpc_vehicle_x_true", "sdfnmpc_plant_step_vehicle", "sdfnmpc_vehicle_set_body", "sdfnmpc_vehicle_body_state",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -156,13 +156,20 @@ class RolloutArgsC(C.Structure):
     _fields_ = [("steps", C.c_int), ("shift", C.c_int), ("ref", C.POINTER(RefOptsC))] + [
         (n, C.c_void_p) for n in ("wp_p", "wp_q", "vw", "wrow")] + [("n_wp", C.c_int), ("plant", PlantOptsC)] + [
         (n, C.c_void_p) for n in ("x_log", "u_log", "status_log", "iters_log", "pts_log")] + [
-        ("vehicle", C.c_void_p), ("frame0", C.c_int), ("xhat_log", C.c_void_p), ("uapp_log", C.c_void_p)]
+        ("vehicle", C.c_void_p), ("frame0", C.c_int), ("xhat_log", C.c_void_p), ("uapp_log", C.c_void_p),
+        ("omega_log", C.c_void_p), ("rotor_log", C.c_void_p)]
 
 
 class VehicleOptsC(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("d", C.c_int), ("tau_m", C.c_double), ("drag", C.c_double * 3)] + [
         (n, C.c_double) for n in ("gust_std", "gust_tau", "est_std_p", "est_std_v", "est_std_yaw")] + [
         ("est_bias", C.c_void_p), ("stream_id", C.c_void_p), ("g", C.c_double), ("gamma", C.c_double)]
+
+
+class BodyOptsC(C.Structure):
+    _fields_ = [("mass", C.c_double), ("inertia", C.c_double * 3), ("Gf", C.c_double * 12), ("Gt", C.c_double * 12),
+                ("mixer", C.c_double * 16), ("wp_max", C.c_double), ("wp_idle", C.c_double), ("tau_att", C.c_double),
+                ("k_rate", C.c_double * 3), ("tau_mot", C.c_double)]
 
 
 SCENE_MAX_PRIMS = 32  # SDFNMPC_SCENE_MAX_PRIMS
@@ -314,11 +321,13 @@ def load():
         "sdfnmpc_vehicle_begin": (i, [vp, vp, vp, i]),
         "sdfnmpc_vehicle_x_true": (vp, [vp]),
         "sdfnmpc_plant_step_vehicle": (i, [vp, P(PlantOptsC), vp, i, vp, i, vp]),
+        "sdfnmpc_vehicle_set_body": (i, [vp, P(BodyOptsC)]),
+        "sdfnmpc_vehicle_body_state": (i, [vp, P(vp), P(vp)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 15:
+    if lib.sdfnmpc_abi_version() != 16:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -1071,11 +1080,12 @@ class FieldView:
 
 
 def _vehicle_fields(vehicle):
-    """The trailing fields of sdfnmpc_rollout_args: (handle, frame0, xhat_log, uapp_log) or None."""
+    """The trailing fields of sdfnmpc_rollout_args: (handle, frame0, xhat_log, uapp_log[, omega_log, rotor_log]) or
+    None."""
     if vehicle is None:
-        return None, 0, None, None
-    h, frame0, xhat_log, uapp_log = vehicle
-    return h, int(frame0), _ptr(xhat_log), _ptr(uapp_log)
+        return None, 0, None, None, None, None
+    h, frame0, xhat_log, uapp_log, *body = tuple(vehicle) + (None, None)
+    return h, int(frame0), _ptr(xhat_log), _ptr(uapp_log), _ptr(body[0]), _ptr(body[1])
 
 
 def _sensor_args(sensor):
@@ -1158,8 +1168,9 @@ class Solver:
         scene_clock: (t0, dt) -- the image before step k shows the scene at t0 + (phase + k) dt
         (sdfnmpc_solver_rollout_perceive_at).  sensor: (SensorOptsC, scratch [B][h][w] float32 or None) -- the
         degradation of every new image before it is encoded (sdfnmpc_solver_rollout_perceive_sensor).  vehicle:
-        (handle, frame0, xhat_log [B][K+1][10] or None, uapp_log [B][K][4] or None) -- the vehicle model whose plant
-        call replaces the plant's (sdfnmpc_rollout_args.vehicle), after sdfnmpc_vehicle_begin on the x0 field."""
+        (handle, frame0, xhat_log [B][K+1][10] or None, uapp_log [B][K][4] or None[, omega_log [B][K+1][3] or None,
+        rotor_log [B][K+1][4] or None]) -- the vehicle model whose plant call replaces the plant's
+        (sdfnmpc_rollout_args.vehicle), after sdfnmpc_vehicle_begin on the x0 field; the last two for a rigid body."""
         a = self._rollout_args(steps, plant, x_log, u_log, status_log, iters_log, pts_log, shift, ref, wp_p, wp_q, vw,
                                wrow, n_wp, vehicle, perceive, sensor)
         if sensor is not None:

@@ -36,13 +36,14 @@ class Rollout:
     (the scene's clock at every log row), and with keep_img img [B, h, w] float32, the last images rendered (raw
     sensor values).  With a vehicle model x, col, pts and clearance are the true vehicle's, u the commands, and
     xhat [B, K+1, 10] the state estimates the controller was given (row 0 the one it started from), u_applied [B, K, 4]
-    the inputs the vehicle applied (the delayed commands); else both None."""
+    the inputs the vehicle applied (the delayed commands); else both None.  With a rigid-body vehicle omega [B, K+1, 3],
+    its body rates, and rotor [B, K+1, 4], its rotor speeds (row 0 before the first step); else both None."""
 
     def __init__(self, x, u, status, iters, col=None, pts=None, clearance=None, img=None, t=None, xhat=None,
-                 u_applied=None):
+                 u_applied=None, omega=None, rotor=None):
         self.x, self.u, self.status, self.iters, self.col, self.pts = x, u, status, iters, col, pts
         self.clearance, self.img, self.t = clearance, img, t
-        self.xhat, self.u_applied = xhat, u_applied
+        self.xhat, self.u_applied, self.omega, self.rotor = xhat, u_applied, omega, rotor
 
 
 class Nmpc:
@@ -380,7 +381,9 @@ class Nmpc:
         ``u_applied``.  With ``scene`` the camera sees from the true state while the body pose in p comes from the
         estimate; references (and a scene source's pose refresh) read the estimate.  The model keeps its hidden states
         from call to call (``vehicle.reset()`` starts afresh), so chunks with ``perceive_phase`` carried equal the uncut
-        rollout.  Afterwards ``self.x0`` is the true final state.
+        rollout.  Afterwards ``self.x0`` is the true final state.  A model with a ``body`` (``vehicle.RigidBody``) flies a
+        rigid body under an attitude and rate loop with lagging, saturating rotors; the result gains ``omega`` and
+        ``rotor``, and a plant whose ``dt / substeps`` the inner loop does not admit is refused (ValueError).
 
         Returns a ``Rollout`` of numpy arrays, batch-leading also for one instance: x [B, K+1, 10] (row 0 the
         start), u [B, K, 4], status / iters [B, K]; with imgs also col [B, K+1] bool and pts [B, K+1, 3] float32.
@@ -466,6 +469,8 @@ class Nmpc:
                 kw["vw"] = self._dev(np.reshape(np.asarray(vw, float), (Bn, 4)))
         if plant is None:
             plant = _lib.plant_opts(self.cfg, dt=float(self.ocp.dt[0]))
+        if vehicle is not None:
+            vehicle.check_plant(plant)  # a rigid body's step size, before anything is enqueued
         t0, dts = float(scene_t0), float(plant.dt if scene_dt is None else scene_dt)  # step k is at t0 + (phase + k) dts
         perc = rv = sn = None
         if scene is not None:  # pose, render, sensor, then into the latent, or (normalised) into the image source
@@ -495,6 +500,8 @@ class Nmpc:
         if vehicle is not None:  # x0 holds the truth: the model takes it and leaves its estimate there
             vehicle.begin(solver.field("x0"), int(perceive_phase))
             vlog = (_lib.DeviceArray(ctx, (Bn, K + 1, 10)), _lib.DeviceArray(ctx, (Bn, max(K, 1), 4)))
+            if vehicle.body is not None:
+                vlog += (_lib.DeviceArray(ctx, (Bn, K + 1, 3)), _lib.DeviceArray(ctx, (Bn, K + 1, 4)))
             kw["vehicle"] = (vehicle.h, int(perceive_phase)) + vlog
         if src is not None:  # the pose the FOV rows read is refreshed from the plant state, the scene's clock per step
             ws = _pose_workspaces(ctx, Bn)
@@ -515,6 +522,8 @@ class Nmpc:
         out = Rollout(log["x_log"].numpy(), log["u_log"].numpy(), log["status_log"].numpy(), log["iters_log"].numpy())
         if vehicle is not None:
             out.xhat, out.u_applied = vlog[0].numpy(), vlog[1].numpy()
+            if vehicle.body is not None:
+                out.omega, out.rotor = vlog[2].numpy(), vlog[3].numpy()
         if dimg is not None:
             s = self.cfg.sensor
             pts = _lib.FieldView(log["pts_log"].data_ptr(), (Bn * (K + 1), 3), np.float32, ctx)

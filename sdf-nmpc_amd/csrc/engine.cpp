@@ -1853,6 +1853,10 @@ struct sdfnmpc_vehicle {
     bool neutral = false;
     double* block = nullptr;  // [x_true B*10 | gamma_act B | w B*3 | ring B*d*4 | pose scratch B*12]
     double *x_true = nullptr, *gamma_act = nullptr, *w = nullptr, *ring = nullptr, *scratch = nullptr;
+    // the rigid body (sdfnmpc_vehicle_set_body): its options, and [omega B*3 | rotor B*4], allocated with the first body
+    bool body = false;
+    sdfnmpc_body_opts bo{};
+    double* body_block = nullptr;
 };
 
 // the option half of a VehicleArgs block (the plant's block, the frame, x_est and the logs are the caller's)
@@ -1920,7 +1924,27 @@ extern "C" void sdfnmpc_vehicle_destroy(sdfnmpc_vehicle* v) {
     if (!v) return;
     ScopedDevice sd(v->device);  // the context may be gone already: hipFree waits for the device
     if (v->block) (void)hipFree(v->block);
+    if (v->body_block) (void)hipFree(v->body_block);
     delete v;
+}
+
+// the body half of a VehicleBodyArgs block around a vehicle block (the logs are the caller's)
+static VehicleBodyArgs vehicle_body_block(const sdfnmpc_vehicle* v, const VehicleArgs& va) {
+    const sdfnmpc_body_opts& o = v->bo;
+    VehicleBodyArgs a{};
+    a.V = va;
+    a.m = o.mass; a.im = 1.0 / o.mass;
+    for (int i = 0; i < 3; ++i) { a.J[i] = o.inertia[i]; a.iJ[i] = 1.0 / o.inertia[i]; a.k_rate[i] = o.k_rate[i]; }
+    for (int i = 0; i < 12; ++i) { a.Gf[i] = o.Gf[i]; a.Gt[i] = o.Gt[i]; }
+    for (int i = 0; i < 16; ++i) a.M[i] = o.mixer[i];
+    a.s_min = o.wp_idle * o.wp_idle; a.s_max = o.wp_max * o.wp_max;
+    a.katt = 2.0 / o.tau_att;
+    a.itau_mot = o.tau_mot > 0.0 ? 1.0 / o.tau_mot : 0.0;
+    for (int i = 0; i < 4; ++i)  // sqrt(mixer [m g; 0; 0; 0]), clipped as every commanded speed is
+        a.hover[i] = std::sqrt(std::fmin(std::fmax(o.mixer[i * 4] * (o.mass * v->o.g), a.s_min), a.s_max));
+    a.omega = v->body_block;
+    a.rotor = v->body_block ? v->body_block + (size_t)v->B * 3 : nullptr;
+    return a;
 }
 
 extern "C" int sdfnmpc_vehicle_reset(sdfnmpc_vehicle* v) {
@@ -1928,6 +1952,50 @@ extern "C" int sdfnmpc_vehicle_reset(sdfnmpc_vehicle* v) {
     const VehicleArgs a = vehicle_block(v, 1.0);
     ScopedDevice sd(v->ctx->device);
     HIPCHK(timed(v->ctx, "vehicle_reset", [&] { return launch_vehicle_reset(a, v->ctx->stream); }));
+    if (v->body) {
+        const VehicleBodyArgs ba = vehicle_body_block(v, a);
+        HIPCHK(timed(v->ctx, "vehicle_body_reset", [&] { return launch_vehicle_body_reset(ba, v->ctx->stream); }));
+    }
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_vehicle_set_body(sdfnmpc_vehicle* v, const sdfnmpc_body_opts* o) {
+    if (!v) return fail(SDFNMPC_E_ARG, "NULL vehicle");
+    if (!o) {  // the plain vehicle again
+        v->body = false;
+        return SDFNMPC_OK;
+    }
+    auto pos = [](double a) { return std::isfinite(a) && a > 0.0; };
+    if (!pos(o->mass) || !pos(o->inertia[0]) || !pos(o->inertia[1]) || !pos(o->inertia[2]) || !pos(o->wp_max) ||
+        !pos(o->tau_att) || !pos(o->k_rate[0]) || !pos(o->k_rate[1]) || !pos(o->k_rate[2]))
+        return fail(SDFNMPC_E_ARG, "body opts: mass, inertia, wp_max, tau_att and k_rate must be positive and finite");
+    if (!pos(o->wp_idle) || !(o->wp_idle < o->wp_max)) return fail(SDFNMPC_E_ARG, "body opts: wp_idle must lie in (0, wp_max)");
+    if (!std::isfinite(o->tau_mot) || o->tau_mot < 0.0) return fail(SDFNMPC_E_ARG, "body opts: tau_mot must be finite and not negative");
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(o->mixer[i]) || (i < 12 && (!std::isfinite(o->Gf[i]) || !std::isfinite(o->Gt[i]))))
+            return fail(SDFNMPC_E_ARG, "body opts: Gf, Gt and mixer must be finite");
+    if (v->o.tau_m > 0.0)
+        return fail(SDFNMPC_E_ARG, "body: the vehicle has a thrust lag (tau_m > 0); the rotor lag tau_mot replaces it");
+    ScopedDevice sd(v->ctx->device);
+    if (!v->body_block && v->B > 0) {
+        const hipError_t e = hipMalloc((void**)&v->body_block, (size_t)v->B * 7 * sizeof(double));
+        if (e != hipSuccess) {
+            v->body_block = nullptr;
+            return fail(SDFNMPC_E_HIP, std::string("body buffers: ") + hipGetErrorString(e));
+        }
+    }
+    v->bo = *o;
+    v->body = true;
+    const VehicleBodyArgs ba = vehicle_body_block(v, vehicle_block(v, 1.0));
+    HIPCHK(timed(v->ctx, "vehicle_body_reset", [&] { return launch_vehicle_body_reset(ba, v->ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_vehicle_body_state(sdfnmpc_vehicle* v, double** omega, double** rotor) {
+    if (!v) return fail(SDFNMPC_E_ARG, "NULL vehicle");
+    if (!v->body) return fail(SDFNMPC_E_ARG, "vehicle_body_state: the vehicle has no body");
+    if (omega) *omega = v->body_block;
+    if (rotor) *rotor = v->body_block ? v->body_block + (size_t)v->B * 3 : nullptr;
     return SDFNMPC_OK;
 }
 
@@ -1957,7 +2025,7 @@ extern "C" int sdfnmpc_vehicle_info_(const sdfnmpc_vehicle* v, const sdfnmpc_ctx
     if (!v) return fail(SDFNMPC_E_ARG, "NULL vehicle");
     if (v->ctx != ctx) return fail(SDFNMPC_E_ARG, "vehicle: it lives on another context");
     if (v->B != B) return fail(SDFNMPC_E_ARG, "vehicle: built for " + std::to_string(v->B) + " instances, not " + std::to_string(B));
-    if (neutral) *neutral = v->neutral ? 1 : 0;
+    if (neutral) *neutral = v->neutral && !v->body ? 1 : 0;
     if (x_true) *x_true = v->x_true;
     if (scratch) *scratch = v->scratch;
     return SDFNMPC_OK;
@@ -1968,6 +2036,13 @@ extern "C" int sdfnmpc_vehicle_info_(const sdfnmpc_vehicle* v, const sdfnmpc_ctx
 extern "C" int sdfnmpc_vehicle_args_(const sdfnmpc_vehicle* v, const PlantArgs* pa, double* x_est, VehicleArgs* out) {
     if (!v || !pa || !out || (v->B > 0 && !x_est)) return fail(SDFNMPC_E_ARG, "vehicle: NULL argument");
     if (x_est == v->x_true) return fail(SDFNMPC_E_ARG, "vehicle: the estimate must not be written into the true state");
+    if (v->body) {  // the inner loop's fastest pole against the RK4 step
+        const sdfnmpc_body_opts& b = v->bo;
+        double rate = std::fmax(std::fmax(b.k_rate[0], b.k_rate[1]), std::fmax(b.k_rate[2], 2.0 / b.tau_att));
+        if (b.tau_mot > 0.0) rate = std::fmax(rate, 1.0 / b.tau_mot);
+        if (!((pa->dt / pa->substeps) * rate <= 1.0))
+            return fail(SDFNMPC_E_ARG, "body: (dt / substeps) max(1 / tau_mot, k_rate, 2 / tau_att) > 1: the inner loop needs more substeps");
+    }
     VehicleArgs a = vehicle_block(v, pa->dt);
     a.P = *pa;
     a.P.x = a.P.x_next = v->x_true;
@@ -1982,6 +2057,21 @@ extern "C" int sdfnmpc_vehicle_launch_(sdfnmpc_ctx* ctx, const VehicleArgs* a) {
     return SDFNMPC_OK;
 }
 
+// for solver.hip: whether the vehicle's plant call is the rigid body's
+extern "C" int sdfnmpc_vehicle_has_body_(const sdfnmpc_vehicle* v) { return v && v->body ? 1 : 0; }
+
+// the rigid body's plant call around a filled vehicle block (sdfnmpc_vehicle_args_ plus frame and logs)
+extern "C" int sdfnmpc_vehicle_launch_body_(sdfnmpc_ctx* ctx, const sdfnmpc_vehicle* v, const VehicleArgs* a,
+                                            double* omega_log, double* rotor_log) {
+    if (!v || !v->body) return fail(SDFNMPC_E_ARG, "vehicle: no body");
+    VehicleBodyArgs ba = vehicle_body_block(v, *a);
+    ba.omega_log = omega_log;
+    ba.rotor_log = rotor_log;
+    ScopedDevice sd(ctx->device);
+    HIPCHK(timed(ctx, "plant_vehicle_body", [&] { return launch_vehicle_body(ba, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
 extern "C" int sdfnmpc_plant_step_vehicle(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* o, sdfnmpc_vehicle* v, int B,
                                           const double* u, int frame, double* x_est_out) {
     if (!ctx) return fail(SDFNMPC_E_ARG, "NULL context");
@@ -1991,7 +2081,7 @@ extern "C" int sdfnmpc_plant_step_vehicle(sdfnmpc_ctx* ctx, const sdfnmpc_plant_
     PlantArgs pa{};
     if (int rc = sdfnmpc_plant_args_(o, B, v->x_true, u, v->x_true, &pa)) return rc;
     if (B == 0) return SDFNMPC_OK;
-    if (v->neutral) {  // the plant's own kernel, and the estimate a copy of the truth
+    if (v->neutral && !v->body) {  // the plant's own kernel, and the estimate a copy of the truth
         if (int rc = sdfnmpc_plant_launch_(ctx, &pa)) return rc;
         ScopedDevice sd(ctx->device);
         HIPCHK(hipMemcpyAsync(x_est_out, v->x_true, (size_t)B * 80, hipMemcpyDeviceToDevice, ctx->stream));
@@ -2000,6 +2090,7 @@ extern "C" int sdfnmpc_plant_step_vehicle(sdfnmpc_ctx* ctx, const sdfnmpc_plant_
     VehicleArgs va{};
     if (int rc = sdfnmpc_vehicle_args_(v, &pa, x_est_out, &va)) return rc;
     va.frame = (unsigned)frame;
+    if (v->body) return sdfnmpc_vehicle_launch_body_(ctx, v, &va, nullptr, nullptr);
     return sdfnmpc_vehicle_launch_(ctx, &va);
 }
 

@@ -34,6 +34,10 @@ extern "C" int sdfnmpc_vehicle_info_(const sdfnmpc_vehicle* v, const sdfnmpc_ctx
 extern "C" int sdfnmpc_vehicle_args_(const sdfnmpc_vehicle* v, const sdfn::PlantArgs* pa, double* x_est,
                                      sdfn::VehicleArgs* out);
 extern "C" int sdfnmpc_vehicle_launch_(sdfnmpc_ctx* ctx, const sdfn::VehicleArgs* a);
+// the rigid-body vehicle (timed as "plant_vehicle_body"): whether the vehicle has one, and its launch with its logs
+extern "C" int sdfnmpc_vehicle_has_body_(const sdfnmpc_vehicle* v);
+extern "C" int sdfnmpc_vehicle_launch_body_(sdfnmpc_ctx* ctx, const sdfnmpc_vehicle* v, const sdfn::VehicleArgs* a,
+                                            double* omega_log, double* rotor_log);
 // engine.cpp: the same split for the scene kernels a perceiving rollout repeats, and where an encoder / a scene lives
 extern "C" int sdfnmpc_scene_render_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of,
                                           const sdfnmpc_img_opts* o, int H, int W, float scale, int B,
@@ -418,7 +422,7 @@ extern "C" int sdfnmpc_solver_step(sdfnmpc_solver* s) {
 // on its own true state, and x0 receives the estimate.  neutral: a model with everything off -- the plant runs on x0
 // as without a vehicle, and the end of the rollout copies the logs and the final state the vehicle would have written.
 struct VehicleRun {
-    bool on = false, neutral = false;
+    bool on = false, neutral = false, body = false;
     sdfn::VehicleArgs va{};
     double *x_true = nullptr, *scratch = nullptr;
 };
@@ -490,6 +494,8 @@ static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, Rollou
     if (!a->vehicle) {
         if (a->xhat_log || a->uapp_log)
             return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: xhat_log and uapp_log need a vehicle");
+        if (a->omega_log || a->rotor_log)
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: omega_log and rotor_log need a vehicle with a body");
     } else {
         int neutral = 0;
         if (int rc = sdfnmpc_vehicle_info_(a->vehicle, s->ctx, s->B, &neutral, &vr.x_true, &vr.scratch)) return rc;
@@ -497,6 +503,9 @@ static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, Rollou
             return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the vehicle's frame counter (frame0 + steps) overflows or frame0 < 0");
         vr.neutral = neutral != 0;
         vr.on = !vr.neutral;
+        vr.body = sdfnmpc_vehicle_has_body_(a->vehicle) != 0;
+        if (!vr.body && (a->omega_log || a->rotor_log))
+            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: omega_log and rotor_log need a vehicle with a body");
         if (vr.on)
             if (int rc = sdfnmpc_vehicle_args_(a->vehicle, &pa, s->x0, &vr.va)) return rc;
     }
@@ -525,6 +534,7 @@ static int rollout_plant(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, sdfn:
     va.frame = (unsigned)(a->frame0 + k);
     va.xhat_log = a->xhat_log;
     va.uapp_log = a->uapp_log;
+    if (vr.body) return sdfnmpc_vehicle_launch_body_(s->ctx, a->vehicle, &va, a->omega_log, a->rotor_log);
     return sdfnmpc_vehicle_launch_(s->ctx, &va);
 }
 

@@ -13,7 +13,9 @@ clearance over the batch with and without the sensor model, and per launch the s
 scene_render and the encoder's from one timed rollout, plus the general morphology kernel with the radius-10 disc.
 --vehicle runs the device loop with and without a vehicle model of moderate size (rollout_probe.VEHICLE: two periods of
 input delay, thrust lag, rotor drag, gusts, noise on the state estimate) and prints the distribution of the minimum
-clearance of the true vehicle over the batch for both, and the rollout's ms per step.
+clearance of the true vehicle over the batch for both, and the rollout's ms per step.  --vehicle --body adds the same
+model as a rigid body (rollout_probe.BODY: attitude and rate loop, rotor lag and limits instead of the thrust lag) at
+16 plant substeps.  With synthetic network weights the distributions compare vehicles, not controllers.
 
 One configuration per run (give every run its own time limit):
     timeout 600 python tools/perceive_probe.py --B 1024 --N 40 --every 1
@@ -21,6 +23,7 @@ One configuration per run (give every run its own time limit):
     timeout 200 python tools/perceive_probe.py --B 1 --N 40 --every 1
     timeout 600 python tools/perceive_probe.py --B 256 --N 40 --every 1 --sensor
     timeout 600 python tools/perceive_probe.py --B 256 --N 40 --every 1 --vehicle
+    timeout 600 python tools/perceive_probe.py --B 256 --N 40 --every 1 --vehicle --body
 Prints ms per control step of both loops (best of --reps repetitions after a warm-up) and a JSON line.  Diagnostic."""
 import argparse
 import json
@@ -39,7 +42,7 @@ from sdf_nmpc_amd.scene import Scene
 from sdf_nmpc_amd.sensor import SensorModel
 from sdf_nmpc_amd.vae import VaeWrapper
 from sdf_nmpc_amd.vehicle import VehicleModel
-from rollout_probe import VEHICLE, controller
+from rollout_probe import BODY_SUBSTEPS, VEHICLE, body_vehicle, controller
 
 # vector instructions executed per ray-primitive test, from the loop body in the -save-temps assembly: 38 (box), 39
 # (sphere), 51 (cylinder); the probe's forest is one box, ten cylinders and five spheres
@@ -206,8 +209,10 @@ def vehicle_probe(cfg, a, res):
         n, x0, wps = controller(cfg, a.B, 1)
         ctx = n.ocp.ctx
         scene, vae = Scene(ctx, forest(16)), VaeWrapper(cfg, batch=a.B, ctx=ctx)
-        plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]))
+        plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]), substeps=BODY_SUBSTEPS[-1] if name == "body" else 1)
         m = VehicleModel(cfg, ctx, max(a.B, 1), seed=2024, **VEHICLE) if name == "vehicle" else None
+        if name == "body":
+            m = body_vehicle(cfg, ctx, max(a.B, 1), 2024)
         n.set_x0(x0)
         ctx.synchronize()
         t0 = time.perf_counter()
@@ -219,12 +224,13 @@ def vehicle_probe(cfg, a, res):
         n.ocp.close()
         return r, ms
 
-    run("vehicle")  # warms up (workspaces, code objects) and is not timed
+    names = ("perfect", "vehicle", "body") if a.body else ("perfect", "vehicle")
+    run(names[-1])  # warms up (workspaces, code objects) and is not timed
     runs = {}
-    for name in ("perfect", "vehicle"):
+    for name in names:
         runs[name], res[f"rollout_ms_per_step_{name}"] = run(name)
     q = (0, 5, 25, 50, 75, 95, 100)
-    for name in ("perfect", "vehicle"):
+    for name in names:
         mc = runs[name].clearance.min(axis=1)
         res[f"min_clearance_{name}_percentiles"] = dict(zip(map(str, q), np.percentile(mc, q).round(4).tolist()))
         res[f"collided_{name}"] = int((mc < 0).sum())
@@ -233,8 +239,11 @@ def vehicle_probe(cfg, a, res):
     print(f"B={a.B} N={a.N} K={a.K} every={a.every} with the vehicle model {VEHICLE}: rollout "
           f"{res['rollout_ms_per_step_perfect']:.3f} ms/step without it, {res['rollout_ms_per_step_vehicle']:.3f} ms/step "
           f"with it; std of the position estimate's error {res['est_pos_err_std']:.4f} m")
+    if a.body:
+        print(f"as a rigid body ({BODY_SUBSTEPS[-1]} plant substeps): {res['rollout_ms_per_step_body']:.3f} ms/step; rotors within "
+              f"{float(runs['body'].rotor.min()):.2f}..{float(runs['body'].rotor.max()):.2f}")
     print("min clearance of the true vehicle over the batch, percentiles", q)
-    for name in ("perfect", "vehicle"):
+    for name in names:
         print(f"  {name:8s}", list(res[f"min_clearance_{name}_percentiles"].values()), "collided:", res[f"collided_{name}"])
     print(json.dumps(res))
 
@@ -250,7 +259,10 @@ def main():
     ap.add_argument("--kernels-only", action="store_true", help="only the scene kernels' own times")
     ap.add_argument("--sensor", action="store_true", help="the loops under SensorModel.reference_augment")
     ap.add_argument("--vehicle", action="store_true", help="the device loop with and without a vehicle model")
+    ap.add_argument("--body", action="store_true", help="with --vehicle: also the model as a rigid body")
     a = ap.parse_args()
+    if a.body and not a.vehicle:
+        ap.error("--body goes with --vehicle")
     warnings.simplefilter("ignore")
     cfg = Config(mpc__N=a.N)
     res = {"B": a.B, "N": a.N, "K": a.K, "every": a.every, "moving": a.moving}

@@ -5,12 +5,15 @@ it (set_x0 -> gen_refs_device -> solve -> plant_step -> download the state), whi
 three copies per step.  Both use the plant kernel, so the loops compute the same bits (checked) and the difference
 is the host's.  Also the plant kernel's own time (HIP events) at substeps 1 and 10.  With --vehicle: the same for
 the vehicle model's kernel ("plant_vehicle": delay, thrust lag, drag, gusts, estimate noise all on) beside "plant",
-and the rollout's ms per step with and without the model.
+and the rollout's ms per step with and without the model.  With --vehicle --body: the rigid-body kernel
+("plant_vehicle_body": the same model with a RigidBody instead of the thrust lag) beside "plant_vehicle" at 8 and 16
+substeps, the rollout's ms per step with it (16 substeps), and the kernel's share of that step.
 
 One configuration per run (give every run its own time limit):
     timeout 300 python tools/rollout_probe.py --B 1024 --N 40      # C3
     timeout 120 python tools/rollout_probe.py --B 1 --N 40
     timeout 300 python tools/rollout_probe.py --B 1024 --N 40 --vehicle
+    timeout 300 python tools/rollout_probe.py --B 1024 --N 40 --vehicle --body
 Prints ms per control step of both loops (best of --reps repetitions after a warm-up) and a JSON line.  Diagnostic."""
 import argparse
 import json
@@ -27,11 +30,21 @@ from sdf_nmpc_amd import _lib
 from sdf_nmpc_amd.config import Config
 from sdf_nmpc_amd.controller import Nmpc
 from sdf_nmpc_amd.reference import yaw2quat
-from sdf_nmpc_amd.vehicle import VehicleModel
+from sdf_nmpc_amd.vehicle import RigidBody, VehicleModel
 
 # a model of moderate size with every term on: what the "plant_vehicle" figures are measured under
 VEHICLE = dict(delay=2, thrust_tau=0.05, drag=(0.3, 0.3, 0.1), gust_std=0.5, gust_tau=1.0, est_std_pos=0.03,
                est_std_vel=0.05, est_std_yaw=0.01)
+# the reference's default.yaml robot.* (mass, inertia, alloc, limits.wp) under RigidBody's default inner loop
+BODY = dict(mass=1.46, inertia=(0.017, 0.018, 0.028), cf=0.02246, ct=0.00020673, wp_max=25.0,
+            motors=[[0.09, -0.09, -0.005, 0, 0, -1], [-0.09, 0.09, -0.005, 0, 0, -1], [0.09, 0.09, -0.005, 0, 0, 1],
+                    [-0.09, -0.09, -0.005, 0, 0, 1]])
+BODY_SUBSTEPS = (8, 16)
+
+
+def body_vehicle(cfg, ctx, B, seed):
+    """VEHICLE with a rigid body: the rotor lag replaces the thrust lag."""
+    return VehicleModel(cfg, ctx, B, seed=seed, body=RigidBody(**BODY), **{k: v for k, v in VEHICLE.items() if k != "thrust_tau"})
 
 
 def controller(cfg, B, seed):
@@ -70,7 +83,10 @@ def main():
     ap.add_argument("--K", type=int, default=50)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--vehicle", action="store_true", help="also time the vehicle model's kernel and a rollout with it")
+    ap.add_argument("--body", action="store_true", help="with --vehicle: also the rigid-body kernel and a rollout with it")
     a = ap.parse_args()
+    if a.body and not a.vehicle:
+        ap.error("--body goes with --vehicle")
     warnings.simplefilter("ignore")
     cfg = Config(mpc__N=a.N)
     res = {"B": a.B, "N": a.N, "K": a.K}
@@ -134,6 +150,24 @@ def main():
             ctx.reset_stats()
             res[f"plant_vehicle_us_substeps{sub}"] = ms / cnt * 1e3
         m.close()
+    if a.body:  # both vehicle kernels at the substeps a rigid body needs
+        for name, m in (("plant_vehicle", VehicleModel(cfg, ctx, B, seed=1, **VEHICLE)), ("plant_vehicle_body", body_vehicle(cfg, ctx, B, 1))):
+            est = _lib.DeviceArray.from_numpy(ctx, xh[:, -1])
+            m.begin(est, 0)
+            for sub in BODY_SUBSTEPS:
+                o = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]), substeps=sub)
+                for f in range(20):
+                    m.step(o, du, f, est)
+                ctx.synchronize()
+                ctx.reset_stats()
+                ctx.enable_timing(True)
+                for f in range(200):
+                    m.step(o, du, 20 + f, est)
+                ms, cnt = ctx.kernel_stats(name)
+                ctx.enable_timing(False)
+                ctx.reset_stats()
+                res[f"{name}_us_substeps{sub}"] = ms / cnt * 1e3
+            m.close()
     n.ocp.close()
     if a.vehicle:  # the rollout of the first part again, alternating without and with the model
         t_off, t_on = [], []
@@ -153,6 +187,24 @@ def main():
                     m.close()
                 n.ocp.close()
         res["rollout_ms_per_step_no_vehicle"], res["rollout_ms_per_step_vehicle"] = min(t_off), min(t_on)
+    if a.body:  # and with the rigid body, at the finer plant step it needs
+        t_body = []
+        for rep in range(a.reps + 1):
+            n, x0, wps = controller(cfg, a.B, 1)
+            plant = _lib.plant_opts(cfg, dt=float(n.ocp.dt[0]), substeps=BODY_SUBSTEPS[-1])
+            m = body_vehicle(cfg, n.ocp.ctx, max(a.B, 1), 1)
+            n.set_x0(x0)
+            n.ocp.ctx.synchronize()
+            t0 = time.perf_counter()
+            rb = n.rollout(a.K, refs="wps", wps=wps, plant=plant, vehicle=m)
+            t1 = time.perf_counter()
+            if rep:
+                t_body.append((t1 - t0) / a.K * 1e3)
+            m.close()
+            n.ocp.close()
+        res["rollout_ms_per_step_body"] = min(t_body)
+        res["body_share_of_step"] = res[f"plant_vehicle_body_us_substeps{BODY_SUBSTEPS[-1]}"] * 1e-3 / min(t_body)
+        res["body_rotor_range"] = [float(rb.rotor.min()), float(rb.rotor.max())]
     print(f"B={a.B} N={a.N} K={a.K}: rollout {res['rollout_ms_per_step']:.3f} ms/step, host-driven loop "
           f"{res['host_loop_ms_per_step']:.3f} ms/step (same bits: {res['same_bits']}); plant kernel "
           f"{res['plant_us_substeps1']:.1f} us at substeps 1, {res['plant_us_substeps10']:.1f} us at substeps 10")
@@ -161,6 +213,11 @@ def main():
               f"{res['plant_vehicle_us_substeps10']:.1f} us at substeps 10; rollout "
               f"{res['rollout_ms_per_step_no_vehicle']:.3f} ms/step without the model, "
               f"{res['rollout_ms_per_step_vehicle']:.3f} ms/step with it")
+    if a.body:
+        print("rigid body: " + ", ".join(f"plant_vehicle_body {res[f'plant_vehicle_body_us_substeps{s}']:.1f} us beside plant_vehicle "
+                                          f"{res[f'plant_vehicle_us_substeps{s}']:.1f} us at substeps {s}" for s in BODY_SUBSTEPS) +
+              f"; rollout {res['rollout_ms_per_step_body']:.3f} ms/step with it ({BODY_SUBSTEPS[-1]} substeps), the kernel "
+              f"{100 * res['body_share_of_step']:.1f} % of a step; rotors within {res['body_rotor_range']}")
     print(json.dumps(res))
     if res["rollout_ms_per_step"] > res["host_loop_ms_per_step"]:
         print("NOTE: the rollout was not faster than the host-driven loop in this run")
