@@ -3,167 +3,38 @@
 // Host-side runtime only: all arithmetic of the hot path happens in sdf_mlp.hip / linearize.hip.
 // There is no CPU fallback: without a HIP device every compute entry point fails with
 // SDFNMPC_E_NODEVICE / SDFNMPC_E_HIP.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <thread>
-#include <string>
-#include <vector>
 
-#include "../../include/sdfnmpc.h"
+#include "engine.h"
 #include "lin_kernels.h"
 #include "qp_kernels.h"
 #include "ref_kernels.h"
-#include "sdf_kernels.h"
-#include "vae_kernels.h"
-#include "df_kernels.h"
-#include "plant_kernels.h"
-#include "scene_kernels.h"
-#include "sensor_kernels.h"
-#include "vehicle_kernels.h"
 
 using namespace sdfn;
 
 // ------------------------------------------------------------------------------------------------
 // errors
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) {
+int sdfn::fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(SDFNMPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+int sdfn::fail(int code, const char* msg) {
+    g_err = msg;
+    return code;
+}
 
 extern "C" int sdfnmpc_abi_version(void) { return SDFNMPC_ABI_VERSION; }
-// error reporting for solver.hip (same thread-local message)
-extern "C" int sdfnmpc_solver_fail_(int code, const char* msg) { return fail(code, msg); }
 extern "C" const char* sdfnmpc_last_error(void) { return g_err.c_str(); }
 
 // ------------------------------------------------------------------------------------------------
 // context
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    unsigned long long gen = 0;  // reallocations so far (a captured step graph holds the pointer of its time)
-    hipError_t ensure(size_t n) {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        ++gen;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
-struct KStat {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    double ms = 0.0;
-    long long n = 0;
-};
-
-struct sdfnmpc_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipStream_t aux = nullptr;                       // low-priority side stream (fork/join per call)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool serial_prep = false;  // diagnostic (SDFNMPC_SERIAL_PREP=1): linearize after the SDF kernel, same stream
-    int qp_kernel = SDFNMPC_QP_AUTO;  // SDFNMPC_QP_KERNEL=serial|segmented, or sdfnmpc_ctx_set_qp_kernel
-    int tile_rows = 32;
-    int n_cu = 0;              // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    size_t lds_per_cu = 0;     // LDS bytes per CU (hipDeviceProp_t::maxSharedMemoryPerMultiProcessor)
-    bool timing = false;
-    DevBuf c13, sdf4, lat, out4, glat, qpw, qpst, wws;
-    DevBuf dfpool;  // sdfnmpc_udf: the 5x5 min-pooled images
-    DevBuf imgpts;  // sdfnmpc_img_sdf_rows without the caller's pts: the camera-frame points of the rows
-    DevBuf morph_t, morph_e;  // sdfnmpc_outlier_rm with kernel_size != 3: the thresholded image and its erosion
-    // host-pointer path (sdf_eval_host, the CasADi external): pinned staging, its own hoist buffer and
-    // the latents it was computed for (consecutive acados calls share one latent: the hoist is reused)
-    float* h_pin = nullptr;
-    size_t h_pin_bytes = 0;
-    DevBuf hin, hout, hc13;
-    std::vector<float> h_lat;
-    uint64_t h_net = 0;  // uid of the network the cached hoist belongs to
-    // resident SDF server of the host path (sdf_row.hip, SdfMbox): mailbox in pinned coherent memory, its
-    // own stream, the network it serves, the last request number, and whether it may still be running
-    struct {
-        int mode = -1;                // -1: from SDFNMPC_SDF_SERVER (default on), 0 off, 1 on
-        SdfMbox* mb = nullptr;
-        SdfMbox* mb_dev = nullptr;
-        hipStream_t stream = nullptr;
-        uint64_t net = 0;
-        unsigned long long seq = 0;
-        bool live = false;
-        long long idle_ticks = 0, life_ticks = 0;
-        double idle_s = 0.001, life_s = 0.0008;  // SDFNMPC_SDF_SERVER_IDLE_MS / _LIFE_MS
-        unsigned long long epoch = 0;           // launches so far; the live server's is in `gone` once it left
-        bool abandoned = false;                 // a server that would not stop: its mailbox is never reused
-        double khz = 100000.0;
-        std::chrono::steady_clock::time_point last{};
-        double acc[4] = {0, 0, 0, 0};  // diagnostics: us staging, computing, host round trip; calls
-        double ph[14] = {};            // diagnostics: us per row_eval phase
-    } srv;
-    std::map<std::string, KStat> stats;
-    std::mutex mu;  // serialises the host-pointer path (CasADi externals may be called concurrently)
-    // stage records packed by sdfnmpc_rti_prepare, consumed by the next sdfnmpc_qp_feedback
-    struct {
-        bool valid = false;
-        int B = 0, N = 0;
-        const double* xn = nullptr;  // the lin outputs they were packed from
-        const void* work = nullptr;
-        bool sdf_row_patch = false;  // the feedback's QP kernel copies the sdf row of C^T into them
-        int ny = 0, cost_scaling = 0, lm_scaling = 0;  // the qp options the records were packed under
-        double lm = 0.0;
-        long long cset = 0;  // and their constraint set (cset_key)
-    } prep;
-};
-
-struct ScopedDevice {
-    int prev = -1;
-    explicit ScopedDevice(int d) {
-        (void)hipGetDevice(&prev);
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~ScopedDevice() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-// launch helper with optional HIP-event timing on the context stream
-template <typename F>
-static hipError_t timed(sdfnmpc_ctx* ctx, const char* name, F&& launch, hipStream_t st = nullptr) {
-    if (!ctx->timing) return launch();
-    if (!st) st = ctx->stream;
-    hipEvent_t a, b;
-    hipError_t e = hipEventCreate(&a);
-    if (e != hipSuccess) return e;
-    e = hipEventCreate(&b);
-    if (e != hipSuccess) return e;
-    (void)hipEventRecord(a, st);
-    e = launch();
-    (void)hipEventRecord(b, st);
-    ctx->stats[name].pending.emplace_back(a, b);
-    return e;
-}
-
 extern "C" int sdfnmpc_ctx_create(int device, void* stream, sdfnmpc_ctx** out) {
     if (!out) return fail(SDFNMPC_E_ARG, "out is NULL");
     *out = nullptr;
@@ -1306,14 +1177,6 @@ static hipError_t scene_sdf_rows_enqueue(sdfnmpc_ctx* ctx, const SceneSdfArgs& a
     return timed(ctx, "scene_sdf_rows", [&] { return launch_scene_sdf_rows(a, ctx->stream); });
 }
 
-// the option check + argument block of sdfnmpc_scene_sdf_rows (below, with the scenes): nothing is launched
-extern "C" int sdfnmpc_scene_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int B, int N, int np,
-                                       const double* x, const double* p, double* h, double* Jh, SceneSdfArgs* out);
-// the same split for sdfnmpc_img_sdf_rows (below, with the image ground truth)
-extern "C" int sdfnmpc_img_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int B, int N, int np,
-                                     const double* x, const double* p, double* h, double* Jh, float* pts,
-                                     ImgSdfArgs* out);
-
 // the launch of sdfnmpc_img_sdf_rows on the context stream: the scan reads its point from a buffer, the caller's pts or a
 // workspace of the context
 static int img_sdf_launch(sdfnmpc_ctx* ctx, ImgSdfArgs a) {
@@ -1369,10 +1232,10 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
     if (net && net->device != ctx->device) return fail(SDFNMPC_E_ARG, "net and ctx are on different devices");
     SceneSdfArgs ssa{};
     if (a->sdf_scene)  // refused before the first launch
-        if (int rc_ = sdfnmpc_scene_sdf_args_(ctx, a->sdf_scene, a->B, a->N, a->np, a->x, a->p, a->h, a->Jh, &ssa)) return rc_;
+        if (int rc_ = scene_sdf_args(ctx, a->sdf_scene, a->B, a->N, a->np, a->x, a->p, a->h, a->Jh, ssa)) return rc_;
     ImgSdfArgs isa{};
     if (a->sdf_image)
-        if (int rc_ = sdfnmpc_img_sdf_args_(ctx, a->sdf_image, a->B, a->N, a->np, a->x, a->p, a->h, a->Jh, nullptr, &isa))
+        if (int rc_ = img_sdf_args(ctx, a->sdf_image, a->B, a->N, a->np, a->x, a->p, a->h, a->Jh, nullptr, isa))
             return rc_;
     ScopedDevice sd(ctx->device);
     const long long rows = (long long)a->B * (a->N + 1);
@@ -1803,12 +1666,12 @@ extern "C" int sdfnmpc_rti_apply(sdfnmpc_ctx* ctx, int B, int N, double* x, doub
 }
 
 // ------------------------------------------------------------------------------------------------
-// the plant of a closed loop (plant.hip).  sdfnmpc_plant_args_ checks the options and fills the kernel's
-// argument block (nothing is launched); sdfnmpc_plant_launch_ launches a filled block on the context stream,
+// the plant of a closed loop (plant.hip).  plant_args checks the options and fills the kernel's
+// argument block (nothing is launched); plant_launch launches a filled block on the context stream,
 // timed as "plant".  Both are shared with sdfnmpc_solver_rollout (solver.hip), which adds the log pointers.
-extern "C" int sdfnmpc_plant_args_(const sdfnmpc_plant_opts* o, int B, const double* x, const double* u, double* x_next,
-                                   PlantArgs* out) {
-    if (!o || !out || B < 0 || (B > 0 && (!x || !u || !x_next)))
+int sdfn::plant_args(const sdfnmpc_plant_opts* o, int B, const double* x, const double* u, double* x_next,
+                     PlantArgs& out) {
+    if (!o || B < 0 || (B > 0 && (!x || !u || !x_next)))
         return fail(SDFNMPC_E_ARG, "plant: NULL argument or B < 0");
     if (o->kind != SDFNMPC_MODEL_ATT && o->kind != SDFNMPC_MODEL_ATT_TAU)
         return fail(SDFNMPC_E_UNSUPPORTED, "plant opts: kind: only 0 ('att') and 1 ('att_tau') are built");
@@ -1824,13 +1687,13 @@ extern "C" int sdfnmpc_plant_args_(const sdfnmpc_plant_opts* o, int B, const dou
         a.itau_pitch = 1.0 / o->tau_pitch;
     }
     a.x = x; a.u = u; a.x_next = x_next; a.acc_dist = o->acc_dist; a.gamma_scale = o->gamma_scale;
-    *out = a;
+    out = a;
     return SDFNMPC_OK;
 }
 
-extern "C" int sdfnmpc_plant_launch_(sdfnmpc_ctx* ctx, const PlantArgs* a) {
+int sdfn::plant_launch(sdfnmpc_ctx* ctx, const PlantArgs& a) {
     ScopedDevice sd(ctx->device);
-    HIPCHK(timed(ctx, "plant", [&] { return launch_plant(*a, ctx->stream); }));
+    HIPCHK(timed(ctx, "plant", [&] { return launch_plant(a, ctx->stream); }));
     return SDFNMPC_OK;
 }
 
@@ -1838,26 +1701,12 @@ extern "C" int sdfnmpc_plant_step(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* o,
                                   double* x_next) {
     if (!ctx) return fail(SDFNMPC_E_ARG, "NULL context");
     PlantArgs a{};
-    if (int rc = sdfnmpc_plant_args_(o, B, x, u, x_next, &a)) return rc;
-    return sdfnmpc_plant_launch_(ctx, &a);
+    if (int rc = plant_args(o, B, x, u, x_next, a)) return rc;
+    return plant_launch(ctx, a);
 }
 
 // ------------------------------------------------------------------------------------------------
-// the vehicle model around the plant (vehicle.hip).  The object owns the hidden states of B instances in one device
-// block; a model with everything off is `neutral` and every entry point runs the plant's own kernel (or a copy) for it.
-struct sdfnmpc_vehicle {
-    sdfnmpc_ctx* ctx = nullptr;
-    int device = 0;
-    int B = 0;
-    sdfnmpc_vehicle_opts o{};
-    bool neutral = false;
-    double* block = nullptr;  // [x_true B*10 | gamma_act B | w B*3 | ring B*d*4 | pose scratch B*12]
-    double *x_true = nullptr, *gamma_act = nullptr, *w = nullptr, *ring = nullptr, *scratch = nullptr;
-    // the rigid body (sdfnmpc_vehicle_set_body): its options, and [omega B*3 | rotor B*4], allocated with the first body
-    bool body = false;
-    sdfnmpc_body_opts bo{};
-    double* body_block = nullptr;
-};
+// the vehicle model around the plant (vehicle.hip; struct sdfnmpc_vehicle: engine.h)
 
 // the option half of a VehicleArgs block (the plant's block, the frame, x_est and the logs are the caller's)
 static VehicleArgs vehicle_block(const sdfnmpc_vehicle* v, double dt) {
@@ -2019,9 +1868,8 @@ extern "C" int sdfnmpc_vehicle_begin(sdfnmpc_ctx* ctx, sdfnmpc_vehicle* v, doubl
     return SDFNMPC_OK;
 }
 
-// for solver.hip: refuse a vehicle a rollout cannot use; *neutral, and where its true state and pose scratch live
-extern "C" int sdfnmpc_vehicle_info_(const sdfnmpc_vehicle* v, const sdfnmpc_ctx* ctx, int B, int* neutral,
-                                     double** x_true, double** scratch) {
+int sdfn::vehicle_info(const sdfnmpc_vehicle* v, const sdfnmpc_ctx* ctx, int B, int* neutral, double** x_true,
+                       double** scratch) {
     if (!v) return fail(SDFNMPC_E_ARG, "NULL vehicle");
     if (v->ctx != ctx) return fail(SDFNMPC_E_ARG, "vehicle: it lives on another context");
     if (v->B != B) return fail(SDFNMPC_E_ARG, "vehicle: built for " + std::to_string(v->B) + " instances, not " + std::to_string(B));
@@ -2031,40 +1879,36 @@ extern "C" int sdfnmpc_vehicle_info_(const sdfnmpc_vehicle* v, const sdfnmpc_ctx
     return SDFNMPC_OK;
 }
 
-// the vehicle's kernel block around a filled plant block (whose x / x_next become the vehicle's true state); frame and
-// the log pointers are the caller's.  Nothing is launched.
-extern "C" int sdfnmpc_vehicle_args_(const sdfnmpc_vehicle* v, const PlantArgs* pa, double* x_est, VehicleArgs* out) {
-    if (!v || !pa || !out || (v->B > 0 && !x_est)) return fail(SDFNMPC_E_ARG, "vehicle: NULL argument");
+// frame and the log pointers are the caller's
+int sdfn::vehicle_args(const sdfnmpc_vehicle* v, const PlantArgs& pa, double* x_est, VehicleArgs& out) {
+    if (!v || (v->B > 0 && !x_est)) return fail(SDFNMPC_E_ARG, "vehicle: NULL argument");
     if (x_est == v->x_true) return fail(SDFNMPC_E_ARG, "vehicle: the estimate must not be written into the true state");
     if (v->body) {  // the inner loop's fastest pole against the RK4 step
         const sdfnmpc_body_opts& b = v->bo;
         double rate = std::fmax(std::fmax(b.k_rate[0], b.k_rate[1]), std::fmax(b.k_rate[2], 2.0 / b.tau_att));
         if (b.tau_mot > 0.0) rate = std::fmax(rate, 1.0 / b.tau_mot);
-        if (!((pa->dt / pa->substeps) * rate <= 1.0))
+        if (!((pa.dt / pa.substeps) * rate <= 1.0))
             return fail(SDFNMPC_E_ARG, "body: (dt / substeps) max(1 / tau_mot, k_rate, 2 / tau_att) > 1: the inner loop needs more substeps");
     }
-    VehicleArgs a = vehicle_block(v, pa->dt);
-    a.P = *pa;
+    VehicleArgs a = vehicle_block(v, pa.dt);
+    a.P = pa;
     a.P.x = a.P.x_next = v->x_true;
     a.x_est = x_est;
-    *out = a;
+    out = a;
     return SDFNMPC_OK;
 }
 
-extern "C" int sdfnmpc_vehicle_launch_(sdfnmpc_ctx* ctx, const VehicleArgs* a) {
+int sdfn::vehicle_launch(sdfnmpc_ctx* ctx, const VehicleArgs& a) {
     ScopedDevice sd(ctx->device);
-    HIPCHK(timed(ctx, "plant_vehicle", [&] { return launch_vehicle(*a, ctx->stream); }));
+    HIPCHK(timed(ctx, "plant_vehicle", [&] { return launch_vehicle(a, ctx->stream); }));
     return SDFNMPC_OK;
 }
 
-// for solver.hip: whether the vehicle's plant call is the rigid body's
-extern "C" int sdfnmpc_vehicle_has_body_(const sdfnmpc_vehicle* v) { return v && v->body ? 1 : 0; }
-
-// the rigid body's plant call around a filled vehicle block (sdfnmpc_vehicle_args_ plus frame and logs)
-extern "C" int sdfnmpc_vehicle_launch_body_(sdfnmpc_ctx* ctx, const sdfnmpc_vehicle* v, const VehicleArgs* a,
-                                            double* omega_log, double* rotor_log) {
+// the rigid body's plant call around a filled vehicle block (vehicle_args plus frame and logs)
+int sdfn::vehicle_launch_body(sdfnmpc_ctx* ctx, const sdfnmpc_vehicle* v, const VehicleArgs& a, double* omega_log,
+                              double* rotor_log) {
     if (!v || !v->body) return fail(SDFNMPC_E_ARG, "vehicle: no body");
-    VehicleBodyArgs ba = vehicle_body_block(v, *a);
+    VehicleBodyArgs ba = vehicle_body_block(v, a);
     ba.omega_log = omega_log;
     ba.rotor_log = rotor_log;
     ScopedDevice sd(ctx->device);
@@ -2075,23 +1919,23 @@ extern "C" int sdfnmpc_vehicle_launch_body_(sdfnmpc_ctx* ctx, const sdfnmpc_vehi
 extern "C" int sdfnmpc_plant_step_vehicle(sdfnmpc_ctx* ctx, const sdfnmpc_plant_opts* o, sdfnmpc_vehicle* v, int B,
                                           const double* u, int frame, double* x_est_out) {
     if (!ctx) return fail(SDFNMPC_E_ARG, "NULL context");
-    if (int rc = sdfnmpc_vehicle_info_(v, ctx, B, nullptr, nullptr, nullptr)) return rc;
+    if (int rc = vehicle_info(v, ctx, B, nullptr, nullptr, nullptr)) return rc;
     if (frame < 0 || frame == 2147483647) return fail(SDFNMPC_E_ARG, "plant_step_vehicle: frame must be >= 0 and frame + 1 must not overflow");
     if (B > 0 && !x_est_out) return fail(SDFNMPC_E_ARG, "plant_step_vehicle: NULL x_est_out");
     PlantArgs pa{};
-    if (int rc = sdfnmpc_plant_args_(o, B, v->x_true, u, v->x_true, &pa)) return rc;
+    if (int rc = plant_args(o, B, v->x_true, u, v->x_true, pa)) return rc;
     if (B == 0) return SDFNMPC_OK;
     if (v->neutral && !v->body) {  // the plant's own kernel, and the estimate a copy of the truth
-        if (int rc = sdfnmpc_plant_launch_(ctx, &pa)) return rc;
+        if (int rc = plant_launch(ctx, pa)) return rc;
         ScopedDevice sd(ctx->device);
         HIPCHK(hipMemcpyAsync(x_est_out, v->x_true, (size_t)B * 80, hipMemcpyDeviceToDevice, ctx->stream));
         return SDFNMPC_OK;
     }
     VehicleArgs va{};
-    if (int rc = sdfnmpc_vehicle_args_(v, &pa, x_est_out, &va)) return rc;
+    if (int rc = vehicle_args(v, pa, x_est_out, va)) return rc;
     va.frame = (unsigned)frame;
-    if (v->body) return sdfnmpc_vehicle_launch_body_(ctx, v, &va, nullptr, nullptr);
-    return sdfnmpc_vehicle_launch_(ctx, &va);
+    if (v->body) return vehicle_launch_body(ctx, v, va, nullptr, nullptr);
+    return vehicle_launch(ctx, va);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2125,26 +1969,6 @@ extern "C" int sdfnmpc_shooting_grid(int N, double T, int uniform, int n_short, 
 
 // ------------------------------------------------------------------------------------------------
 // in-loop VAE encoder: .vaew blob -> device weights + activation workspace
-struct VaeLayer {
-    const float* w = nullptr;
-    const float* b = nullptr;
-    const unsigned short* wpl = nullptr;  // convolutions: w split into bf16 planes (VaeConvArgs::wpl)
-    int cin = 0, cout = 0, ks = 0, stride = 0;
-};
-
-struct sdfnmpc_vae {
-    int device = 0;
-    const sdfnmpc_ctx* ctx = nullptr;  // the context it was loaded on (sdfnmpc_solver_rollout_perceive asks)
-    int L = 0, H = 0, W = 0;
-    int Hc = 0, Wc = 0, Hp = 0, Wp = 0;
-    int bh[4] = {0}, bw[4] = {0};  // block output maps
-    void* dmem = nullptr;
-    VaeLayer stem, conv[11], head;  // conv: b0a b0s b0b b1a b1s b1b b2a b2s b2b b3a b3b
-    const unsigned short* stem_wpl = nullptr;  // the stem weights split into bf16 planes (VaeStemArgs::wpl)
-    const float* zero16 = nullptr;              // 16 zero floats (VaeConvArgs::zero: a tap outside the map)
-    DevBuf ws;
-    int ws_B = 0;
-};
 
 static const int kVaeBlockIn[4] = {64, 128, 256, 512};
 static const int kVaeBlockStride[4] = {2, 2, 2, 1};
@@ -2364,26 +2188,6 @@ extern "C" int sdfnmpc_vae_encode(sdfnmpc_ctx* ctx, sdfnmpc_vae* v, const sdfnmp
 
 // ------------------------------------------------------------------------------------------------
 // VAE decoder (vae_dec.hip): .vaed blob -> device weights + activation workspace
-struct VaeDecOp {
-    size_t wpl_off = 0, b_off = 0;  // in floats from the device block
-    const unsigned short* wpl = nullptr;
-    const float* b = nullptr;
-    size_t wps = 0;
-    int cin = 0, cout = 0, nphase = 0;
-    int ntaps[4] = {0}, py[4] = {0}, px[4] = {0};
-    unsigned woff[4] = {0};
-    signed char dy[4][VAE_DEC_TAPS] = {{0}}, dx[4][VAE_DEC_TAPS] = {{0}};
-};
-
-struct sdfnmpc_vae_dec {
-    int device = 0;
-    const sdfnmpc_ctx* ctx = nullptr;
-    int L = 0;
-    void* dmem = nullptr;
-    const float *head_w = nullptr, *head_b = nullptr, *tail_w = nullptr, *tail_b = nullptr;
-    VaeDecOp up[4], sc[4], cv[4];  // per ResBlockDeconv: the stride-2 3x3, the shortcut, the stride-1 3x3
-    DevBuf ws;
-};
 
 static const int kDecH0 = 8, kDecW0 = 15, kDecC0 = 512, kDecF = 512 * 8 * 15;
 static const int kDecChunk = 64;  // images decoded per pass: bounds the workspace (about 22 MB an image)
@@ -2529,7 +2333,6 @@ extern "C" void sdfnmpc_vae_dec_free(sdfnmpc_vae_dec* d) {
 }
 
 extern "C" int sdfnmpc_vae_dec_size_latent(const sdfnmpc_vae_dec* d) { return d ? d->L : -1; }
-extern "C" int sdfnmpc_vae_dec_on_ctx_(const sdfnmpc_vae_dec* d, const sdfnmpc_ctx* ctx) { return d && d->ctx == ctx; }
 
 extern "C" int sdfnmpc_vae_decode(sdfnmpc_ctx* ctx, sdfnmpc_vae_dec* d, int B, const float* latent, int out_h, int out_w,
                                   float* img, float* logits) {
@@ -2689,10 +2492,9 @@ extern "C" int sdfnmpc_sdf_truth(sdfnmpc_ctx* ctx, const sdfnmpc_img_opts* o, fl
 
 // the image's own field as the SDF row (df_truth.hip: img_sdf_rows_kernel): the option check and the argument block,
 // split from the launch for the preparation phase (lin_args.sdf_image) and the solver.  Nothing is launched.
-extern "C" int sdfnmpc_img_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int B, int N, int np,
-                                     const double* x, const double* p, double* h, double* Jh, float* pts,
-                                     ImgSdfArgs* out) {
-    if (!ctx || !o || !out) return fail(SDFNMPC_E_ARG, "img_sdf_rows: NULL context or options");
+int sdfn::img_sdf_args(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int B, int N, int np, const double* x,
+                       const double* p, double* h, double* Jh, float* pts, ImgSdfArgs& out) {
+    if (!ctx || !o) return fail(SDFNMPC_E_ARG, "img_sdf_rows: NULL context or options");
     if (B < 0 || N < 1 || np < 17) return fail(SDFNMPC_E_ARG, "img_sdf_rows: B >= 0, N >= 1 and np >= 17 required");
     if (!(o->img.dmax > 0.f) || !(o->img.hfov > 0.f) || !(o->img.vfov > 0.f))
         return fail(SDFNMPC_E_ARG, "img_sdf_rows: dmax, hfov and vfov must be positive");
@@ -2720,14 +2522,14 @@ extern "C" int sdfnmpc_img_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opt
     a.grid = o->grid; a.dist = o->dist; a.orig_idx = o->orig_idx; a.G = o->G;
     a.rows = (long long)B * (N + 1); a.N1 = N + 1; a.np = np;
     a.x = x; a.p = p; a.h = h; a.Jh = Jh; a.pts = pts;
-    *out = a;
+    out = a;
     return SDFNMPC_OK;
 }
 
 extern "C" int sdfnmpc_img_sdf_rows(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int B, int N, int np,
                                     const double* x, const double* p, double* h, double* Jh, float* pts) {
     ImgSdfArgs a{};
-    if (int rc = sdfnmpc_img_sdf_args_(ctx, o, B, N, np, x, p, h, Jh, pts, &a)) return rc;
+    if (int rc = img_sdf_args(ctx, o, B, N, np, x, p, h, Jh, pts, a)) return rc;
     if (B == 0) return SDFNMPC_OK;
     ScopedDevice sd(ctx->device);
     return img_sdf_launch(ctx, a);
@@ -2750,18 +2552,6 @@ extern "C" int sdfnmpc_img_sdf_pool(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts
 
 // ------------------------------------------------------------------------------------------------
 // analytic scenes (scene.hip)
-struct sdfnmpc_scene {
-    int device = 0;
-    const sdfnmpc_ctx* ctx = nullptr;
-    int S = 0;
-    void* dmem = nullptr;  // count [S] | ScenePrimD [S][32] | ScenePrimF [S][32] | dynamic: ScenePrimDyn [S][32]
-    SceneDev dev{};
-    const ScenePrimDyn* dyn = nullptr;  // non-NULL: a dynamic set (some primitive is oriented or moves)
-    const int* mcount = nullptr;        // [S]: with dev.ghdr and dyn, the movers per scene of a mixed set
-    // an indexed set (sdfnmpc_scene_create_large; dev.ghdr != nullptr): count [S] | SceneGridHdr [S] | ScenePrimD [total]
-    // | ScenePrimF [total] | cell_start | cell_items, every block at a multiple of 16 bytes; a mixed set
-    // (sdfnmpc_scene_create_mixed; dev.ghdr and dyn both non-NULL) appends mcount [S] | ScenePrimDyn [S][32]
-};
 
 // kind, values and ranges of one primitive, as sdfnmpc_scene_create checks them; na = the number of values read
 static int scene_prim_check(const sdfnmpc_prim* p, int* na) {
@@ -3110,17 +2900,13 @@ extern "C" void sdfnmpc_scene_free(sdfnmpc_scene* sc) {
     delete sc;
 }
 
-// whether an encoder / a scene lives on this very context (sdfnmpc_solver_rollout_perceive, solver.hip)
-extern "C" int sdfnmpc_vae_on_ctx_(const sdfnmpc_vae* v, const sdfnmpc_ctx* ctx) { return v && v->ctx == ctx; }
-extern "C" int sdfnmpc_scene_on_ctx_(const sdfnmpc_scene* sc, const sdfnmpc_ctx* ctx) { return sc && sc->ctx == ctx; }
 extern "C" int sdfnmpc_scene_is_dynamic(const sdfnmpc_scene* sc) { return sc && sc->dyn; }
 
-// the option checks of the two launches a rollout repeats, split from the launches as the plant's are: _args_
-// refuses or fills the kernel's argument block (nothing is launched), _launch_ enqueues a filled block
-extern "C" int sdfnmpc_scene_render_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of,
-                                          const sdfnmpc_img_opts* o, int H, int W, float scale, int B,
-                                          const double* W_p_C, const double* W_R_C, float* img, SceneRenderArgs* out) {
-    if (!ctx || !sc || !o || !out) return fail(SDFNMPC_E_ARG, "scene_render: NULL context, scene or options");
+// the option checks of the two launches a rollout repeats, split from the launches as the plant's are
+int sdfn::scene_render_args(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of, const sdfnmpc_img_opts* o,
+                            int H, int W, float scale, int B, const double* W_p_C, const double* W_R_C, float* img,
+                            SceneRenderArgs& out) {
+    if (!ctx || !sc || !o) return fail(SDFNMPC_E_ARG, "scene_render: NULL context, scene or options");
     if (sc->device != ctx->device) return fail(SDFNMPC_E_ARG, "scene_render: the scene lives on another device");
     if (B < 0 || B > 65535) return fail(SDFNMPC_E_ARG, "scene_render: B must be 0..65535");
     if (H < 1 || W < 1 || (long long)H * W > 2147483647LL) return fail(SDFNMPC_E_ARG, "scene_render: bad image size");
@@ -3143,27 +2929,26 @@ extern "C" int sdfnmpc_scene_render_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene*
         a.tz0 = (float)(tv * (1.0 - 1.0 / H)); a.tz1 = (float)(-2.0 * tv / H);
     }
     a.img = img;
-    *out = a;
+    out = a;
     return SDFNMPC_OK;
 }
 
-extern "C" int sdfnmpc_scene_render_launch_(sdfnmpc_ctx* ctx, const SceneRenderArgs* a) {
+static int scene_render_static(sdfnmpc_ctx* ctx, const SceneRenderArgs& a) {
     ScopedDevice sd(ctx->device);
-    if (a->sc.ghdr) {  // an indexed set
-        HIPCHK(timed(ctx, "scene_render_grid", [&] { return launch_scene_render_grid(*a, ctx->stream); }));
+    if (a.sc.ghdr) {  // an indexed set
+        HIPCHK(timed(ctx, "scene_render_grid", [&] { return launch_scene_render_grid(a, ctx->stream); }));
         return SDFNMPC_OK;
     }
-    HIPCHK(timed(ctx, "scene_render", [&] { return launch_scene_render(*a, ctx->stream); }));
+    HIPCHK(timed(ctx, "scene_render", [&] { return launch_scene_render(a, ctx->stream); }));
     return SDFNMPC_OK;
 }
 
 // the scene at time t: a static set takes the launch above whatever t is, a dynamic one its own kernel
-extern "C" int sdfnmpc_scene_render_launch_at_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const SceneRenderArgs* a,
-                                               double t) {
-    if (!sc->dyn) return sdfnmpc_scene_render_launch_(ctx, a);
-    const SceneRenderDynArgs da{*a, sc->dyn, t, sc->mcount};
+int sdfn::scene_render_launch(sdfnmpc_ctx* ctx, const sdfnmpc_scene& sc, const SceneRenderArgs& a, double t) {
+    if (!sc.dyn) return scene_render_static(ctx, a);
+    const SceneRenderDynArgs da{a, sc.dyn, t, sc.mcount};
     ScopedDevice sd(ctx->device);
-    if (a->sc.ghdr) {  // a mixed set: the grid plus movers
+    if (a.sc.ghdr) {  // a mixed set: the grid plus movers
         HIPCHK(timed(ctx, "scene_render_mixed", [&] { return launch_scene_render_mixed(da, ctx->stream); }));
         return SDFNMPC_OK;
     }
@@ -3171,9 +2956,9 @@ extern "C" int sdfnmpc_scene_render_launch_at_(sdfnmpc_ctx* ctx, const sdfnmpc_s
     return SDFNMPC_OK;
 }
 
-extern "C" int sdfnmpc_scene_pose_args_(const double* B_p_C, const double* B_R_C, int B, const double* x, double* W_p_Bo,
-                                        double* W_R_Bo, double* W_p_C, double* W_R_C, ScenePoseArgs* out) {
-    if (!B_p_C || !B_R_C || !out) return fail(SDFNMPC_E_ARG, "scene_pose: NULL extrinsics");
+int sdfn::scene_pose_args(const double* B_p_C, const double* B_R_C, int B, const double* x, double* W_p_Bo,
+                          double* W_R_Bo, double* W_p_C, double* W_R_C, ScenePoseArgs& out) {
+    if (!B_p_C || !B_R_C) return fail(SDFNMPC_E_ARG, "scene_pose: NULL extrinsics");
     if (B < 0) return fail(SDFNMPC_E_ARG, "scene_pose: B < 0");
     if (B > 0 && (!x || !W_p_Bo || !W_R_Bo || !W_p_C || !W_R_C)) return fail(SDFNMPC_E_ARG, "scene_pose: NULL state or output");
     ScenePoseArgs a{};
@@ -3181,13 +2966,13 @@ extern "C" int sdfnmpc_scene_pose_args_(const double* B_p_C, const double* B_R_C
     for (int i = 0; i < 3; ++i) a.B_p_C[i] = B_p_C[i];
     for (int i = 0; i < 9; ++i) a.B_R_C[i] = B_R_C[i];
     a.W_p_Bo = W_p_Bo; a.W_R_Bo = W_R_Bo; a.W_p_C = W_p_C; a.W_R_C = W_R_C;
-    *out = a;
+    out = a;
     return SDFNMPC_OK;
 }
 
-extern "C" int sdfnmpc_scene_pose_launch_(sdfnmpc_ctx* ctx, const ScenePoseArgs* a) {
+int sdfn::scene_pose_launch(sdfnmpc_ctx* ctx, const ScenePoseArgs& a) {
     ScopedDevice sd(ctx->device);
-    HIPCHK(timed(ctx, "scene_pose", [&] { return launch_scene_pose(*a, ctx->stream); }));
+    HIPCHK(timed(ctx, "scene_pose", [&] { return launch_scene_pose(a, ctx->stream); }));
     return SDFNMPC_OK;
 }
 
@@ -3195,25 +2980,25 @@ extern "C" int sdfnmpc_scene_render(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, c
                                     const sdfnmpc_img_opts* o, int H, int W, float scale, int B, const double* W_p_C,
                                     const double* W_R_C, float* img) {
     SceneRenderArgs a{};
-    if (int rc = sdfnmpc_scene_render_args_(ctx, sc, scene_of, o, H, W, scale, B, W_p_C, W_R_C, img, &a)) return rc;
-    return B == 0 ? SDFNMPC_OK : sdfnmpc_scene_render_launch_at_(ctx, sc, &a, 0.0);  // a dynamic set at t = 0
+    if (int rc = scene_render_args(ctx, sc, scene_of, o, H, W, scale, B, W_p_C, W_R_C, img, a)) return rc;
+    return B == 0 ? SDFNMPC_OK : scene_render_launch(ctx, *sc, a, 0.0);  // a dynamic set at t = 0
 }
 
 extern "C" int sdfnmpc_scene_render_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of,
                                        const sdfnmpc_img_opts* o, int H, int W, float scale, int B, const double* W_p_C,
                                        const double* W_R_C, double t, float* img) {
     SceneRenderArgs a{};
-    if (int rc = sdfnmpc_scene_render_args_(ctx, sc, scene_of, o, H, W, scale, B, W_p_C, W_R_C, img, &a)) return rc;
+    if (int rc = scene_render_args(ctx, sc, scene_of, o, H, W, scale, B, W_p_C, W_R_C, img, a)) return rc;
     if (!std::isfinite(t)) return fail(SDFNMPC_E_ARG, "scene_render: the time must be finite");
-    return B == 0 ? SDFNMPC_OK : sdfnmpc_scene_render_launch_at_(ctx, sc, &a, t);
+    return B == 0 ? SDFNMPC_OK : scene_render_launch(ctx, *sc, a, t);
 }
 
 extern "C" int sdfnmpc_scene_pose(sdfnmpc_ctx* ctx, const double* B_p_C, const double* B_R_C, int B, const double* x,
                                   double* W_p_Bo, double* W_R_Bo, double* W_p_C, double* W_R_C) {
     if (!ctx) return fail(SDFNMPC_E_ARG, "NULL context");
     ScenePoseArgs a{};
-    if (int rc = sdfnmpc_scene_pose_args_(B_p_C, B_R_C, B, x, W_p_Bo, W_R_Bo, W_p_C, W_R_C, &a)) return rc;
-    return B == 0 ? SDFNMPC_OK : sdfnmpc_scene_pose_launch_(ctx, &a);
+    if (int rc = scene_pose_args(B_p_C, B_R_C, B, x, W_p_Bo, W_R_Bo, W_p_C, W_R_C, a)) return rc;
+    return B == 0 ? SDFNMPC_OK : scene_pose_launch(ctx, a);
 }
 
 extern "C" int sdfnmpc_scene_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const double* points,
@@ -3252,9 +3037,9 @@ extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* 
 
 // the scene's exact distance as the SDF row (scene_sdf.hip): the option check and the argument block, split from the
 // launch as the other scene entry points' are, for the preparation phase (lin_args.sdf_scene) and the solver
-extern "C" int sdfnmpc_scene_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int B, int N, int np,
-                                       const double* x, const double* p, double* h, double* Jh, SceneSdfArgs* out) {
-    if (!ctx || !o || !o->scene || !out) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: NULL context, options or scene");
+int sdfn::scene_sdf_args(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int B, int N, int np, const double* x,
+                         const double* p, double* h, double* Jh, SceneSdfArgs& out) {
+    if (!ctx || !o || !o->scene) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: NULL context, options or scene");
     if (B < 0 || N < 1 || np < 17) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: B >= 0, N >= 1 and np >= 17 required");
     if (!(o->max_df > 0.0) || !std::isfinite(o->max_df))
         return fail(SDFNMPC_E_ARG, "scene_sdf_rows: max_df must be positive and finite");
@@ -3266,14 +3051,14 @@ extern "C" int sdfnmpc_scene_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf
     a.rows = (long long)B * (N + 1); a.N1 = N + 1; a.np = np;
     a.x = x; a.p = p; a.h = h; a.Jh = Jh;
     a.max_df = o->max_df; a.t0 = o->t0; a.tau = o->tau;
-    *out = a;
+    out = a;
     return SDFNMPC_OK;
 }
 
 extern "C" int sdfnmpc_scene_sdf_rows(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int B, int N, int np,
                                       const double* x, const double* p, double* h, double* Jh) {
     SceneSdfArgs a{};
-    if (int rc = sdfnmpc_scene_sdf_args_(ctx, o, B, N, np, x, p, h, Jh, &a)) return rc;
+    if (int rc = scene_sdf_args(ctx, o, B, N, np, x, p, h, Jh, a)) return rc;
     if (B == 0) return SDFNMPC_OK;
     ScopedDevice sd(ctx->device);
     HIPCHK(scene_sdf_rows_enqueue(ctx, a));
@@ -3359,11 +3144,11 @@ extern "C" int sdfnmpc_outlier_rm(sdfnmpc_ctx* ctx, int kernel_size, float min_r
     return SDFNMPC_OK;
 }
 
-// sdfnmpc_sensor_apply in two halves (solver.hip repeats the second inside a rollout): _args_ refuses or fills the two
-// kernels' argument blocks, _launch_ enqueues them for a frame
-extern "C" int sdfnmpc_sensor_args_(const sdfnmpc_sensor_opts* o, float* img, int B, int H, int W, float* scratch,
-                                    SensorArgs* sa, OutlierArgs* oa) {
-    if (!o || !sa || !oa) return fail(SDFNMPC_E_ARG, "sensor: NULL options");
+// sdfnmpc_sensor_apply in two halves (solver.hip repeats the second inside a rollout): sensor_args refuses or fills the
+// two kernels' argument blocks, sensor_launch enqueues them for a frame
+int sdfn::sensor_args(const sdfnmpc_sensor_opts* o, float* img, int B, int H, int W, float* scratch, SensorArgs& sa,
+                      OutlierArgs& oa) {
+    if (!o) return fail(SDFNMPC_E_ARG, "sensor: NULL options");
     if (int rc = image_batch_check("sensor", B, H, W)) return rc;
     if (!(std::isfinite(o->a) && o->a >= 0.f && std::isfinite(o->b) && o->b >= 0.f))
         return fail(SDFNMPC_E_ARG, "sensor: a and b must be finite and not negative");
@@ -3373,7 +3158,7 @@ extern "C" int sdfnmpc_sensor_args_(const sdfnmpc_sensor_opts* o, float* img, in
     if (B > 0 && !img) return fail(SDFNMPC_E_ARG, "sensor: NULL image");
     if (o->outlier_rm) {
         if (B > 0 && !scratch) return fail(SDFNMPC_E_ARG, "sensor: outlier_rm needs the scratch image");
-        if (int rc = outlier_args(o->min_range, img, B, H, W, scratch, oa)) return rc;
+        if (int rc = outlier_args(o->min_range, img, B, H, W, scratch, &oa)) return rc;
     }
     SensorArgs a{};
     a.img = img; a.B = B; a.H = H; a.W = W;
@@ -3381,20 +3166,19 @@ extern "C" int sdfnmpc_sensor_args_(const sdfnmpc_sensor_opts* o, float* img, in
     a.a = o->a; a.b = o->b; a.vmax = o->vmax; a.p_thresh = o->p_thresh; a.miss_invalid = o->miss_invalid != 0;
     a.boxes = (o->boxes && o->max_boxes > 0) ? o->boxes : nullptr;
     a.n_frames = o->n_frames; a.max_boxes = o->max_boxes; a.stream_id = o->stream_id;
-    *sa = a;
+    sa = a;
     return SDFNMPC_OK;
 }
 
-extern "C" int sdfnmpc_sensor_launch_(sdfnmpc_ctx* ctx, const SensorArgs* sa, const OutlierArgs* oa, int outlier_rm,
-                                      int frame) {
-    if (sa->B == 0) return SDFNMPC_OK;
-    SensorArgs a = *sa;
+int sdfn::sensor_launch(sdfnmpc_ctx* ctx, const SensorArgs& sa, const OutlierArgs& oa, int outlier_rm, int frame) {
+    if (sa.B == 0) return SDFNMPC_OK;
+    SensorArgs a = sa;
     a.frame = (unsigned)frame;
     ScopedDevice sd(ctx->device);
     HIPCHK(timed(ctx, "sensor_degrade", [&] { return launch_sensor_degrade(a, ctx->stream); }));
     if (outlier_rm) {
-        HIPCHK(timed(ctx, "outlier_rm", [&] { return launch_outlier_rm(*oa, ctx->stream); }));
-        HIPCHK(hipMemcpyAsync(a.img, oa->out, (size_t)a.B * a.H * a.W * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(timed(ctx, "outlier_rm", [&] { return launch_outlier_rm(oa, ctx->stream); }));
+        HIPCHK(hipMemcpyAsync(a.img, oa.out, (size_t)a.B * a.H * a.W * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     }
     return SDFNMPC_OK;
 }
@@ -3404,7 +3188,7 @@ extern "C" int sdfnmpc_sensor_apply(sdfnmpc_ctx* ctx, const sdfnmpc_sensor_opts*
     if (!ctx) return fail(SDFNMPC_E_ARG, "sensor: NULL context");
     SensorArgs sa{};
     OutlierArgs oa{};
-    if (int rc = sdfnmpc_sensor_args_(o, img, B, H, W, scratch, &sa, &oa)) return rc;
+    if (int rc = sensor_args(o, img, B, H, W, scratch, sa, oa)) return rc;
     if (frame < 0) return fail(SDFNMPC_E_ARG, "sensor: frame must be >= 0");
-    return sdfnmpc_sensor_launch_(ctx, &sa, &oa, o->outlier_rm != 0, frame);
+    return sensor_launch(ctx, sa, oa, o->outlier_rm != 0, frame);
 }

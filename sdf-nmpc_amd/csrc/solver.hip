@@ -7,69 +7,15 @@
 // instances.  The compute is the lower-level entry points (sdfnmpc_rti_prepare, sdfnmpc_qp_feedback,
 // sdfnmpc_rti_apply); this file adds buffer ownership, masked row uploads through a pinned staging
 // arena, and the asynchronous step / wait split that lets one host thread keep several devices busy.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/sdfnmpc.h"
-#include "df_kernels.h"
-#include "plant_kernels.h"
+#include "engine.h"
 #include "ref_kernels.h"
-#include "scene_kernels.h"
-#include "sensor_kernels.h"
-#include "vehicle_kernels.h"
 
-extern "C" int sdfnmpc_solver_fail_(int code, const char* msg);  // engine.cpp: sets sdfnmpc_last_error
-// engine.cpp: the plant's option check + argument block, and its launch on the context stream (timed as "plant")
-extern "C" int sdfnmpc_plant_args_(const sdfnmpc_plant_opts* o, int B, const double* x, const double* u, double* x_next,
-                                   sdfn::PlantArgs* out);
-extern "C" int sdfnmpc_plant_launch_(sdfnmpc_ctx* ctx, const sdfn::PlantArgs* a);
-// engine.cpp: the vehicle model around the plant -- what a rollout refuses about it, its argument block around a
-// filled plant block, and its launch (timed as "plant_vehicle")
-extern "C" int sdfnmpc_vehicle_info_(const sdfnmpc_vehicle* v, const sdfnmpc_ctx* ctx, int B, int* neutral, double** x_true,
-                                     double** scratch);
-extern "C" int sdfnmpc_vehicle_args_(const sdfnmpc_vehicle* v, const sdfn::PlantArgs* pa, double* x_est,
-                                     sdfn::VehicleArgs* out);
-extern "C" int sdfnmpc_vehicle_launch_(sdfnmpc_ctx* ctx, const sdfn::VehicleArgs* a);
-// the rigid-body vehicle (timed as "plant_vehicle_body"): whether the vehicle has one, and its launch with its logs
-extern "C" int sdfnmpc_vehicle_has_body_(const sdfnmpc_vehicle* v);
-extern "C" int sdfnmpc_vehicle_launch_body_(sdfnmpc_ctx* ctx, const sdfnmpc_vehicle* v, const sdfn::VehicleArgs* a,
-                                            double* omega_log, double* rotor_log);
-// engine.cpp: the same split for the scene kernels a perceiving rollout repeats, and where an encoder / a scene lives
-extern "C" int sdfnmpc_scene_render_args_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of,
-                                          const sdfnmpc_img_opts* o, int H, int W, float scale, int B,
-                                          const double* W_p_C, const double* W_R_C, float* img,
-                                          sdfn::SceneRenderArgs* out);
-extern "C" int sdfnmpc_scene_render_launch_at_(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const sdfn::SceneRenderArgs* a,
-                                               double t);
-extern "C" int sdfnmpc_scene_pose_args_(const double* B_p_C, const double* B_R_C, int B, const double* x, double* W_p_Bo,
-                                        double* W_R_Bo, double* W_p_C, double* W_R_C,
-                                        sdfn::ScenePoseArgs* out);
-extern "C" int sdfnmpc_scene_pose_launch_(sdfnmpc_ctx* ctx, const sdfn::ScenePoseArgs* a);
-extern "C" int sdfnmpc_vae_on_ctx_(const sdfnmpc_vae* v, const sdfnmpc_ctx* ctx);
-extern "C" int sdfnmpc_vae_dec_on_ctx_(const sdfnmpc_vae_dec* d, const sdfnmpc_ctx* ctx);
-// engine.cpp: the same split for the sensor stage of a perceiving rollout (degradation, then the fused outlier removal)
-extern "C" int sdfnmpc_sensor_args_(const sdfnmpc_sensor_opts* o, float* img, int B, int H, int W, float* scratch,
-                                    sdfn::SensorArgs* sa, sdfn::OutlierArgs* oa);
-extern "C" int sdfnmpc_sensor_launch_(sdfnmpc_ctx* ctx, const sdfn::SensorArgs* sa, const sdfn::OutlierArgs* oa,
-                                      int outlier_rm, int frame);
-extern "C" int sdfnmpc_scene_on_ctx_(const sdfnmpc_scene* sc, const sdfnmpc_ctx* ctx);
-// engine.cpp: the option check of sdfnmpc_img_sdf_rows (nothing is launched)
-extern "C" int sdfnmpc_img_sdf_args_(sdfnmpc_ctx* ctx, const sdfnmpc_img_sdf_opts* o, int B, int N, int np,
-                                     const double* x, const double* p, double* h, double* Jh, float* pts,
-                                     sdfn::ImgSdfArgs* out);
+using namespace sdfn;
 
 namespace {
-
-#define SCHK(expr)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return sdfnmpc_solver_fail_(SDFNMPC_E_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 // rows r of a [rows][width] field receive staged[r'][0..ncol) at columns col0.. (r = idx[r'])
 __global__ __launch_bounds__(256) void scatter_rows_kernel(double* dst, int width, int col0, int ncol,
@@ -206,41 +152,28 @@ struct sdfnmpc_solver {
     }
 };
 
-struct SolverDevice {
-    int prev = -1;
-    explicit SolverDevice(int d) {
-        (void)hipGetDevice(&prev);
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~SolverDevice() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 extern "C" int sdfnmpc_solver_create(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_solver_opts* o,
                                      sdfnmpc_solver** out) {
-    if (!ctx || !o || !out) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_create");
+    if (!ctx || !o || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_create");
     *out = nullptr;
     if (o->B < 1 || o->N < 1 || o->np < 17 || (o->ny != 11 && o->ny != 12) || !o->dt ||
         (o->latent_mode != 0 && o->latent_mode != 1) || o->qp.ny != o->ny)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "solver opts: B, N >= 1, np >= 17, ny in {11, 12} == qp.ny, dt required");
+        return fail(SDFNMPC_E_ARG, "solver opts: B, N >= 1, np >= 17, ny in {11, 12} == qp.ny, dt required");
     if (o->qp.nyN != 4 && o->qp.nyN != 5)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "solver opts: qp.nyN must be 4 or 5");
+        return fail(SDFNMPC_E_ARG, "solver opts: qp.nyN must be 4 or 5");
     // the model kinds the preparation phase is built for (sdfnmpc_quad_model.kind), refused here and not at the first step
     if (o->model.kind != SDFNMPC_MODEL_ATT && o->model.kind != SDFNMPC_MODEL_ATT_TAU)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_UNSUPPORTED, "solver opts: model.kind: only 0 ('att') and 1 ('att_tau') are built");
+        return fail(SDFNMPC_E_UNSUPPORTED, "solver opts: model.kind: only 0 ('att') and 1 ('att_tau') are built");
     if (o->model.kind == SDFNMPC_MODEL_ATT_TAU && (o->model.rec_feas || o->model.stability))
-        return sdfnmpc_solver_fail_(SDFNMPC_E_UNSUPPORTED, "solver opts: model.kind 1 ('att_tau') with rec_feas / stability");
+        return fail(SDFNMPC_E_UNSUPPORTED, "solver opts: model.kind 1 ('att_tau') with rec_feas / stability");
     bool need_sdf = o->ny == 12;  // the constraint set or the cost reads the network
     for (int j = 0; j < o->qp.nh && j < 3; ++j) need_sdf = need_sdf || o->qp.h_col[j] == 2;
     for (int j = 0; j < o->qp.nhN && j < SDFNMPC_NHN_MAX; ++j) need_sdf = need_sdf || o->qp.hN_col[j] == 2;
     if (need_sdf && !net)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "solver: the constraint set / cost reads the SDF but the network is NULL");
+        return fail(SDFNMPC_E_ARG, "solver: the constraint set / cost reads the SDF but the network is NULL");
     if (net && o->np < 17 + sdfnmpc_net_size_latent(net))  // the stage parameters end with the network's latent
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, ("solver opts: np = " + std::to_string(o->np) + " < 17 + latent size " +
-                                                    std::to_string(sdfnmpc_net_size_latent(net)) + " of this network").c_str());
+        return fail(SDFNMPC_E_ARG, "solver opts: np = " + std::to_string(o->np) + " < 17 + latent size " +
+                                       std::to_string(sdfnmpc_net_size_latent(net)) + " of this network");
     auto* s = new sdfnmpc_solver();
     s->ctx = ctx;
     s->net = net;
@@ -252,7 +185,7 @@ extern "C" int sdfnmpc_solver_create(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, c
     s->model = o->model;
     s->qp = o->qp;
     s->h_dt.assign(o->dt, o->dt + o->N);
-    SolverDevice sd(s->device);
+    ScopedDevice sd(s->device);
     const size_t B = o->B, N = o->N, N1 = N + 1;
     hipError_t e = hipSuccess;
     auto A = [&](auto** p, size_t n) { if (e == hipSuccess) e = s->alloc(p, n); };
@@ -277,7 +210,7 @@ extern "C" int sdfnmpc_solver_create(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, c
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     if (e != hipSuccess) {
         delete s;
-        return sdfnmpc_solver_fail_(SDFNMPC_E_HIP, (std::string("solver buffers: ") + hipGetErrorString(e)).c_str());
+        return fail(SDFNMPC_E_HIP, std::string("solver buffers: ") + hipGetErrorString(e));
     }
     const int n = (int)N, n1 = (int)N1, d = 8, w = (int)nyN;
     s->fields = {{"x", s->x, n1, 10, d},       {"u", s->u, n, 4, d},          {"p", s->p, n1, o->np, d},
@@ -296,9 +229,9 @@ extern "C" int sdfnmpc_solver_create(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, c
 extern "C" void sdfnmpc_solver_destroy(sdfnmpc_solver* s) { delete s; }
 
 extern "C" int sdfnmpc_solver_field(sdfnmpc_solver* s, const char* name, void** dev, int* nodes, int* width) {
-    if (!s || !name) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_field");
+    if (!s || !name) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_field");
     const Field* f = s->field(name);
-    if (!f) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, (std::string("no solver field ") + name).c_str());
+    if (!f) return fail(SDFNMPC_E_ARG, std::string("no solver field ") + name);
     if (dev) *dev = f->dev;
     if (nodes) *nodes = f->nodes;
     if (width) *width = f->width;
@@ -307,18 +240,18 @@ extern "C" int sdfnmpc_solver_field(sdfnmpc_solver* s, const char* name, void** 
 
 extern "C" int sdfnmpc_solver_upload(sdfnmpc_solver* s, const char* name, int col0, int ncol, const unsigned char* mask,
                                      const double* host) {
-    if (!s || !name || !host) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_upload");
+    if (!s || !name || !host) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_upload");
     const Field* f = s->field(name);
-    if (!f || f->elem != 8) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, (std::string("no fp64 solver field ") + name).c_str());
-    if (col0 < 0 || ncol < 1 || col0 + ncol > f->width) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "upload columns out of range");
-    SolverDevice sd(s->device);
+    if (!f || f->elem != 8) return fail(SDFNMPC_E_ARG, std::string("no fp64 solver field ") + name);
+    if (col0 < 0 || ncol < 1 || col0 + ncol > f->width) return fail(SDFNMPC_E_ARG, "upload columns out of range");
+    ScopedDevice sd(s->device);
     const int rows = s->B * f->nodes;
     if (!mask && col0 == 0 && ncol == f->width) {  // the whole field: one staged copy
         char* st = nullptr;
         const size_t bytes = (size_t)rows * f->width * 8;
-        SCHK(s->stage(bytes, &st));
+        HIPCHK(s->stage(bytes, &st));
         memcpy(st, host, bytes);
-        SCHK(hipMemcpyAsync(f->dev, st, bytes, hipMemcpyHostToDevice, s->stream));
+        HIPCHK(hipMemcpyAsync(f->dev, st, bytes, hipMemcpyHostToDevice, s->stream));
         return SDFNMPC_OK;
     }
     int n_rows = 0;
@@ -328,7 +261,7 @@ extern "C" int sdfnmpc_solver_upload(sdfnmpc_solver* s, const char* name, int co
     // and hand out a block overlapping the first
     char *vals = nullptr, *dvals = nullptr;
     const size_t vbytes = ((size_t)n_rows * ncol * 8 + 15) & ~(size_t)15;
-    SCHK(s->stage(vbytes + (size_t)n_rows * 4, &vals, &dvals));
+    HIPCHK(s->stage(vbytes + (size_t)n_rows * 4, &vals, &dvals));
     char *idx = vals + vbytes, *didx = dvals + vbytes;
     double* v = (double*)vals;
     int* ix = (int*)idx;
@@ -337,48 +270,48 @@ extern "C" int sdfnmpc_solver_upload(sdfnmpc_solver* s, const char* name, int co
             memcpy(v + (size_t)q * ncol, host + (size_t)r * f->width + col0, (size_t)ncol * 8);
             ix[q++] = r;
         }
-    SCHK(hipMemcpyAsync(dvals, vals, (size_t)n_rows * ncol * 8, hipMemcpyHostToDevice, s->stream));
-    SCHK(hipMemcpyAsync(didx, idx, (size_t)n_rows * 4, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemcpyAsync(dvals, vals, (size_t)n_rows * ncol * 8, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemcpyAsync(didx, idx, (size_t)n_rows * 4, hipMemcpyHostToDevice, s->stream));
     const long long n = (long long)n_rows * ncol;
     hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (double*)f->dev,
                        f->width, col0, ncol, (const double*)dvals, (const int*)didx, n_rows);
-    SCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SDFNMPC_OK;
 }
 
 extern "C" int sdfnmpc_solver_download(sdfnmpc_solver* s, const char* name, void* host) {
-    if (!s || !name || !host) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_download");
+    if (!s || !name || !host) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_download");
     const Field* f = s->field(name);
-    if (!f) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, (std::string("no solver field ") + name).c_str());
-    SolverDevice sd(s->device);
-    SCHK(hipMemcpyAsync(host, f->dev, (size_t)s->B * f->nodes * f->width * f->elem, hipMemcpyDeviceToHost, s->stream));
-    SCHK(hipStreamSynchronize(s->stream));
+    if (!f) return fail(SDFNMPC_E_ARG, std::string("no solver field ") + name);
+    ScopedDevice sd(s->device);
+    HIPCHK(hipMemcpyAsync(host, f->dev, (size_t)s->B * f->nodes * f->width * f->elem, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
     return SDFNMPC_OK;
 }
 
 extern "C" int sdfnmpc_solver_init(sdfnmpc_solver* s, const double* x0, const double* u_init) {
-    if (!s || !x0 || !u_init) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_init");
-    SolverDevice sd(s->device);
+    if (!s || !x0 || !u_init) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_init");
+    ScopedDevice sd(s->device);
     int rc = sdfnmpc_solver_upload(s, "x0", 0, 10, nullptr, x0);
     if (rc) return rc;
     const long long n = (long long)s->B * (s->N + 1) * 10;
     hipLaunchKernelGGL(init_iterate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->B, s->N, s->x,
                        s->u, (const double*)s->x0, u_init[0], u_init[1], u_init[2], u_init[3]);
-    SCHK(hipGetLastError());
-    SCHK(hipMemsetAsync(s->dx, 0, (size_t)s->B * (s->N + 1) * 10 * 8, s->stream));
-    SCHK(hipMemsetAsync(s->du, 0, (size_t)s->B * s->N * 4 * 8, s->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(s->dx, 0, (size_t)s->B * (s->N + 1) * 10 * 8, s->stream));
+    HIPCHK(hipMemsetAsync(s->du, 0, (size_t)s->B * s->N * 4 * 8, s->stream));
     return SDFNMPC_OK;
 }
 
 extern "C" int sdfnmpc_solver_shift(sdfnmpc_solver* s, int k) {
-    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
+    if (!s) return fail(SDFNMPC_E_ARG, "NULL solver");
     if (k <= 0 || k >= s->N) return SDFNMPC_OK;  // ocp.py:153: k > 0 shifts nodes k..N-1 down by k
-    SolverDevice sd(s->device);
+    ScopedDevice sd(s->device);
     // one launch (it was four strided copies through a scratch buffer: launch latency on the C1 path)
     const long long n = (long long)s->B * 14;
     hipLaunchKernelGGL(shift_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->B, s->N, k, s->x,
                        s->u);
-    SCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SDFNMPC_OK;
 }
 
@@ -386,7 +319,7 @@ extern "C" int sdfnmpc_solver_shift(sdfnmpc_solver* s, int k) {
 static int step_enqueue(sdfnmpc_solver* s) {
     const size_t n1 = s->N + 1;
     // x_0 of the iterate = the measured state (Ocp.solve: solver.set(0, 'x', x0), ocp.py:161)
-    SCHK(hipMemcpy2DAsync(s->x, n1 * 80, s->x0, 80, 80, s->B, hipMemcpyDeviceToDevice, s->stream));
+    HIPCHK(hipMemcpy2DAsync(s->x, n1 * 80, s->x0, 80, 80, s->B, hipMemcpyDeviceToDevice, s->stream));
     sdfnmpc_lin_args la{};
     la.B = s->B; la.N = s->N; la.np = s->np; la.latent_mode = s->latent_mode;
     la.x = s->x; la.u = s->u; la.p = s->p; la.dt = s->dt;
@@ -410,10 +343,10 @@ static int step_enqueue(sdfnmpc_solver* s) {
 }
 
 extern "C" int sdfnmpc_solver_step(sdfnmpc_solver* s) {
-    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
-    SolverDevice sd(s->device);
+    if (!s) return fail(SDFNMPC_E_ARG, "NULL solver");
+    ScopedDevice sd(s->device);
     if (int rc = step_enqueue(s)) return rc;
-    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // u0, status, iters
+    HIPCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // u0, status, iters
     s->pending = true;
     return SDFNMPC_OK;
 }
@@ -472,13 +405,13 @@ struct RolloutPlan {
 
 static int rollout_clock(double t0, double dt) {
     if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
+        return fail(SDFNMPC_E_ARG, "rollout: the scene clock needs a finite t0 and a finite dt >= 0");
     return SDFNMPC_OK;
 }
 
 static int rollout_schedule(int every, int phase) {
     if (every < 1 || phase < 0)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
+        return fail(SDFNMPC_E_ARG, "rollout: perceive needs every >= 1 and phase >= 0");
     return SDFNMPC_OK;
 }
 
@@ -488,34 +421,34 @@ static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, Rollou
     sdfn::PlantArgs& pa = pl.pa;
     sdfnmpc_ref_args& ra = pl.ra;
     VehicleRun& vr = pl.vr;
-    if (a->steps < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
-    if (!a->x_log || !a->u_log) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: x_log and u_log are required");
-    if (int rc = sdfnmpc_plant_args_(&a->plant, s->B, s->x0, s->u0, s->x0, &pa)) return rc;
+    if (a->steps < 1) return fail(SDFNMPC_E_ARG, "rollout: steps must be >= 1");
+    if (!a->x_log || !a->u_log) return fail(SDFNMPC_E_ARG, "rollout: x_log and u_log are required");
+    if (int rc = plant_args(&a->plant, s->B, s->x0, s->u0, s->x0, pa)) return rc;
     if (!a->vehicle) {
         if (a->xhat_log || a->uapp_log)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: xhat_log and uapp_log need a vehicle");
+            return fail(SDFNMPC_E_ARG, "rollout: xhat_log and uapp_log need a vehicle");
         if (a->omega_log || a->rotor_log)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: omega_log and rotor_log need a vehicle with a body");
+            return fail(SDFNMPC_E_ARG, "rollout: omega_log and rotor_log need a vehicle with a body");
     } else {
         int neutral = 0;
-        if (int rc = sdfnmpc_vehicle_info_(a->vehicle, s->ctx, s->B, &neutral, &vr.x_true, &vr.scratch)) return rc;
+        if (int rc = vehicle_info(a->vehicle, s->ctx, s->B, &neutral, &vr.x_true, &vr.scratch)) return rc;
         if (a->frame0 < 0 || (long long)a->frame0 + a->steps > 2147483647LL)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the vehicle's frame counter (frame0 + steps) overflows or frame0 < 0");
+            return fail(SDFNMPC_E_ARG, "rollout: the vehicle's frame counter (frame0 + steps) overflows or frame0 < 0");
         vr.neutral = neutral != 0;
         vr.on = !vr.neutral;
-        vr.body = sdfnmpc_vehicle_has_body_(a->vehicle) != 0;
+        vr.body = a->vehicle->body;
         if (!vr.body && (a->omega_log || a->rotor_log))
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: omega_log and rotor_log need a vehicle with a body");
+            return fail(SDFNMPC_E_ARG, "rollout: omega_log and rotor_log need a vehicle with a body");
         if (vr.on)
-            if (int rc = sdfnmpc_vehicle_args_(a->vehicle, &pa, s->x0, &vr.va)) return rc;
+            if (int rc = vehicle_args(a->vehicle, pa, s->x0, vr.va)) return rc;
     }
     if (a->ref) {
         const int mode = a->ref->mode;
-        if (mode < 0 || mode > 2) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref->mode must be 0, 1 or 2");
-        if (!a->wrow) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref needs wrow");
+        if (mode < 0 || mode > 2) return fail(SDFNMPC_E_ARG, "rollout: ref->mode must be 0, 1 or 2");
+        if (!a->wrow) return fail(SDFNMPC_E_ARG, "rollout: ref needs wrow");
         if (mode == 0 && (a->n_wp < 1 || a->n_wp > sdfn::RP_MAX_WP || !a->wp_p || !a->wp_q))
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref mode 0 needs 1..32 waypoints (wp_p, wp_q)");
-        if (mode == 1 && !a->vw) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: ref mode 1 needs vw");
+            return fail(SDFNMPC_E_ARG, "rollout: ref mode 0 needs 1..32 waypoints (wp_p, wp_q)");
+        if (mode == 1 && !a->vw) return fail(SDFNMPC_E_ARG, "rollout: ref mode 1 needs vw");
         ra.B = s->B; ra.N = s->N; ra.np = s->np; ra.ny = s->ny; ra.n_wp = mode == 0 ? a->n_wp : 0;
         ra.x0 = s->x0; ra.x0_stride = 10;
         ra.wp_p = a->wp_p; ra.wp_q = a->wp_q; ra.vw = a->vw; ra.wrow = a->wrow;
@@ -527,35 +460,35 @@ static int rollout_args(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, Rollou
 // step k's plant call: the plant on x0, or the vehicle at frame frame0 + k (pa carries the log pointers either way)
 static int rollout_plant(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, sdfn::PlantArgs& pa, const VehicleRun& vr, int k) {
     pa.k = k;
-    if (!vr.on) return sdfnmpc_plant_launch_(s->ctx, &pa);
+    if (!vr.on) return plant_launch(s->ctx, pa);
     sdfn::VehicleArgs va = vr.va;
     va.P = pa;
     va.P.x = va.P.x_next = vr.x_true;
     va.frame = (unsigned)(a->frame0 + k);
     va.xhat_log = a->xhat_log;
     va.uapp_log = a->uapp_log;
-    if (vr.body) return sdfnmpc_vehicle_launch_body_(s->ctx, a->vehicle, &va, a->omega_log, a->rotor_log);
-    return sdfnmpc_vehicle_launch_(s->ctx, &va);
+    if (vr.body) return vehicle_launch_body(s->ctx, a->vehicle, va, a->omega_log, a->rotor_log);
+    return vehicle_launch(s->ctx, va);
 }
 
 // the poses of a perceiving step: the camera sees from where the vehicle is (its true state), the body pose the
 // controller is given comes from its estimate in x0 -- two launches, the unused pair of each into the vehicle's scratch
 static int rollout_pose(sdfnmpc_solver* s, const sdfn::ScenePoseArgs& spa, const VehicleRun& vr) {
-    if (!vr.on) return sdfnmpc_scene_pose_launch_(s->ctx, &spa);
+    if (!vr.on) return scene_pose_launch(s->ctx, spa);
     sdfn::ScenePoseArgs cam = spa, body = spa;
     cam.x = vr.x_true; cam.W_p_Bo = vr.scratch; cam.W_R_Bo = vr.scratch + (size_t)s->B * 3;
-    if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &cam)) return rc;
+    if (int rc = scene_pose_launch(s->ctx, cam)) return rc;
     body.W_p_C = vr.scratch; body.W_R_C = vr.scratch + (size_t)s->B * 3;
-    return sdfnmpc_scene_pose_launch_(s->ctx, &body);
+    return scene_pose_launch(s->ctx, body);
 }
 
 // after the last step: a neutral vehicle receives what its own kernel would have written
 static int rollout_end(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, const VehicleRun& vr) {
     if (!vr.neutral) return SDFNMPC_OK;
     const size_t B = s->B, K = a->steps;
-    SCHK(hipMemcpyAsync(vr.x_true, s->x0, B * 80, hipMemcpyDeviceToDevice, s->stream));
-    if (a->xhat_log) SCHK(hipMemcpyAsync(a->xhat_log, a->x_log, B * (K + 1) * 80, hipMemcpyDeviceToDevice, s->stream));
-    if (a->uapp_log) SCHK(hipMemcpyAsync(a->uapp_log, a->u_log, B * K * 32, hipMemcpyDeviceToDevice, s->stream));
+    HIPCHK(hipMemcpyAsync(vr.x_true, s->x0, B * 80, hipMemcpyDeviceToDevice, s->stream));
+    if (a->xhat_log) HIPCHK(hipMemcpyAsync(a->xhat_log, a->x_log, B * (K + 1) * 80, hipMemcpyDeviceToDevice, s->stream));
+    if (a->uapp_log) HIPCHK(hipMemcpyAsync(a->uapp_log, a->u_log, B * K * 32, hipMemcpyDeviceToDevice, s->stream));
     return SDFNMPC_OK;
 }
 
@@ -572,11 +505,10 @@ static void rollout_pack(const sdfnmpc_solver* s, int mode, const double* B_p_C,
 
 // the stages every perceiving flavour has: perc's schedule, the vehicle's pose pair, the render into img, the pack
 static int rollout_camera(sdfnmpc_solver* s, const sdfnmpc_perceive_args* pc, float* img, int mode, RolloutPlan& pl) {
-    if (int rc = sdfnmpc_scene_pose_args_(pc->B_p_C, pc->B_R_C, s->B, s->x0, pc->W_p_Bo, pc->W_R_Bo, pc->W_p_C, pc->W_R_C,
-                                          &pl.spa))
+    if (int rc = scene_pose_args(pc->B_p_C, pc->B_R_C, s->B, s->x0, pc->W_p_Bo, pc->W_R_Bo, pc->W_p_C, pc->W_R_C, pl.spa))
         return rc;
-    if (int rc = sdfnmpc_scene_render_args_(s->ctx, pc->scene, pc->scene_of, &pc->img, pc->h, pc->w, pc->scale, s->B,
-                                            pc->W_p_C, pc->W_R_C, img, &pl.sra))
+    if (int rc = scene_render_args(s->ctx, pc->scene, pc->scene_of, &pc->img, pc->h, pc->w, pc->scale, s->B, pc->W_p_C,
+                                   pc->W_R_C, img, pl.sra))
         return rc;
     pl.every = pc->every; pl.phase = pc->phase;
     pl.pose = RolloutPlan::POSE_VEHICLE;
@@ -589,9 +521,9 @@ static int rollout_camera(sdfnmpc_solver* s, const sdfnmpc_perceive_args* pc, fl
 static int rollout_sensor(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, const sdfnmpc_sensor_opts* sensor, float* img,
                           int h, int w, float* scratch, RolloutPlan& pl) {
     if ((long long)pl.phase + a->steps > 2147483647LL)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the sensor's frame counter (phase + steps) overflows");
+        return fail(SDFNMPC_E_ARG, "rollout: the sensor's frame counter (phase + steps) overflows");
     pl.sensor = sensor;
-    return sdfnmpc_sensor_args_(sensor, img, s->B, h, w, scratch, &pl.sna, &pl.ora);
+    return sensor_args(sensor, img, s->B, h, w, scratch, pl.sna, pl.ora);
 }
 
 // The one rollout loop: nothing in here refuses, the plan has been checked.  Per step [pose, render, sensor, encode,
@@ -603,7 +535,7 @@ static int rollout_run(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, Rollout
     pa.pts_log = a->pts_log;
     pa.status = s->status; pa.iters = s->iters;
     pa.p = s->p; pa.p_stride = (long long)(s->N + 1) * s->np;
-    SolverDevice sd(s->device);
+    ScopedDevice sd(s->device);
     for (int k = 0; k < a->steps; ++k) {
         // the time of step k, t0 + (phase + k) dt: the product is rounded on its own (a volatile temporary keeps the
         // compiler from contracting it into a fused multiply-add), as a host loop forms it
@@ -612,13 +544,13 @@ static int rollout_run(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, Rollout
         if (pl.scene_clock) s->sdf_src.t0 = t;
         if (pl.every > 0 && (k + pl.phase) % pl.every == 0) {  // a new view from the current state
             if (pl.pose == RolloutPlan::POSE_X0)
-                if (int rc = sdfnmpc_scene_pose_launch_(s->ctx, &pl.spa)) return rc;
+                if (int rc = scene_pose_launch(s->ctx, pl.spa)) return rc;
             if (pl.pose == RolloutPlan::POSE_VEHICLE)
                 if (int rc = rollout_pose(s, pl.spa, pl.vr)) return rc;
             if (pl.scene)
-                if (int rc = sdfnmpc_scene_render_launch_at_(s->ctx, pl.scene, &pl.sra, t)) return rc;
+                if (int rc = scene_render_launch(s->ctx, *pl.scene, pl.sra, t)) return rc;
             if (pl.sensor)  // what the camera makes of the exact image: frame = phase + k, as a chunked or host loop counts
-                if (int rc = sdfnmpc_sensor_launch_(s->ctx, &pl.sna, &pl.ora, pl.sensor->outlier_rm != 0, pl.phase + k))
+                if (int rc = sensor_launch(s->ctx, pl.sna, pl.ora, pl.sensor->outlier_rm != 0, pl.phase + k))
                     return rc;
             if (pl.vae)
                 if (int rc = sdfnmpc_vae_encode(s->ctx, pl.vae, &pl.vo, pl.cam, pl.latent, pl.latent64)) return rc;
@@ -637,7 +569,7 @@ static int rollout_run(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a, Rollout
         if (int rc = rollout_plant(s, a, pa, pl.vr, k)) return rc;
     }
     if (int rc = rollout_end(s, a, pl.vr)) return rc;
-    SCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
+    HIPCHK(hipMemcpyAsync(s->h_u0, s->u0, (size_t)s->B * 40, hipMemcpyDeviceToHost, s->stream));  // the last step's
     s->pending = true;
     return SDFNMPC_OK;
 }
@@ -659,23 +591,23 @@ extern "C" int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnm
 extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
                                                       const sdfnmpc_perceive_args* pc, double t0, double dt,
                                                       const sdfnmpc_sensor_opts* sensor, float* scratch) {
-    if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout");
-    if (sensor && !pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: a sensor model needs perception (perc)");
+    if (!s || !a) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout");
+    if (sensor && !pc) return fail(SDFNMPC_E_ARG, "rollout: a sensor model needs perception (perc)");
     if (int rc = rollout_clock(t0, dt)) return rc;
     RolloutPlan pl;
     pl.t0 = t0; pl.dt = dt;
     if (int rc = rollout_args(s, a, pl)) return rc;
     if (pc) {  // what sdfnmpc_vae_encode / sdfnmpc_pack_refs (mode -1) would refuse; the image goes into the camera buffer
         if (int rc = rollout_schedule(pc->every, pc->phase)) return rc;
-        if (!pc->scene || !pc->vae) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perception needs a scene and an encoder");
-        if (!sdfnmpc_scene_on_ctx_(pc->scene, s->ctx) || !sdfnmpc_vae_on_ctx_(pc->vae, s->ctx))
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the scene and the encoder must live on the solver's context");
+        if (!pc->scene || !pc->vae) return fail(SDFNMPC_E_ARG, "rollout: perception needs a scene and an encoder");
+        if (pc->scene->ctx != s->ctx || pc->vae->ctx != s->ctx)
+            return fail(SDFNMPC_E_ARG, "rollout: the scene and the encoder must live on the solver's context");
         if (!pc->images || !pc->latent || !pc->latent64 || !pc->W_p_Bo || !pc->W_R_Bo || !pc->W_p_C || !pc->W_R_C)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: perception needs its workspaces (images, latents, poses)");
+            return fail(SDFNMPC_E_ARG, "rollout: perception needs its workspaces (images, latents, poses)");
         const int L = sdfnmpc_vae_size_latent(pc->vae);
         if (L < 1 || 17 + L > s->np)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: the encoder's latent does not fit the parameter row");
-        if (!(pc->vae_opts.clip > 0.f)) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: vae_opts.clip must be > 0");
+            return fail(SDFNMPC_E_ARG, "rollout: the encoder's latent does not fit the parameter row");
+        if (!(pc->vae_opts.clip > 0.f)) return fail(SDFNMPC_E_ARG, "rollout: vae_opts.clip must be > 0");
         if (int rc = rollout_camera(s, pc, pc->images, -1, pl)) return rc;
         pl.pra.L = L; pl.pra.latent = pc->latent64;
         pl.vae = pc->vae; pl.cam = pc->images; pl.latent = pc->latent; pl.latent64 = pc->latent64;
@@ -689,26 +621,26 @@ extern "C" int sdfnmpc_solver_rollout_perceive_sensor(sdfnmpc_solver* s, const s
 
 extern "C" int sdfnmpc_solver_set_sdf_scene(sdfnmpc_solver* s, const sdfnmpc_scene* scene, const int* scene_of,
                                             double max_df, int predict) {
-    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
+    if (!s) return fail(SDFNMPC_E_ARG, "NULL solver");
     if (!scene) {  // back to the network, from either source; the scene time stays
         s->sdf_src = sdfnmpc_scene_sdf_opts{nullptr, nullptr, 0.0, s->sdf_src.t0, nullptr};
         s->has_img = false;
         return SDFNMPC_OK;
     }
     if (s->no_sdf)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_sdf_scene: no row or cost of the solver's constraint set reads the SDF");
-    if (!sdfnmpc_scene_on_ctx_(scene, s->ctx))
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_sdf_scene: the scene must live on the solver's context");
+        return fail(SDFNMPC_E_ARG, "set_sdf_scene: no row or cost of the solver's constraint set reads the SDF");
+    if (scene->ctx != s->ctx)
+        return fail(SDFNMPC_E_ARG, "set_sdf_scene: the scene must live on the solver's context");
     if (!(max_df > 0.0) || !std::isfinite(max_df))
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_sdf_scene: max_df must be positive and finite");
-    SolverDevice sd(s->device);
+        return fail(SDFNMPC_E_ARG, "set_sdf_scene: max_df must be positive and finite");
+    ScopedDevice sd(s->device);
     if (predict && !s->tau) {  // tau[0] = 0, tau[k] = tau[k-1] + dt[k-1], summed in that order
         std::vector<double> tau(s->N + 1, 0.0);
         for (int k = 1; k <= s->N; ++k) tau[k] = tau[k - 1] + s->h_dt[k - 1];
         double* d = nullptr;
-        SCHK(s->alloc(&d, (size_t)s->N + 1));
-        SCHK(hipMemcpyAsync(d, tau.data(), tau.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        SCHK(hipStreamSynchronize(s->stream));  // tau is a host temporary
+        HIPCHK(s->alloc(&d, (size_t)s->N + 1));
+        HIPCHK(hipMemcpyAsync(d, tau.data(), tau.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));  // tau is a host temporary
         s->tau = d;
     }
     const double t = s->sdf_src.t0;  // the scene time survives a change of source
@@ -718,12 +650,12 @@ extern "C" int sdfnmpc_solver_set_sdf_scene(sdfnmpc_solver* s, const sdfnmpc_sce
 }
 
 extern "C" int sdfnmpc_solver_set_sdf_image(sdfnmpc_solver* s, const sdfnmpc_img_sdf_opts* o) {
-    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
+    if (!s) return fail(SDFNMPC_E_ARG, "NULL solver");
     if (!o) return sdfnmpc_solver_set_sdf_scene(s, nullptr, nullptr, 0.0, 0);  // back to the network
     if (s->no_sdf)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_sdf_image: no row or cost of the solver's constraint set reads the SDF");
+        return fail(SDFNMPC_E_ARG, "set_sdf_image: no row or cost of the solver's constraint set reads the SDF");
     sdfn::ImgSdfArgs ia{};
-    if (int rc = sdfnmpc_img_sdf_args_(s->ctx, o, s->B, s->N, s->np, s->x, s->p, s->h, s->Jh, nullptr, &ia)) return rc;
+    if (int rc = img_sdf_args(s->ctx, o, s->B, s->N, s->np, s->x, s->p, s->h, s->Jh, nullptr, ia)) return rc;
     s->img_src = *o;
     s->has_img = true;
     s->sdf_src = sdfnmpc_scene_sdf_opts{nullptr, nullptr, 0.0, s->sdf_src.t0, nullptr};
@@ -731,29 +663,29 @@ extern "C" int sdfnmpc_solver_set_sdf_image(sdfnmpc_solver* s, const sdfnmpc_img
 }
 
 extern "C" int sdfnmpc_solver_set_scene_time(sdfnmpc_solver* s, double t) {
-    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
-    if (!std::isfinite(t)) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "set_scene_time: the time must be finite");
+    if (!s) return fail(SDFNMPC_E_ARG, "NULL solver");
+    if (!std::isfinite(t)) return fail(SDFNMPC_E_ARG, "set_scene_time: the time must be finite");
     s->sdf_src.t0 = t;
     return SDFNMPC_OK;
 }
 
 extern "C" int sdfnmpc_solver_rollout_scene_sdf(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
                                                 const sdfnmpc_pose_refresh_args* pose, int phase, double t0, double dt) {
-    if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_scene_sdf");
+    if (!s || !a) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_scene_sdf");
     if (!s->sdf_src.scene)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: no scene source set (sdfnmpc_solver_set_sdf_scene)");
+        return fail(SDFNMPC_E_ARG, "rollout_scene_sdf: no scene source set (sdfnmpc_solver_set_sdf_scene)");
     if (int rc = rollout_clock(t0, dt)) return rc;
-    if (phase < 0) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: phase must be >= 0");
+    if (phase < 0) return fail(SDFNMPC_E_ARG, "rollout_scene_sdf: phase must be >= 0");
     RolloutPlan pl;
     pl.t0 = t0; pl.dt = dt; pl.phase = phase;
     pl.scene_clock = true;  // from the first step on, so after the last refusal
     if (int rc = rollout_args(s, a, pl)) return rc;
     if (pose) {  // the camera pose the FOV rows read, from x0: the pose block, and what sdfnmpc_pack_refs (mode -2) would refuse
-        if (pose->every < 1) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: pose->every must be >= 1");
+        if (pose->every < 1) return fail(SDFNMPC_E_ARG, "rollout_scene_sdf: pose->every must be >= 1");
         if (!pose->W_p_Bo || !pose->W_R_Bo || !pose->W_p_C || !pose->W_R_C)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_scene_sdf: the pose refresh needs its workspaces");
-        if (int rc = sdfnmpc_scene_pose_args_(pose->B_p_C, pose->B_R_C, s->B, s->x0, pose->W_p_Bo, pose->W_R_Bo,
-                                              pose->W_p_C, pose->W_R_C, &pl.spa))
+            return fail(SDFNMPC_E_ARG, "rollout_scene_sdf: the pose refresh needs its workspaces");
+        if (int rc = scene_pose_args(pose->B_p_C, pose->B_R_C, s->B, s->x0, pose->W_p_Bo, pose->W_R_Bo, pose->W_p_C,
+                                     pose->W_R_C, pl.spa))
             return rc;
         pl.every = pose->every;
         pl.pose = RolloutPlan::POSE_X0;
@@ -765,10 +697,10 @@ extern "C" int sdfnmpc_solver_rollout_scene_sdf(sdfnmpc_solver* s, const sdfnmpc
 extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
                                                 const sdfnmpc_perceive_args* pc, double t0, double dt,
                                                 const sdfnmpc_sensor_opts* sensor, float* scratch) {
-    if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_image_sdf");
+    if (!s || !a) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_image_sdf");
     if (!s->has_img)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: no image source set (sdfnmpc_solver_set_sdf_image)");
-    if (sensor && !pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout: a sensor model needs perception (perc)");
+        return fail(SDFNMPC_E_ARG, "rollout_image_sdf: no image source set (sdfnmpc_solver_set_sdf_image)");
+    if (sensor && !pc) return fail(SDFNMPC_E_ARG, "rollout: a sensor model needs perception (perc)");
     if (int rc = rollout_clock(t0, dt)) return rc;
     RolloutPlan pl;
     pl.t0 = t0; pl.dt = dt;
@@ -776,14 +708,14 @@ extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc
     const sdfnmpc_img_sdf_opts& src = s->img_src;
     if (pc) {  // re-imaging: rendered into the source itself; NULL keeps the image and the pose as set
         if (int rc = rollout_schedule(pc->every, pc->phase)) return rc;
-        if (!pc->scene || !sdfnmpc_scene_on_ctx_(pc->scene, s->ctx))
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging needs a scene on the solver's context");
+        if (!pc->scene || pc->scene->ctx != s->ctx)
+            return fail(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging needs a scene on the solver's context");
         if (pc->h != src.H || pc->w != src.W)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: the render size must equal the source's H x W");
+            return fail(SDFNMPC_E_ARG, "rollout_image_sdf: the render size must equal the source's H x W");
         if (src.img_of)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging renders one image per instance (img_of must be NULL)");
+            return fail(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging renders one image per instance (img_of must be NULL)");
         if (!pc->W_p_Bo || !pc->W_R_Bo || !pc->W_p_C || !pc->W_R_C)
-            return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging needs the pose workspaces");
+            return fail(SDFNMPC_E_ARG, "rollout_image_sdf: re-imaging needs the pose workspaces");
         float* img = const_cast<float*>(src.images);
         if (int rc = rollout_camera(s, pc, img, -2, pl)) return rc;
         pl.src = &src; pl.pool = !src.is_signed;
@@ -796,33 +728,33 @@ extern "C" int sdfnmpc_solver_rollout_image_sdf(sdfnmpc_solver* s, const sdfnmpc
 extern "C" int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnmpc_rollout_args* a,
                                                   const sdfnmpc_perceive_args* pc, double t0, double dt,
                                                   const sdfnmpc_sensor_opts* sensor, float* scratch, sdfnmpc_vae_dec* dec) {
-    if (!s || !a) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_image_recon");
+    if (!s || !a) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_solver_rollout_image_recon");
     if (!s->has_img)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: no image source set (sdfnmpc_solver_set_sdf_image)");
-    if (!pc) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: perception (perc) is required");
-    if (!dec) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: no decoder");
+        return fail(SDFNMPC_E_ARG, "rollout_image_recon: no image source set (sdfnmpc_solver_set_sdf_image)");
+    if (!pc) return fail(SDFNMPC_E_ARG, "rollout_image_recon: perception (perc) is required");
+    if (!dec) return fail(SDFNMPC_E_ARG, "rollout_image_recon: no decoder");
     if (int rc = rollout_clock(t0, dt)) return rc;
     RolloutPlan pl;
     pl.t0 = t0; pl.dt = dt;
     if (int rc = rollout_args(s, a, pl)) return rc;
     const sdfnmpc_img_sdf_opts& src = s->img_src;
     if (int rc = rollout_schedule(pc->every, pc->phase)) return rc;
-    if (!pc->scene || !sdfnmpc_scene_on_ctx_(pc->scene, s->ctx))
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: re-imaging needs a scene on the solver's context");
-    if (!pc->vae || !sdfnmpc_vae_on_ctx_(pc->vae, s->ctx) || !sdfnmpc_vae_dec_on_ctx_(dec, s->ctx))
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: the encoder and the decoder must live on the solver's context");
+    if (!pc->scene || pc->scene->ctx != s->ctx)
+        return fail(SDFNMPC_E_ARG, "rollout_image_recon: re-imaging needs a scene on the solver's context");
+    if (!pc->vae || pc->vae->ctx != s->ctx || dec->ctx != s->ctx)
+        return fail(SDFNMPC_E_ARG, "rollout_image_recon: the encoder and the decoder must live on the solver's context");
     if (sdfnmpc_vae_size_latent(pc->vae) != sdfnmpc_vae_dec_size_latent(dec))
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: the encoder and the decoder have different latent sizes");
+        return fail(SDFNMPC_E_ARG, "rollout_image_recon: the encoder and the decoder have different latent sizes");
     if (pc->h != src.H || pc->w != src.W)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: the render size must equal the source's H x W");
+        return fail(SDFNMPC_E_ARG, "rollout_image_recon: the render size must equal the source's H x W");
     if (src.img_of)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: re-imaging renders one image per instance (img_of must be NULL)");
+        return fail(SDFNMPC_E_ARG, "rollout_image_recon: re-imaging renders one image per instance (img_of must be NULL)");
     if (!pc->images || !pc->latent || !pc->W_p_Bo || !pc->W_R_Bo || !pc->W_p_C || !pc->W_R_C)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: perception needs its workspaces (camera images, latent, poses)");
+        return fail(SDFNMPC_E_ARG, "rollout_image_recon: perception needs its workspaces (camera images, latent, poses)");
     if (pc->images == src.images)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: the camera buffer must not be the source's images");
+        return fail(SDFNMPC_E_ARG, "rollout_image_recon: the camera buffer must not be the source's images");
     if (pc->img.is_depth && !pc->vae_opts.yz)
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "rollout_image_recon: a depth camera needs the Depth2Range table (vae_opts.yz)");
+        return fail(SDFNMPC_E_ARG, "rollout_image_recon: a depth camera needs the Depth2Range table (vae_opts.yz)");
     // rendered into the camera buffer, encoded, the reconstruction decoded into the source
     if (int rc = rollout_camera(s, pc, pc->images, -2, pl)) return rc;
     pl.vae = pc->vae; pl.cam = pc->images; pl.latent = pc->latent; pl.latent64 = pc->latent64;
@@ -835,12 +767,12 @@ extern "C" int sdfnmpc_solver_rollout_image_recon(sdfnmpc_solver* s, const sdfnm
 }
 
 extern "C" int sdfnmpc_solver_wait(sdfnmpc_solver* s, double* u0, int* status, int* iters) {
-    if (!s) return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "NULL solver");
-    SolverDevice sd(s->device);
-    SCHK(hipStreamSynchronize(s->stream));
+    if (!s) return fail(SDFNMPC_E_ARG, "NULL solver");
+    ScopedDevice sd(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
     s->arena_used = 0;  // every staged upload has landed
     if (!s->pending && (u0 || status || iters))
-        return sdfnmpc_solver_fail_(SDFNMPC_E_ARG, "sdfnmpc_solver_wait: no step was enqueued");
+        return fail(SDFNMPC_E_ARG, "sdfnmpc_solver_wait: no step was enqueued");
     s->pending = false;
     if (u0) memcpy(u0, s->h_u0, (size_t)s->B * 32);
     if (status) memcpy(status, s->h_status, (size_t)s->B * 4);

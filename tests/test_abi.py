@@ -6,6 +6,8 @@ reporting) are exercised.
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -37,6 +39,17 @@ def test_sdfnmpc_exports_header(libs):
     missing = [f for f in fns if not hasattr(lib, f)]
     assert not missing, missing
     assert sorted(_lib.SYMBOLS) == fns
+
+
+def test_sdfnmpc_exports_nothing_but_the_header(libs):
+    """Every sdfnmpc_* symbol the library defines is declared in include/sdfnmpc.h: what the host files share among
+    themselves has C++ linkage (csrc/engine.h), so no undeclared C name can be bound across them by name alone."""
+    nm = shutil.which("nm") or shutil.which("llvm-nm")
+    if nm is None:
+        pytest.skip("no nm or llvm-nm to read the dynamic symbol table with")
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    names = [line.split()[-1] for line in out.splitlines() if line.strip()]
+    assert sorted(n for n in names if n.startswith("sdfnmpc_")) == header_functions("sdfnmpc.h")
 
 
 def test_sdf_l4c_exports_header(libs):
