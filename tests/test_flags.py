@@ -229,6 +229,75 @@ def test_phase_split_problems_converge_in_the_c_ipm(oracle_lib, B, N, kernel, se
         assert (r["status"] == 0).all(), (name, r["status"])
 
 
+def test_serial_edge_table_and_lds_formula():
+    """flag_sets' restatement of the serial kernel's LDS formula: the row counts it reads from FLAG_SETS are the
+    model's, and the long-horizon edges are the largest horizons that fit 160 KiB (the next one does not)."""
+    for name in F.FLAG_SETS:
+        q = F.quad(name)
+        assert F.qp_rows(name) == (q.nh, q.nhN, q.nsN, q.nhs), name
+    for name in ("default", "stability"):
+        n = F.serial_max_horizon(name)
+        assert F.qp_lds_doubles(n, F.qp_rows(name)) * 8 <= F.LDS_PER_CU < F.qp_lds_doubles(n + 1, F.qp_rows(name)) * 8
+    for name in ("no_sdf", "hard_all", "rec_feas_no_sdf_row"):  # the ABI's limit, not the LDS, bounds these
+        assert F.serial_max_horizon(name) == F.QP_N_MAX
+    Ns = [N for N, _ in F.SERIAL_EDGES]
+    assert Ns[:8] == [1, 2, 3, 4, 5, 8, 35, 64] and Ns[8] < Ns[9] == F.serial_max_horizon("default") < F.QP_N_MAX
+    assert all(N < 36 or N >= 64 for N in Ns)  # horizons AUTO gives the serial kernel at every batch size
+    assert sum(len(s) for _, s in F.SERIAL_EDGES) == 25
+
+
+@pytest.mark.parametrize("N,name", [(N, name) for N, sets in F.SERIAL_EDGES for name in sets])
+def test_serial_edges_references(oracle_lib, N, name):
+    """The references of test_gpu_flags.test_serial_qp_horizon_edges meet its bars among themselves, on that test's
+    problems (B = 16, flag_sets.serial_edge_seed).  The C IPM's serial recursion converges on every instance.  Up
+    to N = 8 every instance has an exact solution (the dense KKT solve + active-set polish), the C IPM's point is
+    inside the objective bound and the strong-convexity ball around it, and within SOL_ATOL of its du on >= 90 %
+    of the instances (test_gpu_qp._agree's share; a degenerate instance moves along its flat direction).  From
+    N = 35 on there is no dense solve: the serial recursion against the recursion over four segments (which the C
+    code, unlike rti_qp_seg.hip, runs at any horizon), to test_segment_edges_serial_vs_segmented_c_ipm's bars.
+    At the long horizons the same pair after one and two iterations is the yardstick of the GPU test's
+    per-iteration bar (flag_sets.SERIAL_STEP_ATOL_LONG, at least 10 x the measured flag_sets.SERIAL_STEP_SELF_LONG):
+    the references meet a tenth of that bar."""
+    import qp_oracle
+    B = 16
+    cfg, q, prob, x0, lin = _problem(oracle_lib, name, B, N, seed=F.serial_edge_seed(N, name))
+    r = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL)
+    assert (r["status"] == 0).all(), (r["status"], r["iters"])
+    if N <= 8:
+        close = 0
+        for b in range(B):
+            qq = qp_oracle.stage_qp({k: v[b] for k, v in lin.items() if k != "sdf"}, prob["x"][b], prob["u"][b], x0[b],
+                                    prob["yref"][b], prob["W"][b], prob["yN"][b], prob["WN"][b], prob["dt"], q, 10.0)
+            H, g, E, e, G, d = qp_oracle.dense_problem(qq)
+            ex = qp_oracle.polish_active_set(qq, qp_oracle.solve_dense(qq))
+            assert ex["max_violation"] < 1e-9 and ex["min_dual"] > -1e-9, (b, ex["max_violation"], ex["min_dual"])
+            sol = dict(dx=r["dx"][b], du=r["du"][b], sl=r["slack"][b][..., 0], su=r["slack"][b][..., 1])
+            z, zs = qp_oracle.z_of(qq, sol), qp_oracle.z_of(qq, ex)
+            Fz, Fs = 0.5 * z @ H @ z + g @ z, 0.5 * zs @ H @ zs + g @ zs
+            assert Fz - Fs <= qp_oracle.objective_bound(G.shape[0], QP_TOL, ex["lam_l1"], r["res"][b, 1]), (b, Fz - Fs)
+            n_xu = 10 * (N + 1) + 4 * N
+            mu = np.linalg.eigvalsh(H[:n_xu, :n_xu]).min()
+            assert np.linalg.norm(z[:n_xu] - zs[:n_xu]) <= np.sqrt(2 * max(Fz - Fs, 0.0) / mu) + 1e-6
+            close += np.abs(sol["du"] - ex["du"]).max() <= SOL_ATOL
+        print(f"\nserial edge N={N} {name}: {close} of {B} within {SOL_ATOL:g} of the exact du, iters {r['iters'].tolist()}")
+        assert close >= 0.9 * B
+        return
+    s = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, start=dict(seg=4))
+    assert (s["status"] == 0).all(), s["status"]
+    assert np.abs(r["iters"] - s["iters"]).max() <= 1, (r["iters"], s["iters"])
+    gap = np.abs(r["du"] - s["du"]).max(axis=(1, 2))
+    print(f"\nserial edge N={N} {name}: serial vs 4 segments, worst |du - du| {gap.max():.2e}, iters {r['iters'].tolist()}")
+    assert (gap <= 5e-6).mean() >= 0.9, gap
+    if N >= F.SERIAL_LONG_N:
+        for it in (1, 2):
+            a = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, max_iter=it)
+            b = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, max_iter=it, start=dict(seg=4))
+            self_err = np.abs(a["du"] - b["du"]).max()
+            print(f"  max_iter={it}: serial vs 4 segments |du - du| = {self_err:.3e}, |du| max {np.abs(a['du']).max():.3e}")
+            assert (a["iters"] == it).all() and (a["status"] == 1).all()
+            assert 10 * self_err <= F.SERIAL_STEP_ATOL_LONG
+
+
 @pytest.mark.parametrize("N,P", [(N, P) for N, _, P in F.SEG_EDGES])
 def test_segment_edges_serial_vs_segmented_c_ipm(oracle_lib, N, P):
     """The references of test_gpu_flags.test_segmented_qp_horizon_and_segment_edges meet its bars among

@@ -157,13 +157,129 @@ def test_segmented_qp_horizon_and_segment_edges(gpu_ctx, oracle_lib, monkeypatch
               n_exact=1 if N >= 47 else 2, nseg=nseg)
 
 
-def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_frac=1.0, n_exact=None, nseg=4):
+def _solve_again(gpu_ctx, w, B, N, du0=None, **opts):
+    """Another serial-kernel solve on the buffers of a _check_qp run (du0: the du buffer's entry values)."""
+    import torch
+    t = w["t"]
+    for k in ("dx", "du", "slack", "res"):
+        t[k].fill_(float("nan"))
+    if du0 is not None:
+        t["du"].copy_(torch.from_numpy(np.ascontiguousarray(du0)))
+    t["status"].fill_(-1)
+    t["iters"].fill_(-1)
+    torch.cuda.synchronize()
+    gpu_ctx.set_qp_kernel("serial")
+    try:
+        _lib.qp_solve(gpu_ctx, _lib.qp_opts(w["q"], tol=QP_TOL, **opts), B, N, t)
+        gpu_ctx.synchronize()
+    finally:
+        gpu_ctx.set_qp_kernel("auto")
+    return _np(t, ("dx", "du", "slack", "status", "iters", "res"))
+
+
+@pytest.mark.parametrize("N,name", [pytest.param(N, name, id=f"N{N}-{name}") for N, sets in F.SERIAL_EDGES for name in sets])
+def test_serial_qp_horizon_edges(gpu_ctx, oracle_lib, N, name):
+    """The serial kernel (rti_qp.hip, one wavefront per instance) where its control flow depends on the horizon
+    (flag_sets.SERIAL_EDGES: the single-trip branch at N + 1 <= 3 ring positions, a first and a last trip with
+    two, one and no dead tail position at N = 3, 4, 5, one middle trip at N = 8, AUTO's serial horizons next to
+    the segmented range, and the largest horizon whose instance fits a CU's LDS), on the GPU linearisation of
+    each set -- so linearize and the pack kernel run at 2 .. 195 nodes too -- to _check_qp's bars against the C
+    IPM's serial recursion.  Up to N = 8 every instance against the exact solution, at 35 and 64 the first one,
+    at the long horizons none (dense=False: the point itself is checked).  B = 16;
+    test_flags.test_serial_edges_references holds the references to these bars on the CPU.
+
+    Per-iteration pin: du after max_iter = 1 and 2 from a cold start equals the C IPM's at the same max_iter to
+    flag_sets.SERIAL_STEP_ATOL (1e-9; SERIAL_STEP_ATOL_LONG at the long horizons, from the reference's own
+    rounding there).  After one or two Newton steps no flat direction has opened: a wrong stage, a missed node
+    or a stale factor row shows at the size of the step.  Warm start at N = 1 and 3 (default): a zero du
+    reproduces the cold solve bit for bit, one iteration from a random du equals the C IPM's from the same du.
+    Determinism at N = 2, 4 and the largest default horizon: a second solve agrees bit for bit."""
+    B = 16
+    rows = F.qp_rows(name)
+    long_n = N >= F.SERIAL_LONG_N
+    # the LDS formula the table's horizons come from is the library's (its QP_RING * 168 term: a ring of 3)
+    assert _lib.load().sdfnmpc_qp_lds_bytes(N) == F.qp_lds_doubles(N, F.qp_rows("default")) * 8
+    opts = _lib.qp_opts(F.quad(name, _config(name, N)), tol=QP_TOL)
+    assert gpu_ctx.qp_capacity(N, opts) > 0
+    if long_n and F.serial_max_horizon(name) == N:
+        assert F.qp_lds_doubles(N + 1, rows) * 8 > F.LDS_PER_CU and gpu_ctx.qp_capacity(N + 1, opts) == 0
+    w = _check_qp(gpu_ctx, oracle_lib, name, B, N, "serial", need_active=False, n_exact=None if N <= 8 else 1,
+                  seed=F.serial_edge_seed(N, name), dense=not long_n)
+    q, prob, x0, lin, full = w["q"], w["prob"], w["x0"], w["lin"], w["got"]
+    atol = F.SERIAL_STEP_ATOL_LONG if long_n else F.SERIAL_STEP_ATOL
+    for it in (1, 2):
+        g = _solve_again(gpu_ctx, w, B, N, max_iter=it)
+        c = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, max_iter=it)
+        print(f"serial edge N={N} {name} max_iter={it}: |du - du_C| = {np.nan_to_num(np.abs(g['du'] - c['du']), nan=np.inf).max():.3e}, "
+              f"|du_C| max {np.abs(c['du']).max():.3e}")
+        assert (c["status"] == 1).all() and (c["iters"] == it).all()
+        assert (g["status"] == 1).all() and (g["iters"] == it).all(), (g["status"], g["iters"])
+        assert np.isfinite(g["res"]).all()
+        np.testing.assert_allclose(g["du"], c["du"], rtol=0, atol=atol)
+    if name == "default" and N in (1, 3):
+        g = _solve_again(gpu_ctx, w, B, N, du0=np.zeros((B, N, 4)), warm_start=True)
+        for k in ("du", "dx", "iters", "status"):
+            np.testing.assert_array_equal(g[k], full[k], err_msg=k)
+        du_ws = np.random.default_rng(14).normal(0, 0.1, (B, N, 4))
+        g = _solve_again(gpu_ctx, w, B, N, du0=du_ws, warm_start=True, max_iter=1)
+        c = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, max_iter=1, du_ws=du_ws)
+        assert np.abs(c["du"] - oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, max_iter=1)["du"]).max() > 1e-3  # the start is live
+        np.testing.assert_allclose(g["du"], c["du"], rtol=0, atol=F.SERIAL_STEP_ATOL)
+    if N in (2, 4) or (name == "default" and long_n):
+        g = _solve_again(gpu_ctx, w, B, N)
+        for k in ("du", "dx", "slack", "iters", "status", "res"):
+            np.testing.assert_array_equal(g[k], full[k], err_msg=k)
+
+
+def test_serial_qp_upper_end_refusals(gpu_ctx, oracle_lib):
+    """The upper end of the serial kernel's horizon range.  The default rows at the first horizon that does not
+    fit a CU's LDS and at the ABI's largest, 200: qp_solve and rti_prepare refuse (SDFNMPC_E_UNSUPPORTED, -4,
+    "horizon too long") with nothing enqueued -- every output buffer keeps its fill -- and qp_capacity is 0.
+    no_sdf (no stage row) fits at 200: solved, status 0, du within ORC_ATOL of the C IPM.  N = 201 and N = 0 are
+    argument errors (SDFNMPC_E_ARG, -1)."""
+    B = 4
+    for N in (F.serial_max_horizon("default") + 1, F.QP_N_MAX):
+        cfg, q, prob, x0, t = _setup(gpu_ctx, "default", B, N, seed=12)
+        opts = _lib.qp_opts(q, tol=QP_TOL)
+        assert gpu_ctx.qp_capacity(N, opts) == 0
+        with pytest.raises(_lib.SdfnmpcError, match=r"error -4: .*horizon too long"):
+            _lib.rti_prepare(gpu_ctx, _net(gpu_ctx, q), _lib.quad_model(cfg, q), opts, B, N, q.np, t)
+        with pytest.raises(_lib.SdfnmpcError, match=r"error -4: .*horizon too long"):
+            _lib.qp_solve(gpu_ctx, opts, B, N, t)
+        gpu_ctx.synchronize()
+        got = _np(t, OUT)
+        assert all(np.isnan(got[k]).all() for k in OUT if k not in ("status", "iters")), "a refused call wrote an output"
+        assert (got["status"] == -1).all() and (got["iters"] == -1).all()
+    for N in (F.QP_N_MAX + 1, 0):  # (the buffers of the last setup: the horizon is refused before anything is read)
+        with pytest.raises(_lib.SdfnmpcError, match="error -1: "):
+            _lib.qp_solve(gpu_ctx, opts, B, N, t)
+    N = F.QP_N_MAX
+    assert F.serial_max_horizon("no_sdf") == N
+    cfg, q, prob, x0, t = _setup(gpu_ctx, "no_sdf", B, N, seed=12)
+    opts = _lib.qp_opts(q, tol=QP_TOL)
+    assert gpu_ctx.qp_capacity(N, opts) > 0 and gpu_ctx.qp_kernel(N, B, opts) == "serial"
+    _lib.linearize(gpu_ctx, None, _lib.quad_model(cfg, q), B, N, q.np, t, nyN=q.nyN, no_sdf=True)
+    _lib.qp_solve(gpu_ctx, opts, B, N, t)
+    gpu_ctx.synchronize()
+    got = _np(t, OUT)
+    c = oracle_lib.qp_ipm_batch({k: got[k] for k in LIN}, prob, x0, q, tol=QP_TOL)
+    assert (c["status"] == 0).all() and (got["status"] == 0).all(), (got["status"], got["iters"])
+    assert np.abs(got["iters"] - c["iters"]).max() <= 1
+    np.testing.assert_allclose(got["du"], c["du"], rtol=0, atol=ORC_ATOL)
+    _check_point(prob, x0, {k: got[k] for k in LIN}, q, got)
+
+
+def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_frac=1.0, n_exact=None, nseg=4, seed=12,
+              dense=True):
     """n_exact: the exact solution (a dense KKT solve, ~2 s per instance at N = 40) for the first n_exact
     instances and every instance whose du is off the C IPM's by more than the bar (None: all).  nseg: the
-    segments of the segmented kernel at this N (the C IPM runs lqr_seg over the same partition)."""
+    segments of the segmented kernel at this N (the C IPM runs lqr_seg over the same partition).  dense=False
+    (long horizons, where one dense solve takes a minute): no exact solution at all -- an instance off the C IPM
+    is held to _agree's m tol gap bound, and every instance's point to the x0 row, the linearised dynamics and
+    the input boxes directly.  Returns the problem, its device buffers and the C IPM's result (whole batch)."""
     import qp_oracle
     from test_gpu_qp import _agree
-    cfg, q, prob, x0, t = _setup(gpu_ctx, name, B, N, seed=12)
+    cfg, q, prob, x0, t = _setup(gpu_ctx, name, B, N, seed=seed)
     _lib.linearize(gpu_ctx, _net(gpu_ctx, q), _lib.quad_model(cfg, q), B, N, q.np, t, nyN=q.nyN, no_sdf=not q.need_sdf)
     opts = _lib.qp_opts(q, tol=QP_TOL)
     gpu_ctx.set_qp_kernel(kernel)
@@ -178,6 +294,7 @@ def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_f
     # the segmented kernel against the C IPM's segmented recursion (oracle/qp_ipm.c lqr_seg: the same
     # segments and couplings), the serial one against the serial recursion
     c = oracle_lib.qp_ipm_batch(lin, prob, x0, q, tol=QP_TOL, start=dict(seg=nseg) if kernel == "segmented" else None)
+    whole = dict(cfg=cfg, q=q, prob=prob, x0=x0, t=t, opts=opts, lin=lin, got=got, c=c)
     gap = np.abs(got["du"] - c["du"]).max(axis=(1, 2))[(c["status"] == 0) & (got["status"] == 0)]
     print(f"\n_check_qp {name} B={B} N={N} {kernel}" + (f" P={nseg}" if kernel == "segmented" else "") +
           f": worst |du - du_C| = {gap.max() if gap.size else float('nan'):.2e}, share within {ORC_ATOL:g}: "
@@ -197,12 +314,13 @@ def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_f
     assert (np.abs(got["iters"] - c["iters"]) <= 1).mean() >= iters_frac, (got["iters"], c["iters"])
     off = np.abs(got["du"] - c["du"]).max(axis=(1, 2)) > ORC_ATOL
     exact = {}
-    for b in range(B):
+    for b in range(B if dense else 0):
         if n_exact is None or b < n_exact or off[b]:
             qq = qp_oracle.stage_qp({k: v[b] for k, v in lin.items()}, prob["x"][b], prob["u"][b], x0[b], prob["yref"][b],
                                     prob["W"][b], prob["yN"][b], prob["WN"][b], prob["dt"], q, 10.0)
             exact[b] = (qq, qp_oracle.polish_active_set(qq, qp_oracle.solve_dense(qq)))
-    _agree(prob, x0, lin, q, got, c, atol=ORC_ATOL, lam_l1=[exact[b][1]["lam_l1"] if b in exact else None for b in range(B)])
+    _agree(prob, x0, lin, q, got, c, atol=ORC_ATOL,
+           lam_l1=[exact[b][1]["lam_l1"] if b in exact else None for b in range(B)] if dense else None)
     ok = np.abs(got["du"] - c["du"]).max(axis=(1, 2)) <= ORC_ATOL
     # dx accumulates du through the dynamics: 4x the du bar where du agrees
     assert (np.abs(got["dx"] - c["dx"]).max(axis=(1, 2))[ok] <= 4 * ORC_ATOL).all()
@@ -223,6 +341,21 @@ def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_f
         assert hard_active > 0
     # unused slack entries are zero: stage rows past nh, terminal rows past nsN
     assert (got["slack"][:, :N, q.nh:] == 0).all() and (got["slack"][:, N, q.nsN:] == 0).all()
+    if not dense:
+        _check_point(prob, x0, lin, q, got)
+    return whole
+
+
+def _check_point(prob, x0, lin, q, got):
+    """The returned point itself: the x0 row, the linearised dynamics and the input boxes (the bars of
+    test_gpu_qp.test_qp_full_size_feasibility_and_determinism)."""
+    dx, du = got["dx"], got["du"]
+    np.testing.assert_allclose(dx[:, 0], x0 - prob["x"][:, 0], rtol=0, atol=1e-12)
+    cc = lin["xn"] - prob["x"][:, 1:]
+    pred = np.einsum("bkji,bkj->bki", lin["AB"][:, :, :10], dx[:, :-1]) + np.einsum("bkji,bkj->bki", lin["AB"][:, :, 10:], du) + cc
+    np.testing.assert_allclose(dx[:, 1:], pred, rtol=0, atol=1e-9)
+    u_new = prob["u"] + du
+    assert (u_new >= np.asarray(q.lbu) - 1e-7).all() and (u_new <= np.asarray(q.ubu) + 1e-7).all()
 
 
 @pytest.mark.parametrize("name,B,N,kernel,seed", [
