@@ -844,6 +844,37 @@ int sdfnmpc_scene_render_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const 
 int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const double* points, const int* p_to_scene,
                               const double* times, long long n, double* out);
 
+/* ---- swept clearance: the minimum distance over a segment of space-time (csrc/scene_swept.hip) ----
+ * Segment j runs from (p0[j], t0[j]) to (p1[j], t1[j]): p(s) = p0 + s (p1 - p0), t(s) = t0 + s (t1 - t0), s in [0, 1],
+ * and D(s) is what sdfnmpc_scene_distance_at returns for the point p(s) at the time t(s).  The call returns the minimum
+ * of D over s with a certificate:
+ *   dmin [n]   the smallest value found, a value of D at an actual point
+ *   s [n]      the parameter of that point (the smaller one on a tie)
+ *   gap [n]    the true minimum lies in [dmin - gap, dmin]
+ *   evals [n]  evaluations of D used (int32)
+ * by a deterministic Lipschitz branch and bound on dyadic intervals.  D is Lipschitz in s with L = |p1 - p0| +
+ * V |t1 - t0|, where V bounds the speed of any surface point of any mover of the scene: the maximum over its movers of
+ * |v| + |omega| |amp| + |yaw_rate| rho in Euclidean norms (rho: 0 for a sphere, the half diagonal of a box, sqrt(r^2 +
+ * hz^2) for a cylinder), formed in fp64 when the scene is created and inflated by 1 + 1e-12; 0 for a set that is not
+ * dynamic.  sdfnmpc_scene_speed_bound copies V of the S scenes to out (host [S]).  An interval [a, b] of width w holds
+ * no value below lb = (D(a) + D(b) - L w) / 2; one with lb >= best - eps is dropped, any other is halved at its midpoint,
+ * the left half first, down to a width of 2^-20 and until max_evals evaluations are used.  gap = max(0, dmin - the
+ * smallest lb of any interval dropped), so gap <= eps when neither limit was met, and larger -- never wrong -- when one
+ * was.  Every loop's trip count is fixed by max_evals before it starts.  A zero-length segment of one time gives one
+ * evaluation, s = 0 and gap 0; a non-finite coordinate or time gives NaN in dmin, s and gap and 0 in evals for that
+ * segment alone; a scene without primitives gives +inf and gap 0.
+ * All arrays are device arrays; p_to_scene as for sdfnmpc_scene_distance (segment j -> scene); t0 and t1 may both be
+ * NULL (t = 0), and a set that is not dynamic does not read them; s, gap and evals may be NULL.  The kernels are
+ * "scene_swept", "scene_swept_dyn", "scene_swept_grid" and "scene_swept_mixed" in sdfnmpc_ctx_kernel_stats, one thread
+ * per segment over the device functions of the distance kernels.  fp64, asynchronous; n == 0 is a no-op.
+ * SDFNMPC_E_ARG (nothing launched, no output written): NULL ctx, scene, p0, p1 or dmin, n < 0 or beyond 2^31 - 1, NULL
+ * p_to_scene with n % S != 0, one of t0 and t1 NULL alone, eps not finite or below 1e-6, max_evals outside 2..65536, a
+ * scene of another context. */
+int sdfnmpc_scene_swept_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scene* scene, const double* p0, const double* p1,
+                                 const int* p_to_scene, const double* t0, const double* t1, long long n, double eps,
+                                 int max_evals, double* dmin, double* s, double* gap, int* evals);
+int sdfnmpc_scene_speed_bound(const sdfnmpc_scene* scene, double* out);
+
 /* ---- scenes of many primitives: a uniform-grid index (csrc/scene_grid.hip) ----
  * sdfnmpc_scene_create_large is sdfnmpc_scene_create for S scenes of 0..SDFNMPC_SCENE_LARGE_MAX_PRIMS static
  * primitives each (the same kinds, checks and fp32 rounding; no motion records), with a uniform grid per scene built

@@ -49,6 +49,7 @@ SYMBOLS = [
     "sdfnmpc_scene_create_large", "sdfnmpc_scene_is_indexed", "sdfnmpc_scene_create_mixed",
     "sdfnmpc_vehicle_create", "sdfnmpc_vehicle_destroy", "sdfnmpc_vehicle_reset", "sdfnmpc_vehicle_begin",
     "sdfnmpc_vehicle_x_true", "sdfnmpc_plant_step_vehicle", "sdfnmpc_vehicle_set_body", "sdfnmpc_vehicle_body_state",
+    "sdfnmpc_scene_swept_distance", "sdfnmpc_scene_speed_bound",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -301,6 +302,8 @@ def load():
         "sdfnmpc_scene_create_mixed": (i, [vp, i, P(i), P(PrimC), d, P(i), P(PrimC), P(PrimMotionC), P(vp)]),
         "sdfnmpc_scene_render_at": (i, [vp, vp, vp, P(ImgOptsC), i, i, f, i, vp, vp, d, vp]),
         "sdfnmpc_scene_distance_at": (i, [vp, vp, vp, vp, vp, ll, vp]),
+        "sdfnmpc_scene_swept_distance": (i, [vp, vp, vp, vp, vp, vp, vp, ll, d, i, vp, vp, vp, vp]),
+        "sdfnmpc_scene_speed_bound": (i, [vp, P(d)]),
         "sdfnmpc_solver_rollout_perceive_at": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d]),
         "sdfnmpc_morph": (i, [vp, i, vp, i, i, i, vp, i, i, i, vp]),
         "sdfnmpc_outlier_rm": (i, [vp, i, f, vp, i, i, i, vp]),
@@ -909,6 +912,22 @@ def scene_distance_at(ctx: "Context", scene_h, points, p_to_scene, times, n: int
     """Enqueue sdfnmpc_scene_distance_at: times [n] device float64 (None: t = 0), the time of every point."""
     _check(load().sdfnmpc_scene_distance_at(ctx.h, scene_h, _ptr(points), _ptr(p_to_scene), _ptr(times), int(n),
                                             _ptr(out)))
+
+
+def scene_swept_distance(ctx: "Context", scene_h, p0, p1, p_to_scene, t0, t1, n: int, eps: float, max_evals: int, dmin,
+                         s=None, gap=None, evals=None):
+    """Enqueue sdfnmpc_scene_swept_distance: segments p0 -> p1 [n][3] device float64 between the times t0, t1 [n] (both
+    None: t = 0) -> dmin, s, gap [n] device float64 and evals [n] device int32 (the last three optional)."""
+    _check(load().sdfnmpc_scene_swept_distance(ctx.h, scene_h, _ptr(p0), _ptr(p1), _ptr(p_to_scene), _ptr(t0), _ptr(t1),
+                                               int(n), float(eps), int(max_evals), _ptr(dmin), _ptr(s), _ptr(gap),
+                                               _ptr(evals)))
+
+
+def scene_speed_bound(scene_h, S: int) -> np.ndarray:
+    """sdfnmpc_scene_speed_bound: [S] float64, the bound on the speed of any surface point of each scene's movers."""
+    out = np.zeros(int(S), dtype=np.float64)
+    _check(load().sdfnmpc_scene_speed_bound(scene_h, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
 
 
 def scene_pose(ctx: "Context", B_p_C, B_R_C, B: int, x, W_p_Bo, W_R_Bo, W_p_C, W_R_C):

@@ -2618,6 +2618,27 @@ static void scene_dyn_fill(ScenePrimDyn& y, const sdfnmpc_prim* p, const sdfnmpc
     y.yaw_rate = m.yaw_rate; y.omega = m.omega; y.phase = m.phase;
 }
 
+// A bound on the speed of any surface point of a filled record, |v| + |omega| |amp| + |yaw_rate| rho in Euclidean norms:
+// the centre's speed plus the yaw's at the farthest point of the shape from its centre (rho: 0 for a sphere, the half
+// diagonal of a box, sqrt(r^2 + hz^2) for a cylinder).  The scene's distance at a fixed point changes no faster
+// (scene_swept.hip).
+static double scene_dyn_speed(const ScenePrimDyn& y) {
+    const double rho = y.kind == SDFNMPC_PRIM_SPHERE ? 0.0
+                       : y.kind == SDFNMPC_PRIM_BOX  ? std::hypot(y.h[0], y.h[1], y.h[2])
+                                                     : std::hypot(y.h[0], y.h[2]);
+    return std::hypot(y.v[0], y.v[1], y.v[2]) + std::fabs(y.omega) * std::hypot(y.amp[0], y.amp[1], y.amp[2]) +
+           std::fabs(y.yaw_rate) * rho;
+}
+
+// vmax [S] of the filled records hm [S][32], count[s] of them in use, inflated by 1 + 1e-12 over its own rounding
+static void scene_speed_bounds(const ScenePrimDyn* hm, int S, const int* count, double* vmax) {
+    for (int s = 0; s < S; ++s) {
+        double v = 0.0;
+        for (int i = 0; i < count[s]; ++i) v = std::max(v, scene_dyn_speed(hm[(size_t)s * SCENE_MAX_PRIMS + i]));
+        vmax[s] = v * (1.0 + 1e-12);
+    }
+}
+
 extern "C" int sdfnmpc_scene_create(sdfnmpc_ctx* ctx, int S, const int* count, const sdfnmpc_prim* prims,
                                     sdfnmpc_scene** out) {
     return sdfnmpc_scene_create_moving(ctx, S, count, prims, nullptr, out);
@@ -2642,7 +2663,8 @@ extern "C" int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* c
     bool dynamic = false;
     if (int rc = scene_motion_check(motion, total, &dynamic)) return rc;
     const size_t static_bytes = cnt_bytes + n * (sizeof(ScenePrimD) + sizeof(ScenePrimF));
-    std::vector<char> host(static_bytes + (dynamic ? n * sizeof(ScenePrimDyn) : 0), 0);
+    const size_t dyn_bytes = dynamic ? n * sizeof(ScenePrimDyn) : 0;  // then vmax [S]
+    std::vector<char> host(static_bytes + dyn_bytes + (dynamic ? (size_t)S * sizeof(double) : 0), 0);
     ScenePrimDyn* hm = dynamic ? (ScenePrimDyn*)(host.data() + static_bytes) : nullptr;
     static_assert((sizeof(ScenePrimD) + sizeof(ScenePrimF)) * SCENE_MAX_PRIMS % 16 == 0, "fp64 alignment of the motion block");
     int* hc = (int*)host.data();
@@ -2665,6 +2687,12 @@ extern "C" int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* c
             if (hm) scene_dyn_fill(hm[(size_t)s * SCENE_MAX_PRIMS + i], p, motion + (p - prims));
         }
     }
+    static_assert(sizeof(ScenePrimDyn) % 8 == 0, "fp64 alignment of the speed bounds");
+    std::vector<double> vmax((size_t)S, 0.0);
+    if (hm) {
+        scene_speed_bounds(hm, S, count, vmax.data());
+        std::memcpy(host.data() + static_bytes + dyn_bytes, vmax.data(), (size_t)S * sizeof(double));
+    }
     ScopedDevice sd(ctx->device);
     auto* sc = new sdfnmpc_scene();
     sc->device = ctx->device; sc->ctx = ctx; sc->S = S;
@@ -2678,7 +2706,11 @@ extern "C" int sdfnmpc_scene_create_moving(sdfnmpc_ctx* ctx, int S, const int* c
     char* d = (char*)sc->dmem;
     sc->dev = SceneDev{S, (const int*)d, (const ScenePrimF*)(d + cnt_bytes + n * sizeof(ScenePrimD)),
                        (const ScenePrimD*)(d + cnt_bytes)};
-    if (dynamic) sc->dyn = (const ScenePrimDyn*)(d + static_bytes);
+    sc->vmax = std::move(vmax);
+    if (dynamic) {
+        sc->dyn = (const ScenePrimDyn*)(d + static_bytes);
+        sc->dvmax = (const double*)(d + static_bytes + dyn_bytes);
+    }
     *out = sc;
     return SDFNMPC_OK;
 }
@@ -2814,7 +2846,9 @@ static int scene_create_indexed(sdfnmpc_ctx* ctx, int S, const int* count, const
     const size_t o_ci = up16(o_cs + cell_start.size() * sizeof(int));
     const size_t o_mc = up16(o_ci + cell_items.size() * sizeof(int)) + 16;  // the indexed set's image ends here
     const size_t o_dyn = up16(o_mc + (size_t)S * sizeof(int));
-    std::vector<char> host(mcount ? o_dyn + (size_t)S * SCENE_MAX_PRIMS * sizeof(ScenePrimDyn) : o_mc, 0);
+    const size_t o_vmax = o_dyn + (size_t)S * SCENE_MAX_PRIMS * sizeof(ScenePrimDyn);  // a mixed set's speed bounds [S]
+    std::vector<char> host(mcount ? o_vmax + (size_t)S * sizeof(double) : o_mc, 0);
+    std::vector<double> vmax((size_t)S, 0.0);
     if (mcount) {
         std::memcpy(host.data() + o_mc, mcount, (size_t)S * sizeof(int));
         ScenePrimDyn* hm = (ScenePrimDyn*)(host.data() + o_dyn);
@@ -2822,6 +2856,8 @@ static int scene_create_indexed(sdfnmpc_ctx* ctx, int S, const int* count, const
         for (int s = 0; s < S; ++s)
             for (int i = 0; i < mcount[s]; ++i, ++q)
                 scene_dyn_fill(hm[(size_t)s * SCENE_MAX_PRIMS + i], q, mmotion ? mmotion + (q - mprims) : nullptr);
+        scene_speed_bounds(hm, S, mcount, vmax.data());
+        std::memcpy(host.data() + o_vmax, vmax.data(), (size_t)S * sizeof(double));
     }
     std::memcpy(host.data(), count, (size_t)S * sizeof(int));
     std::memcpy(host.data() + o_hdr, hdr.data(), (size_t)S * sizeof(SceneGridHdr));
@@ -2851,9 +2887,11 @@ static int scene_create_indexed(sdfnmpc_ctx* ctx, int S, const int* count, const
     char* d = (char*)sc->dmem;
     sc->dev = SceneDev{S, (const int*)d, (const ScenePrimF*)(d + o_pf), (const ScenePrimD*)(d + o_pd),
                        (const SceneGridHdr*)(d + o_hdr), (const int*)(d + o_cs), (const int*)(d + o_ci)};
+    sc->vmax = std::move(vmax);
     if (mcount) {
         sc->mcount = (const int*)(d + o_mc);
         sc->dyn = (const ScenePrimDyn*)(d + o_dyn);
+        sc->dvmax = (const double*)(d + o_vmax);
     }
     *out = sc;
     return SDFNMPC_OK;
@@ -3032,6 +3070,53 @@ extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* 
         return SDFNMPC_OK;
     }
     HIPCHK(timed(ctx, "scene_dist", [&] { return launch_scene_distance(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+// the minimum of sdfnmpc_scene_distance_at over segments of space-time (scene_swept.hip), dispatched on the handle as
+// that function is; a set that is not dynamic does not read the times
+extern "C" int sdfnmpc_scene_swept_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const double* p0, const double* p1,
+                                            const int* p_to_scene, const double* t0, const double* t1, long long n,
+                                            double eps, int max_evals, double* dmin, double* s, double* gap, int* evals) {
+    if (!ctx || !sc) return fail(SDFNMPC_E_ARG, "scene_swept_distance: NULL context or scene");
+    if (sc->ctx != ctx) return fail(SDFNMPC_E_ARG, "scene_swept_distance: the scene lives on another context");
+    if (!p0 || !p1 || !dmin) return fail(SDFNMPC_E_ARG, "scene_swept_distance: NULL p0, p1 or dmin");
+    if (n < 0 || n > 2147483647LL) return fail(SDFNMPC_E_ARG, "scene_swept_distance: n out of range");
+    if (!p_to_scene && n % sc->S != 0)
+        return fail(SDFNMPC_E_ARG,
+                    "scene_swept_distance: without p_to_scene the segments must divide evenly among the scenes");
+    if ((t0 == nullptr) != (t1 == nullptr))
+        return fail(SDFNMPC_E_ARG, "scene_swept_distance: t0 and t1 go together (both NULL: t = 0)");
+    if (!std::isfinite(eps) || eps < 1e-6) return fail(SDFNMPC_E_ARG, "scene_swept_distance: eps must be finite and >= 1e-6");
+    if (max_evals < 2 || max_evals > 65536) return fail(SDFNMPC_E_ARG, "scene_swept_distance: max_evals must be 2..65536");
+    if (n == 0) return SDFNMPC_OK;
+    SceneSweptArgs a{};
+    a.sc = sc->dev; a.dyn = sc->dyn; a.mcount = sc->mcount; a.vmax = sc->dvmax;
+    a.p0 = p0; a.p1 = p1; a.p_to_scene = p_to_scene;
+    a.t0 = sc->dyn ? t0 : nullptr; a.t1 = sc->dyn ? t1 : nullptr;
+    a.n = n; a.per_scene = std::max(1LL, n / sc->S);
+    a.eps = eps; a.max_evals = max_evals;
+    a.dmin = dmin; a.s = s; a.gap = gap; a.evals = evals;
+    ScopedDevice sd(ctx->device);
+    if (a.sc.ghdr && sc->dyn) {
+        HIPCHK(timed(ctx, "scene_swept_mixed", [&] { return launch_scene_swept_mixed(a, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
+    if (a.sc.ghdr) {
+        HIPCHK(timed(ctx, "scene_swept_grid", [&] { return launch_scene_swept_grid(a, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
+    if (sc->dyn) {
+        HIPCHK(timed(ctx, "scene_swept_dyn", [&] { return launch_scene_swept_dyn(a, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
+    HIPCHK(timed(ctx, "scene_swept", [&] { return launch_scene_swept(a, ctx->stream); }));
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_speed_bound(const sdfnmpc_scene* sc, double* out) {
+    if (!sc || !out) return fail(SDFNMPC_E_ARG, "scene_speed_bound: NULL scene or output");
+    std::copy(sc->vmax.begin(), sc->vmax.end(), out);
     return SDFNMPC_OK;
 }
 

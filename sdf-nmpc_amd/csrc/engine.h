@@ -196,13 +196,15 @@ struct sdfnmpc_scene {
     int device = 0;
     const sdfnmpc_ctx* ctx = nullptr;
     int S = 0;
-    void* dmem = nullptr;  // count [S] | ScenePrimD [S][32] | ScenePrimF [S][32] | dynamic: ScenePrimDyn [S][32]
+    void* dmem = nullptr;  // count [S] | ScenePrimD [S][32] | ScenePrimF [S][32] | dynamic: ScenePrimDyn [S][32] | vmax [S]
     sdfn::SceneDev dev{};
     const sdfn::ScenePrimDyn* dyn = nullptr;  // non-NULL: a dynamic set (some primitive is oriented or moves)
     const int* mcount = nullptr;              // [S]: with dev.ghdr and dyn, the movers per scene of a mixed set
+    std::vector<double> vmax;                 // [S]: the bound on the speed of any surface point of a mover (0: none moves)
+    const double* dvmax = nullptr;            // the same on the device, at the end of the image of a set with dyn
     // an indexed set (sdfnmpc_scene_create_large; dev.ghdr != nullptr): count [S] | SceneGridHdr [S] | ScenePrimD [total]
     // | ScenePrimF [total] | cell_start | cell_items, every block at a multiple of 16 bytes; a mixed set
-    // (sdfnmpc_scene_create_mixed; dev.ghdr and dyn both non-NULL) appends mcount [S] | ScenePrimDyn [S][32]
+    // (sdfnmpc_scene_create_mixed; dev.ghdr and dyn both non-NULL) appends mcount [S] | ScenePrimDyn [S][32] | vmax [S]
 };
 
 namespace sdfn {

@@ -1,5 +1,5 @@
-// Device code shared by the scene kernels (scene.hip, scene_sdf.hip, scene_grid.hip): a primitive's frame, and the
-// per-primitive work of the three queries -- the ray's hit, the signed distance, the distance with its gradient.  The
+// Device code shared by the scene kernels (scene.hip, scene_sdf.hip, scene_grid.hip, scene_swept.hip): a primitive's
+// frame, and the per-primitive work of the queries -- the ray's hit, the signed distance, the distance with its gradient.  The
 // brute-force kernels and the grid kernels call the same functions, so that a query over a subset of the primitives
 // that holds the minimiser returns the bits of the query over all of them.  The same holds for a primitive with a
 // frame (frame_ray_hit, frame_distance, frame_sd_grad): the dynamic kernels and the mixed kernels of scene_grid.hip
@@ -292,10 +292,58 @@ __device__ __forceinline__ void frame_grad_world(const double* R, double gx, dou
     bz = dot3_pinned(R[6], gx, R[7], gy, R[8], gz);
 }
 
-// ---- the uniform grid of an indexed scene set (scene_grid.hip)
+// ---- the uniform grid of an indexed scene set (scene_grid.hip; the ring search also in scene_swept.hip)
 // the cell of a coordinate u = (v - org) * inv in cells, clamped into [0, n): NaN gives 0
 __device__ __forceinline__ int grid_cell(double u, int n) {
     return u >= (double)(n - 1) ? n - 1 : (u > 0.0 ? (int)u : 0);
+}
+
+// The ring search of a point: visit(i) for every primitive i listed in the block of cells around the point's cell
+// (clamped into the grid), the block grown by one cell per side and round, until bound() <= the smallest axis gap
+// from the point to a face of the block that is not on the grid's boundary.  bound() is what the caller still cares
+// to find something below: its best so far, or less.
+template <class Visit, class Bound>
+__device__ __forceinline__ void grid_ring_search(const SceneGridHdr& G, const int* cs, const int* items, double px,
+                                                 double py, double pz, Visit visit, Bound bound) {
+    const double p[3] = {px, py, pz};
+    int lo[3], hi[3], plo[3] = {1, 1, 1}, phi[3] = {0, 0, 0};  // the block, and the block already searched (empty)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = grid_cell((p[a] - G.org[a]) * G.inv, G.n[a]);
+    const int nx = G.n[0], ny = G.n[1];
+    const int rounds = max(G.n[0], max(G.n[1], G.n[2]));  // after that many the block is the grid
+    for (int r = 0; r <= rounds; ++r) {
+        for (int k = lo[2]; k <= hi[2]; ++k)
+            for (int j = lo[1]; j <= hi[1]; ++j) {
+                const int row = (k * ny + j) * nx;
+                const bool inner = k >= plo[2] && k <= phi[2] && j >= plo[1] && j <= phi[1];
+                // a run of cells along x is one run of the item list; inside the old block's rows only the two ends
+                if (!inner) {
+                    const int k1 = cs[row + hi[0] + 1];
+                    for (int q = cs[row + lo[0]]; q < k1; ++q) visit(items[q]);
+                } else {
+                    int k1 = cs[row + plo[0]];
+                    for (int q = cs[row + lo[0]]; q < k1; ++q) visit(items[q]);
+                    k1 = cs[row + hi[0] + 1];
+                    for (int q = cs[row + phi[0] + 1]; q < k1; ++q) visit(items[q]);
+                }
+            }
+        double gap = INFINITY;
+        bool grown = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            if (lo[a] > 0) gap = fmin(gap, p[a] - (G.org[a] + (double)lo[a] * G.cell));
+            if (hi[a] < G.n[a] - 1) gap = fmin(gap, (G.org[a] + (double)(hi[a] + 1) * G.cell) - p[a]);
+            grown = grown || lo[a] > 0 || hi[a] < G.n[a] - 1;
+        }
+        if (!grown || !(bound() > gap)) break;  // the whole grid, or nothing unseen below the bound (NaN ends it too)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            plo[a] = lo[a];
+            phi[a] = hi[a];
+            lo[a] = max(lo[a] - 1, 0);
+            hi[a] = min(hi[a] + 1, G.n[a] - 1);
+        }
+    }
 }
 
 }  // namespace sdfn

@@ -131,6 +131,26 @@ struct SceneSdfArgs {
     const int* mcount;       // [S]: the movers of a mixed set (SceneRenderDynArgs), or nullptr
 };
 
+// scene_swept.hip: the minimum of the scene's distance over n segments of space-time (p0, t0) -> (p1, t1), one lane each
+struct SceneSweptArgs {
+    SceneDev sc;
+    const ScenePrimDyn* dyn; // [S][SCENE_MAX_PRIMS], or nullptr: a set that is not dynamic (the times are not read)
+    const int* mcount;       // [S]: the movers of a mixed set (SceneRenderDynArgs), or nullptr
+    const double* vmax;      // [S]: the bound V on the speed of any surface point of the scene's movers (dynamic sets)
+    const double* p0;        // [n][3]
+    const double* p1;        // [n][3]
+    const int* p_to_scene;   // [n] or nullptr: segment j -> scene j / per_scene
+    const double* t0;        // [n], or nullptr together with t1: t = 0
+    const double* t1;        // [n]
+    long long n, per_scene;
+    double eps;              // an interval whose lower bound is within eps of the best value is not searched
+    int max_evals;           // evaluations of the distance per segment, >= 2
+    double* dmin;            // [n]: the smallest value found, at the parameter s
+    double* s;               // [n] or nullptr
+    double* gap;             // [n] or nullptr: the true minimum lies in [dmin - gap, dmin]
+    int* evals;              // [n] or nullptr: evaluations used
+};
+
 inline size_t scene_render_lds_bytes(int h, int w, int is_spherical) {
     return is_spherical ? (size_t)2 * ((size_t)h + (size_t)w) * sizeof(float) : 0;
 }
@@ -150,5 +170,10 @@ hipError_t launch_scene_sdf_rows_grid(const SceneSdfArgs& a, hipStream_t s);
 hipError_t launch_scene_render_mixed(const SceneRenderDynArgs& a, hipStream_t s);
 hipError_t launch_scene_distance_mixed(const SceneDistDynArgs& a, hipStream_t s);
 hipError_t launch_scene_sdf_rows_mixed(const SceneSdfArgs& a, hipStream_t s);
+// scene_swept.hip: one kernel per kind of set -- plain, dynamic, indexed, mixed -- over the distance functions above
+hipError_t launch_scene_swept(const SceneSweptArgs& a, hipStream_t s);
+hipError_t launch_scene_swept_dyn(const SceneSweptArgs& a, hipStream_t s);
+hipError_t launch_scene_swept_grid(const SceneSweptArgs& a, hipStream_t s);
+hipError_t launch_scene_swept_mixed(const SceneSweptArgs& a, hipStream_t s);
 
 }  // namespace sdfn

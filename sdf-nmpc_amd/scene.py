@@ -41,6 +41,13 @@ def _three(a, name):
     return a
 
 
+class Swept:
+    """What ``Scene.swept_distance`` returns, arrays [n]: dmin, s, gap (float64) and evals (int32)."""
+
+    def __init__(self, dmin, s, gap, evals):
+        self.dmin, self.s, self.gap, self.evals = dmin, s, gap, evals
+
+
 class Scene:
     """One scene (a list of primitives) or several (a list of lists) with ``scene_of`` [B], the scene of each
     instance; without ``scene_of`` every instance sees scene 0.  At most 32 primitives per scene; with ``grid=True``
@@ -292,6 +299,48 @@ class Scene:
         else:
             _lib.scene_distance_at(self.ctx, self.h, pts, p2s, times, n, out)
         return out.numpy()  # the copy waits for the launch
+
+    @property
+    def speed_bound(self):
+        """[S] float64: V of each scene, a bound on the speed of any surface point of any of its movers -- the maximum
+        of |v| + |omega| |amp| + |yaw_rate| rho (rho: 0 for a sphere, the half diagonal of a box, sqrt(r^2 + hz^2) for
+        a cylinder), inflated by 1 + 1e-12; 0 for a scene set that is not dynamic.  The scene's distance at a fixed
+        point changes no faster than V."""
+        return _lib.scene_speed_bound(self.h, self.S)
+
+    def swept_distance(self, p0, p1, p_to_scene=None, t0=None, t1=None, eps=1e-3, max_evals=4096):
+        """The minimum signed distance to the scene along segments of space-time: segment j runs from the world point
+        p0[j] at time t0[j] to p1[j] at t1[j] ([n, 3] and a scalar or [n] each; t0 and t1 both None: t = 0, one alone
+        is a ValueError; a scene that is not dynamic ignores them), p(s) = p0 + s (p1 - p0), t(s) = t0 + s (t1 - t0).
+        Returns a ``Swept`` of numpy arrays [n]: ``dmin`` the smallest distance found (the value of ``distance`` at
+        p(s), t(s)), ``s`` where, ``gap`` its certificate -- the true minimum over the segment lies in [dmin - gap, dmin]
+        -- and ``evals`` the distance evaluations used.  A Lipschitz branch and bound with the constant |p1 - p0| +
+        ``speed_bound`` |t1 - t0|: gap <= ``eps`` unless ``max_evals`` (2..65536) ran out or an interval reached
+        2^-20 of the segment, and then gap says by how much.  A segment with a non-finite coordinate or time gives
+        NaN (and 0 evals), the others are unaffected.  p_to_scene as for ``distance``."""
+        a0 = self._f64(p0, (-1, 3) if not hasattr(p0, "data_ptr") else tuple(p0.shape))
+        n = int(np.prod(a0.shape)) // 3
+        a1 = self._f64(p1, (n, 3))
+        p2s = None
+        if p_to_scene is not None:
+            a = np.ascontiguousarray(p_to_scene, dtype=np.int32).ravel()
+            if a.size != n or (n and (a.min() < 0 or a.max() >= self.S)):
+                raise ValueError(f"p_to_scene needs one entry in [0, {self.S}) per segment")
+            p2s = _lib.DeviceArray.from_numpy(self.ctx, a)
+        if (t0 is None) != (t1 is None):
+            raise ValueError("swept_distance: t0 and t1 go together (both None: t = 0)")
+        times = [None, None]
+        if t0 is not None:
+            for k, t in enumerate((t0, t1)):
+                a = np.asarray(t, dtype=np.float64)
+                a = np.full(n, float(a)) if a.ndim == 0 else np.ascontiguousarray(a).ravel()
+                if a.size != n:
+                    raise ValueError(f"t{k} needs one time per segment ({n}) or a scalar")
+                times[k] = _lib.DeviceArray.from_numpy(self.ctx, a)
+        out = Swept(*[_lib.DeviceArray(self.ctx, (n,), dt) for dt in (np.float64, np.float64, np.float64, np.int32)])
+        _lib.scene_swept_distance(self.ctx, self.h, a0, a1, p2s, times[0], times[1], n, eps, max_evals, out.dmin, out.s,
+                                  out.gap, out.evals)
+        return Swept(*[a.numpy() for a in (out.dmin, out.s, out.gap, out.evals)])  # the copies wait for the launch
 
     def close(self):
         if getattr(self, "h", None):
