@@ -924,6 +924,49 @@ int sdfnmpc_scene_create_mixed(sdfnmpc_ctx* ctx, int S, const int* count, const 
                                const int* mcount, const sdfnmpc_prim* mprims, const sdfnmpc_prim_motion* mmotion,
                                sdfnmpc_scene** out);
 
+/* ---- triangle-mesh scenes: mesh sets (csrc/scene_mesh.hip, csrc/mesh_bvh.h) ----
+ * sdfnmpc_scene_create_mesh makes S scenes, each a static triangle mesh behind a bounding-volume hierarchy built on the
+ * host inside the call (synchronous): nvert [S] and ntri [S] per scene, verts [sum of nvert][3] and tris [sum of
+ * ntri][3] scene after scene, the indices local to their scene.  Vertices are rounded to fp32 once, as primitives are;
+ * normals and boxes are formed in fp64 from the rounded values.  A scene with no triangles is allowed (a miss
+ * everywhere, distance +inf).
+ * The hierarchy: top-down, split at the median of the triangle centroids along the longest axis of the centroid bounds,
+ * ordered by (centroid coordinate, triangle index), down to leaf_size triangles per leaf; nodes in depth-first preorder
+ * with a skip index each, so the kernels walk it without a stack.  A box is the fp32 bounds of its fp32 vertices widened
+ * by R / 4096 (R: the scene's largest absolute coordinate); the kernels' results do not depend on the hierarchy, bit for
+ * bit (leaf_size = -1 is the brute-force yardstick through the same kernels).
+ * The handle is used like any other by sdfnmpc_scene_render(_at), sdfnmpc_scene_distance(_at),
+ * sdfnmpc_scene_swept_distance and every rollout that renders a scene; they dispatch on it (sdfnmpc_scene_is_mesh: 1,
+ * else 0) and launch "scene_render_mesh", "scene_dist_mesh" and "scene_swept_mesh" (sdfnmpc_ctx_kernel_stats).  A mesh
+ * set is static: times are ignored, sdfnmpc_scene_is_dynamic and sdfnmpc_scene_is_indexed are 0 and
+ * sdfnmpc_scene_speed_bound gives 0.
+ *   render    the pixel grid, pose rounding, values, clipping and scale of sdfnmpc_scene_render; fp32, one lane per pixel,
+ *             bitwise reproducible.  A mesh is a surface: hits are double-sided with t >= 0, and a camera inside a
+ *             closed mesh sees its inner walls -- there is no "camera inside sees zero" convention here.  The hit test
+ *             evaluates each edge with its endpoints in ascending vertex-index order and accepts inclusively, so no
+ *             ray passes between two triangles that share an edge (by index).
+ *   distance  fp64: the distance to the nearest triangle, ties between triangles to the lower index.  closed = 0: unsigned.
+ *             closed = 1: negative inside, by the sign of (p - c) . n at the closest point c for the angle-weighted
+ *             pseudonormal n of the feature c lies on (face, edge or vertex); a point on the surface counts as outside.
+ * SDFNMPC_E_ARG (nothing is allocated on the device): NULL ctx, nvert, ntri or out, S < 1, a negative count or one over
+ * the limits below, more than 2^24 triangles in the set, a non-finite vertex, an index outside [0, nvert[s]), a
+ * triangle whose area is zero after rounding, a leaf_size outside the values below, and with closed = 1 an edge that is
+ * not shared by exactly two triangles traversing it in opposite directions.
+ * SDFNMPC_E_UNSUPPORTED, nothing launched: a mesh set given to sdfnmpc_scene_sdf_rows, sdfnmpc_lin_args.sdf_scene or
+ * sdfnmpc_solver_set_sdf_scene.  Not built: a mesh as the controller's SDF source, movers beside a mesh, meshes mixed
+ * with primitives in one scene. */
+#define SDFNMPC_MESH_MAX_TRIS (1 << 20)  /* per scene */
+#define SDFNMPC_MESH_MAX_VERTS (1 << 21) /* per scene */
+typedef struct {
+    int leaf_size; /* 1..8 triangles per leaf; 0: the default (4); -1: no hierarchy, one leaf holding every
+                      triangle of the scene -- the brute-force yardstick through the same kernels */
+    int closed;    /* 0: open surfaces, unsigned distance; 1: every scene must be a closed, consistently oriented
+                      manifold (else SDFNMPC_E_ARG) and the distance is signed, negative inside */
+} sdfnmpc_mesh_opts;
+int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts, const int* ntri,
+                              const int* tris, const sdfnmpc_mesh_opts* opts, sdfnmpc_scene** out);
+int sdfnmpc_scene_is_mesh(const sdfnmpc_scene* scene);
+
 /* sdfnmpc_solver_rollout with perception inside the loop.  Before step k with (k + phase) % every == 0 it enqueues, on the
  * solver's stream and in this order: (a) sdfnmpc_scene_pose from the solver's x0 field; (b) sdfnmpc_scene_render of
  * every instance's scene from that camera pose; (c) sdfnmpc_vae_encode of the images; (d) sdfnmpc_pack_refs in mode -1

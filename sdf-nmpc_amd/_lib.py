@@ -50,6 +50,7 @@ SYMBOLS = [
     "sdfnmpc_vehicle_create", "sdfnmpc_vehicle_destroy", "sdfnmpc_vehicle_reset", "sdfnmpc_vehicle_begin",
     "sdfnmpc_vehicle_x_true", "sdfnmpc_plant_step_vehicle", "sdfnmpc_vehicle_set_body", "sdfnmpc_vehicle_body_state",
     "sdfnmpc_scene_swept_distance", "sdfnmpc_scene_speed_bound",
+    "sdfnmpc_scene_create_mesh", "sdfnmpc_scene_is_mesh",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -181,6 +182,10 @@ class PrimC(C.Structure):
     _fields_ = [("kind", C.c_int), ("a", C.c_double * 6)]
 
 
+class MeshOptsC(C.Structure):  # sdfnmpc_mesh_opts
+    _fields_ = [("leaf_size", C.c_int), ("closed", C.c_int)]
+
+
 class PrimMotionC(C.Structure):
     _fields_ = [("q", C.c_double * 4), ("yaw_rate", C.c_double), ("v", C.c_double * 3), ("amp", C.c_double * 3),
                 ("omega", C.c_double), ("phase", C.c_double)]
@@ -304,6 +309,8 @@ def load():
         "sdfnmpc_scene_distance_at": (i, [vp, vp, vp, vp, vp, ll, vp]),
         "sdfnmpc_scene_swept_distance": (i, [vp, vp, vp, vp, vp, vp, vp, ll, d, i, vp, vp, vp, vp]),
         "sdfnmpc_scene_speed_bound": (i, [vp, P(d)]),
+        "sdfnmpc_scene_create_mesh": (i, [vp, i, P(i), P(d), P(i), P(i), P(MeshOptsC), P(vp)]),
+        "sdfnmpc_scene_is_mesh": (i, [vp]),
         "sdfnmpc_solver_rollout_perceive_at": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d]),
         "sdfnmpc_morph": (i, [vp, i, vp, i, i, i, vp, i, i, i, vp]),
         "sdfnmpc_outlier_rm": (i, [vp, i, f, vp, i, i, i, vp]),
@@ -891,6 +898,23 @@ def scene_create_large(ctx: "Context", counts, prims, cell: float = 0.0):
     pr = _prims_c(prims)
     h = C.c_void_p()
     _check(load().sdfnmpc_scene_create_large(ctx.h, len(counts), cn, pr, float(cell), C.byref(h)))
+    return h
+
+
+def scene_create_mesh(ctx: "Context", verts, tris, leaf_size: int = 0, closed: bool = False):
+    """sdfnmpc_scene_create_mesh: one (verts [nv, 3] float64, tris [nt, 3] int32) pair per scene, the indices local to
+    the scene; leaf_size 1..8, 0 (the default) or -1 (no hierarchy); closed: signed distance, and the library checks
+    that every scene is a closed, consistently oriented manifold.  Returns the handle."""
+    vs = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3) for v in verts]
+    ts = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1, 3) for t in tris]
+    nv = (C.c_int * len(vs))(*[v.shape[0] for v in vs])
+    nt = (C.c_int * len(ts))(*[t.shape[0] for t in ts])
+    va = np.ascontiguousarray(np.concatenate(vs, 0)) if vs else np.zeros((0, 3))
+    ta = np.ascontiguousarray(np.concatenate(ts, 0)) if ts else np.zeros((0, 3), np.int32)
+    o = MeshOptsC(int(leaf_size), int(bool(closed)))
+    h = C.c_void_p()
+    _check(load().sdfnmpc_scene_create_mesh(ctx.h, len(vs), nv, va.ctypes.data_as(C.POINTER(C.c_double)), nt,
+                                            ta.ctypes.data_as(C.POINTER(C.c_int)), C.byref(o), C.byref(h)))
     return h
 
 

@@ -2929,6 +2929,107 @@ extern "C" int sdfnmpc_scene_create_mixed(sdfnmpc_ctx* ctx, int S, const int* co
     return scene_create_indexed(ctx, S, count, prims, cell, mixed ? mcount : nullptr, mprims, mmotion, out);
 }
 
+// Mesh sets (scene_mesh.hip): S static triangle meshes, each checked, rounded to fp32 and put behind a hierarchy here on
+// the host (mesh_bvh.h: the layout, the split rule, the boxes and their margin)
+extern "C" int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts, const int* ntri,
+                                         const int* tris, const sdfnmpc_mesh_opts* opts, sdfnmpc_scene** out) {
+    if (!ctx || !nvert || !ntri || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create_mesh");
+    *out = nullptr;
+    if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "mesh: S must be 1..2^20");
+    const sdfnmpc_mesh_opts o = opts ? *opts : sdfnmpc_mesh_opts{0, 0};
+    if (!(o.leaf_size == -1 || (o.leaf_size >= 0 && o.leaf_size <= MESH_LEAF_MAX)))
+        return fail(SDFNMPC_E_ARG, "mesh: leaf_size must be 1..8, 0 (the default) or -1 (no hierarchy)");
+    if (o.closed != 0 && o.closed != 1) return fail(SDFNMPC_E_ARG, "mesh: closed must be 0 or 1");
+    const int leaf = o.leaf_size == 0 ? MESH_LEAF_DEFAULT : o.leaf_size;
+    long long tv = 0, tt = 0;
+    for (int s = 0; s < S; ++s) {
+        if (nvert[s] < 0 || nvert[s] > MESH_MAX_VERTS)
+            return fail(SDFNMPC_E_ARG, "mesh: at most 2^21 vertices per scene (and no negative count)");
+        if (ntri[s] < 0 || ntri[s] > MESH_MAX_TRIS)
+            return fail(SDFNMPC_E_ARG, "mesh: at most 2^20 triangles per scene (and no negative count)");
+        tv += nvert[s];
+        tt += ntri[s];
+    }
+    if (tt > MESH_MAX_SET_TRIS) return fail(SDFNMPC_E_ARG, "mesh: more than 2^24 triangles in the set");
+    if ((tv > 0 && !verts) || (tt > 0 && !tris)) return fail(SDFNMPC_E_ARG, "mesh: NULL vertices or triangles");
+    // per scene: the check, the fp32 vertices, the hierarchy and the triangles in its order
+    std::vector<MeshHdr> hdr((size_t)S);
+    std::vector<MeshNode> nodes;
+    std::vector<MeshTriF> tf((size_t)tt);
+    std::vector<MeshTriD> td((size_t)tt);
+    std::vector<MeshTriN> tn(o.closed ? (size_t)tt : 0);
+    {
+        const double* v = verts;
+        const int* t = tris;
+        long long toff = 0;
+        std::vector<float> vf;
+        std::vector<double> fn;
+        std::vector<MeshTriN> pn;
+        MeshBvh bvh;
+        for (int s = 0; s < S; v += (size_t)nvert[s] * 3, t += (size_t)ntri[s] * 3, ++s) {
+            if (const char* why = mesh_check(v, nvert[s], t, ntri[s], o.closed != 0, vf)) return fail(SDFNMPC_E_ARG, why);
+            const float m = mesh_margin(vf.data(), nvert[s]);
+            mesh_bvh_build(vf.data(), t, ntri[s], leaf, m, bvh);
+            mesh_face_normals(vf.data(), t, ntri[s], fn);
+            if (o.closed) mesh_pseudonormals(vf.data(), nvert[s], t, ntri[s], fn, pn);
+            hdr[s] = MeshHdr{(int)nodes.size(), (int)bvh.nodes.size(), (int)toff, ntri[s], m, {0, 0, 0}};
+            nodes.insert(nodes.end(), bvh.nodes.begin(), bvh.nodes.end());
+            for (int k = 0; k < ntri[s]; ++k) {
+                const int g = bvh.order[k];
+                MeshTriF& F = tf[(size_t)toff + k];
+                MeshTriD& Dd = td[(size_t)toff + k];
+                F = MeshTriF{};
+                Dd = MeshTriD{};
+                for (int c = 0; c < 3; ++c)
+                    for (int a = 0; a < 3; ++a) {
+                        F.v[c * 3 + a] = vf[(size_t)t[g * 3 + c] * 3 + a];
+                        Dd.v[c * 3 + a] = (double)F.v[c * 3 + a];
+                    }
+                for (int a = 0; a < 3; ++a) F.n[a] = (float)fn[(size_t)g * 3 + a];
+                for (int c = 0; c < 3; ++c)
+                    if (t[g * 3 + c] > t[g * 3 + (c + 1) % 3]) F.flip |= 1 << c;
+                Dd.orig = g;
+                if (o.closed) tn[(size_t)toff + k] = pn[(size_t)g];
+            }
+            toff += ntri[s];
+        }
+    }
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_nodes = up16((size_t)S * sizeof(MeshHdr));
+    const size_t o_tf = up16(o_nodes + nodes.size() * sizeof(MeshNode));
+    const size_t o_td = up16(o_tf + tf.size() * sizeof(MeshTriF));
+    const size_t o_tn = up16(o_td + td.size() * sizeof(MeshTriD));
+    const size_t bytes = up16(o_tn + tn.size() * sizeof(MeshTriN)) + 16;
+    ScopedDevice sd(ctx->device);
+    auto* sc = new sdfnmpc_scene();
+    sc->device = ctx->device; sc->ctx = ctx; sc->S = S;
+    hipError_t e = hipMalloc(&sc->dmem, bytes);
+    char* d = (char*)sc->dmem;
+    auto put = [&](size_t off, const void* src, size_t n) {
+        if (e == hipSuccess && n) e = hipMemcpy(d + off, src, n, hipMemcpyHostToDevice);
+    };
+    put(0, hdr.data(), (size_t)S * sizeof(MeshHdr));
+    put(o_nodes, nodes.data(), nodes.size() * sizeof(MeshNode));
+    put(o_tf, tf.data(), tf.size() * sizeof(MeshTriF));
+    put(o_td, td.data(), td.size() * sizeof(MeshTriD));
+    put(o_tn, tn.data(), tn.size() * sizeof(MeshTriN));
+    if (e != hipSuccess) {
+        if (sc->dmem) (void)hipFree(sc->dmem);
+        delete sc;
+        return fail(SDFNMPC_E_HIP, std::string("mesh upload: ") + hipGetErrorString(e));
+    }
+    sc->dev = SceneDev{};
+    sc->dev.S = S;
+    sc->is_mesh = true;
+    sc->mesh = MeshDev{(const MeshHdr*)d, (const MeshNode*)(d + o_nodes), (const MeshTriF*)(d + o_tf),
+                       (const MeshTriD*)(d + o_td), o.closed ? (const MeshTriN*)(d + o_tn) : nullptr};
+    sc->vmax.assign((size_t)S, 0.0);
+    *out = sc;
+    return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_is_mesh(const sdfnmpc_scene* sc) { return sc && sc->is_mesh; }
+
 extern "C" int sdfnmpc_scene_is_indexed(const sdfnmpc_scene* sc) { return sc && sc->dev.ghdr; }
 
 extern "C" void sdfnmpc_scene_free(sdfnmpc_scene* sc) {
@@ -2983,6 +3084,12 @@ static int scene_render_static(sdfnmpc_ctx* ctx, const SceneRenderArgs& a) {
 
 // the scene at time t: a static set takes the launch above whatever t is, a dynamic one its own kernel
 int sdfn::scene_render_launch(sdfnmpc_ctx* ctx, const sdfnmpc_scene& sc, const SceneRenderArgs& a, double t) {
+    if (sc.is_mesh) {  // a mesh set is static: the time does not matter
+        const MeshRenderArgs ma{a, sc.mesh};
+        ScopedDevice sd(ctx->device);
+        HIPCHK(timed(ctx, "scene_render_mesh", [&] { return launch_scene_render_mesh(ma, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (!sc.dyn) return scene_render_static(ctx, a);
     const SceneRenderDynArgs da{a, sc.dyn, t, sc.mcount};
     ScopedDevice sd(ctx->device);
@@ -3055,6 +3162,11 @@ extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* 
     if (!points || !out) return fail(SDFNMPC_E_ARG, "scene_distance: NULL points or output");
     SceneDistArgs a{sc->dev, points, p_to_scene, n, std::max(1LL, n / sc->S), out};
     ScopedDevice sd(ctx->device);
+    if (sc->is_mesh) {  // a mesh set is static: the times do not matter
+        const MeshDistArgs ma{a, sc->mesh};
+        HIPCHK(timed(ctx, "scene_dist_mesh", [&] { return launch_scene_distance_mesh(ma, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (a.sc.ghdr && sc->dyn) {  // a mixed set: the grid plus movers at the points' times
         const SceneDistDynArgs da{a, sc->dyn, times, sc->mcount};
         HIPCHK(timed(ctx, "scene_dist_mixed", [&] { return launch_scene_distance_mixed(da, ctx->stream); }));
@@ -3098,6 +3210,11 @@ extern "C" int sdfnmpc_scene_swept_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scen
     a.eps = eps; a.max_evals = max_evals;
     a.dmin = dmin; a.s = s; a.gap = gap; a.evals = evals;
     ScopedDevice sd(ctx->device);
+    if (sc->is_mesh) {
+        a.mesh = sc->mesh;
+        HIPCHK(timed(ctx, "scene_swept_mesh", [&] { return launch_scene_swept_mesh(a, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (a.sc.ghdr && sc->dyn) {
         HIPCHK(timed(ctx, "scene_swept_mixed", [&] { return launch_scene_swept_mixed(a, ctx->stream); }));
         return SDFNMPC_OK;
@@ -3130,6 +3247,9 @@ int sdfn::scene_sdf_args(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int 
         return fail(SDFNMPC_E_ARG, "scene_sdf_rows: max_df must be positive and finite");
     if (!std::isfinite(o->t0)) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: the time t0 must be finite");
     if (o->scene->ctx != ctx) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: the scene lives on another context");
+    if (o->scene->is_mesh)
+        return fail(SDFNMPC_E_UNSUPPORTED, "scene_sdf_rows: a mesh set cannot be the SDF source (meshes are rendered and "
+                                           "measured, not linearised)");
     if (B > 0 && (!x || !p || !h || !Jh)) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: NULL x, p, h or Jh");
     SceneSdfArgs a{};
     a.sc = o->scene->dev; a.dyn = o->scene->dyn; a.mcount = o->scene->mcount; a.scene_of = o->scene_of;

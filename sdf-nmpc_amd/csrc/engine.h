@@ -205,6 +205,10 @@ struct sdfnmpc_scene {
     // an indexed set (sdfnmpc_scene_create_large; dev.ghdr != nullptr): count [S] | SceneGridHdr [S] | ScenePrimD [total]
     // | ScenePrimF [total] | cell_start | cell_items, every block at a multiple of 16 bytes; a mixed set
     // (sdfnmpc_scene_create_mixed; dev.ghdr and dyn both non-NULL) appends mcount [S] | ScenePrimDyn [S][32] | vmax [S]
+    // a mesh set (sdfnmpc_scene_create_mesh): MeshHdr [S] | MeshNode [nodes] | MeshTriF [tris] | MeshTriD [tris] | closed:
+    // MeshTriN [tris], every block at a multiple of 16 bytes; dev carries S alone, dyn and mcount stay NULL
+    bool is_mesh = false;
+    sdfn::MeshDev mesh{};
 };
 
 namespace sdfn {

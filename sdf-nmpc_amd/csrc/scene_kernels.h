@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mesh_bvh.h"
+
 namespace sdfn {
 
 constexpr int SCENE_MAX_PRIMS = 32;  // SDFNMPC_SCENE_MAX_PRIMS
@@ -68,6 +70,16 @@ struct SceneDev {
     const SceneGridHdr* ghdr;  // [S], or nullptr: not indexed (the brute-force kernels)
     const int* cell_start;
     const int* cell_items;
+};
+
+// A mesh set on the device (sdfnmpc_scene_create_mesh; scene_mesh.hip): S scenes of triangles behind a hierarchy each
+// (the layout and the build: mesh_bvh.h).  The arrays hold scene after scene; hdr[s] says where scene s lies in them.
+struct MeshDev {
+    const MeshHdr* hdr;      // [S]
+    const MeshNode* nodes;   // [sum of nnodes], preorder per scene; first is relative to the scene's tri_off
+    const MeshTriF* tf;      // [sum of ntri], in the hierarchy's order
+    const MeshTriD* td;      // [sum of ntri], the same order
+    const MeshTriN* tn;      // [sum of ntri], the same order; nullptr: an open set (unsigned distance)
 };
 
 struct SceneRenderArgs {
@@ -149,6 +161,17 @@ struct SceneSweptArgs {
     double* s;               // [n] or nullptr
     double* gap;             // [n] or nullptr: the true minimum lies in [dmin - gap, dmin]
     int* evals;              // [n] or nullptr: evaluations used
+    MeshDev mesh;            // a mesh set (launch_scene_swept_mesh); last: the other kernels' arguments stay where they were
+};
+
+// scene_mesh.hip: a mesh set's render and distance; r.sc / d.sc carry S only (count, pf, pd are not read)
+struct MeshRenderArgs {
+    SceneRenderArgs r;
+    MeshDev mesh;
+};
+struct MeshDistArgs {
+    SceneDistArgs d;
+    MeshDev mesh;
 };
 
 inline size_t scene_render_lds_bytes(int h, int w, int is_spherical) {
@@ -175,5 +198,9 @@ hipError_t launch_scene_swept(const SceneSweptArgs& a, hipStream_t s);
 hipError_t launch_scene_swept_dyn(const SceneSweptArgs& a, hipStream_t s);
 hipError_t launch_scene_swept_grid(const SceneSweptArgs& a, hipStream_t s);
 hipError_t launch_scene_swept_mixed(const SceneSweptArgs& a, hipStream_t s);
+// scene_mesh.hip, and scene_swept.hip's kernel over its distance function: the three queries of a mesh set
+hipError_t launch_scene_render_mesh(const MeshRenderArgs& a, hipStream_t s);
+hipError_t launch_scene_distance_mesh(const MeshDistArgs& a, hipStream_t s);
+hipError_t launch_scene_swept_mesh(const SceneSweptArgs& a, hipStream_t s);
 
 }  // namespace sdfn

@@ -1,0 +1,100 @@
+// Triangle-mesh scenes: the render and the distance of a mesh set (sdfnmpc_scene_create_mesh), each scene a static
+// triangle mesh behind a bounding-volume hierarchy that the host built once (mesh_bvh.h).  The swept clearance of a
+// mesh set is scene_swept.hip's kernel over mesh_distance.
+//
+//   scene_render_mesh_kernel    fp32, one pixel per lane: the pixel grid, pose rounding, range and depth values, clipping
+//                               at dmax, scale and block shape of scene_render_kernel; the nearest hit over the
+//                               scene's triangles by a stackless preorder walk (mesh_dev.h).  No atomics, no
+//                               cross-lane traffic: a pixel depends on its instance's pose and scene only, so the
+//                               image is bitwise reproducible and independent of the instance's place in the batch.
+//   scene_distance_mesh_kernel  fp64, one point per lane: the distance to the nearest triangle, unsigned for an open
+//                               set, signed by the pseudonormal of the nearest feature for a closed one.
+//
+// A mesh is a surface, not a solid: hits are double-sided (front and back faces) with t >= 0, and there is no "camera
+// inside sees zero" convention as the primitives have -- a camera inside a closed mesh sees its inner walls.  The hit
+// test is edge-consistent (mesh_dev.h), so no ray passes between two triangles that share an edge.  A scene without
+// triangles renders a miss everywhere and is at distance +inf.
+#include "mesh_dev.h"
+
+namespace sdfn {
+
+namespace {
+
+__global__ __launch_bounds__(SCENE_BLOCK) void scene_render_mesh_kernel(MeshRenderArgs D) {
+    extern __shared__ float tab[];  // spherical: col [2 W] | row [2 H], as in scene_render_kernel
+    __shared__ float pose[12];      // W_p_C | W_R_C, rounded to fp32 once per block
+    const SceneRenderArgs& A = D.r;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int s = A.scene_of ? min(max(A.scene_of[b], 0), A.sc.S - 1) : 0;  // clamped: never outside the scene set
+    if (tid < 3) pose[tid] = (float)A.W_p_C[(size_t)b * 3 + tid];
+    else if (tid < 12) pose[tid] = (float)A.W_R_C[(size_t)b * 9 + (tid - 3)];
+    const int w = A.W, h = A.H;
+    if (A.is_spherical) {
+        for (int t = tid; t < w + h; t += SCENE_BLOCK) {
+            const bool is_col = t < w;
+            const int i = is_col ? t : t - w;
+            const float f = 1.f - (float)(2 * i + 1) / (float)(is_col ? w : h);
+            const float ang = (is_col ? A.hfov : A.vfov) * f;
+            float* dst = is_col ? tab + 2 * t : tab + 2 * w + 2 * i;
+            dst[0] = cosf(ang);
+            dst[1] = sinf(ang);
+        }
+    }
+    __syncthreads();
+    const long long pix = (long long)blockIdx.x * SCENE_BLOCK + tid;
+    if (pix >= (long long)h * w) return;
+    const int v = (int)(pix / w), u = (int)(pix - (long long)v * w);
+
+    // unit ray direction in the camera frame, then in the world frame
+    float cx, cy, cz;
+    if (A.is_spherical) {
+        const float ca = tab[2 * u], sa = tab[2 * u + 1], ce = tab[2 * w + 2 * v], se = tab[2 * w + 2 * v + 1];
+        cx = ce * ca;
+        cy = ce * sa;
+        cz = se;
+    } else {
+        const float ty = fmaf(A.ty1, (float)u, A.ty0), tz = fmaf(A.tz1, (float)v, A.tz0);
+        cx = __builtin_amdgcn_rsqf(fmaf(ty, ty, fmaf(tz, tz, 1.f)));
+        cy = ty * cx;
+        cz = tz * cx;
+    }
+    const float ox = pose[0], oy = pose[1], oz = pose[2];
+    const float dx = fmaf(pose[3], cx, fmaf(pose[4], cy, pose[5] * cz));
+    const float dy = fmaf(pose[6], cx, fmaf(pose[7], cy, pose[8] * cz));
+    const float dz = fmaf(pose[9], cx, fmaf(pose[10], cy, pose[11] * cz));
+    const float ix = frcp(dx), iy = frcp(dy), iz = frcp(dz);
+
+    const MeshHdr hd = D.mesh.hdr[s];  // wave-uniform: one scene per block
+    const float best = mesh_ray_cast(D.mesh, hd, ox, oy, oz, dx, dy, dz, ix, iy, iz);
+    float val = A.dmax;  // a miss
+    if (best < INFINITY) val = fminf(A.is_depth ? best * cx : best, A.dmax);
+    A.img[((size_t)b * h + v) * w + u] = val * A.scale;
+}
+
+__global__ __launch_bounds__(SCENE_BLOCK) void scene_distance_mesh_kernel(MeshDistArgs D) {
+    const SceneDistArgs& A = D.d;
+    const long long j = (long long)blockIdx.x * SCENE_BLOCK + threadIdx.x;
+    if (j >= A.n) return;
+    const long long s = A.p_to_scene ? (long long)min(max(A.p_to_scene[j], 0), A.sc.S - 1) : j / A.per_scene;
+    const MeshHdr hd = D.mesh.hdr[s];
+    A.out[j] = mesh_distance(D.mesh, hd, A.points[j * 3], A.points[j * 3 + 1], A.points[j * 3 + 2]);
+}
+
+}  // namespace
+
+hipError_t launch_scene_render_mesh(const MeshRenderArgs& a, hipStream_t s) {
+    if (a.r.B <= 0) return hipSuccess;
+    const long long tiles = ((long long)a.r.H * a.r.W + SCENE_BLOCK - 1) / SCENE_BLOCK;
+    hipLaunchKernelGGL(scene_render_mesh_kernel, dim3((unsigned)tiles, (unsigned)a.r.B), dim3(SCENE_BLOCK),
+                       scene_render_lds_bytes(a.r.H, a.r.W, a.r.is_spherical), s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_scene_distance_mesh(const MeshDistArgs& a, hipStream_t s) {
+    if (a.d.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scene_distance_mesh_kernel, dim3((unsigned)((a.d.n + SCENE_BLOCK - 1) / SCENE_BLOCK)),
+                       dim3(SCENE_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace sdfn

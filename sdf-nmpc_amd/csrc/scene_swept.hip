@@ -22,6 +22,7 @@
 //
 // The stack is indexed at run time and lives in scratch memory: 24 entries of 24 bytes per lane, touched once per
 // interval beside an evaluation that costs hundreds of fp64 operations per primitive.
+#include "mesh_dev.h"
 #include "scene_dev.h"
 
 namespace sdfn {
@@ -93,6 +94,13 @@ struct EvalMixed {  // scene_distance_mixed_kernel: the movers first, then the r
             [&] { return best; });
         return best;
     }
+};
+
+struct EvalMesh {  // scene_distance_mesh_kernel: a static set of triangles, signed when the set is closed (mesh_dev.h)
+    const MeshDev& M;
+    MeshHdr h;
+    __device__ EvalMesh(const SceneSweptArgs& A, long long s) : M(A.mesh), h(A.mesh.hdr[s]) {}
+    __device__ double operator()(double px, double py, double pz, double) const { return mesh_distance(M, h, px, py, pz); }
 };
 
 __device__ __forceinline__ bool finite3(const double* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
@@ -185,5 +193,6 @@ hipError_t launch_scene_swept(const SceneSweptArgs& a, hipStream_t s) { return l
 hipError_t launch_scene_swept_dyn(const SceneSweptArgs& a, hipStream_t s) { return launch_swept<EvalDyn, true>(a, s); }
 hipError_t launch_scene_swept_grid(const SceneSweptArgs& a, hipStream_t s) { return launch_swept<EvalGrid, false>(a, s); }
 hipError_t launch_scene_swept_mixed(const SceneSweptArgs& a, hipStream_t s) { return launch_swept<EvalMixed, true>(a, s); }
+hipError_t launch_scene_swept_mesh(const SceneSweptArgs& a, hipStream_t s) { return launch_swept<EvalMesh, false>(a, s); }
 
 }  // namespace sdfn

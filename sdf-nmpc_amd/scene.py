@@ -23,6 +23,10 @@ to 65536 static primitives per scene, and every call above -- and every consumer
 scene would return, bit for bit, from kernels that visit only the grid cells along a ray or around a point.  A few
 moving obstacles go beside it: ``Scene(ctx, forest, grid=True, movers=Scene.crowd(8, lo, hi))``.
 
+A world that is a surface -- a cave, a building, terrain -- is a triangle mesh: ``Scene.mesh(ctx, Mesh.tunnel(path, 1.2))``
+holds one static ``mesh.Mesh`` per scene behind a bounding-volume hierarchy (csrc/scene_mesh.hip); ``render``,
+``distance``, ``swept_distance`` and the rollouts take it like any other scene, ``Nmpc.set_sdf_scene`` does not.
+
 World frame z up; camera frame x forward, y left, z up, the pixel grid of ``ColChecker``.  There is no CPU path.
 """
 from __future__ import annotations
@@ -198,13 +202,41 @@ class Scene:
                                        motion if any(m is not None for m in motion) else None)
         self.is_dynamic = bool(_lib.load().sdfnmpc_scene_is_dynamic(self.h))
         self.is_indexed = bool(_lib.load().sdfnmpc_scene_is_indexed(self.h))
+        self.is_mesh = False
+        self._set_scene_of(scene_of)
+
+    @classmethod
+    def mesh(cls, ctx: "_lib.Context", meshes, scene_of=None, closed=False, leaf_size=None):
+        """A scene set of triangle meshes: one ``mesh.Mesh`` or a list of them (S scenes, ``scene_of`` [B] as above), each
+        a static surface behind a bounding-volume hierarchy that the library builds when the scene is created
+        (csrc/mesh_bvh.h) -- ``is_mesh``.  closed=False: open surfaces, ``distance`` is unsigned.  closed=True: every mesh
+        must be a closed, consistently oriented manifold (``Mesh.is_closed``) and ``distance`` is negative inside.
+        leaf_size: 1..8 triangles per leaf (None: the library's default, 4), or -1 for no hierarchy at all -- every
+        result is the same bit for bit, only slower.  ``render``, ``render_from_state``, ``distance``,
+        ``swept_distance``, ``speed_bound`` (0) and ``Nmpc.rollout(scene=)`` take it like any other scene; hits are
+        double-sided, and a camera inside a closed mesh sees its inner walls.  ``Nmpc.set_sdf_scene`` refuses it
+        (SdfnmpcError), and so does the library for a malformed mesh: a non-finite vertex, an index out of range, a
+        triangle of zero area, closed=True on a surface with a boundary or a flipped triangle."""
+        from .mesh import Mesh
+        ms = [meshes] if isinstance(meshes, Mesh) else list(meshes)
+        self = cls.__new__(cls)
+        self.ctx, self.S = ctx, len(ms)
+        self._sdf_users = weakref.WeakSet()
+        self.h = _lib.scene_create_mesh(ctx, [m.verts for m in ms], [m.tris for m in ms],
+                                        0 if leaf_size is None else int(leaf_size), bool(closed))
+        self.is_dynamic = self.is_indexed = False
+        self.is_mesh = bool(_lib.load().sdfnmpc_scene_is_mesh(self.h))
+        self._set_scene_of(scene_of)
+        return self
+
+    def _set_scene_of(self, scene_of):
         self.scene_of = self._scene_of = None
         if scene_of is not None:
             so = np.ascontiguousarray(scene_of, dtype=np.int32).ravel()
             if so.size and (so.min() < 0 or so.max() >= self.S):
                 raise ValueError(f"scene_of entries must lie in [0, {self.S})")
             self.scene_of = so
-            self._scene_of = _lib.DeviceArray.from_numpy(ctx, so)
+            self._scene_of = _lib.DeviceArray.from_numpy(self.ctx, so)
 
     # ---- helpers
     def _f64(self, a, shape):
