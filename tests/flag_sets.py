@@ -147,11 +147,15 @@ def config(name, **more):
     return Config(**{**over, **more})
 
 
-def quad(name, cfg=None, seed=0):
+def quad(name, cfg=None, seed=0, coeffs=None):
+    """coeffs: the braking polynomial of a rec_feas set (default: braking(cfg), the four-term physical law)."""
     from sdf_nmpc_amd import synth
     from sdf_nmpc_amd.model import Quad
     cfg = cfg or config(name)
-    coeffs = braking(cfg) if cfg.flags.recursive_feasibility else None
+    if not cfg.flags.recursive_feasibility:
+        coeffs = None
+    elif coeffs is None:
+        coeffs = braking(cfg)
     return Quad(cfg, braking_coeffs=coeffs)
 
 
@@ -169,6 +173,43 @@ def braking(cfg):
     polynomial_3variate (utils/math.py:307-314), a_b_min = mpc.stability.a_b_min (default.yaml:73-74)."""
     from sdf_nmpc_amd import synth
     return synth.braking_coeffs(int(cfg.mpc.braking_dist.degree), noise=0.0, a_brake=float(cfg.mpc.stability.a_b_min))
+
+
+def dense_braking(deg):
+    """The reference-pinned dense coefficients of polynomial_3variate at degree deg (flags_golden.npz
+    poly/deg*/coeffs, every monomial ~ N(0, 1): test_flags.test_poly_term_order_and_values_match_reference)."""
+    import os
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "flags_golden.npz")) as f:
+        return f[f"poly/deg{deg}/coeffs"].copy()
+
+
+# The coefficient seed of noisy_braking per (flag set, degree, N) where seed 1 does not converge everywhere in
+# the C IPM (test_flags.test_noisy_braking_is_seen_and_converges); none so far.
+NOISY_SEEDS = {}
+NOISY_SETS = ["rec_feas", "rec_feas_soft_brake", "stability", "hard_df_rec_feas"]
+# the QP runs of test_gpu_lin_general.test_qp_with_noisy_braking as (set, degree, B, N, kernel); problem seed 11
+NOISY_QP_RUNS = [("rec_feas_soft_brake", 4, 8, 20, "serial"), ("rec_feas_soft_brake", 6, 8, 20, "serial"),
+                 ("stability", 4, 8, 20, "serial"), ("stability", 6, 8, 20, "serial"),
+                 ("hard_df_rec_feas", 6, 8, 20, "serial"), ("stability", 6, 8, 40, "segmented")]
+
+
+def noisy_braking(cfg, deg, seed=1):
+    """The physical braking law of braking(cfg) at degree deg with N(0, 2e-3) on every monomial
+    (synth.braking_coeffs' noise argument): mixed terms and every degree's coefficients are live."""
+    from sdf_nmpc_amd import synth
+    return synth.braking_coeffs(int(deg), seed=seed, noise=2e-3, a_brake=float(cfg.mpc.stability.a_b_min))
+
+
+def degree_of(coeffs):
+    """The degree whose polynomial_3variate has len(coeffs) monomials ((d + 1)(d + 2)(d + 3) / 6: 1, 4, .., 84)."""
+    return {(d + 1) * (d + 2) * (d + 3) // 6: d for d in range(7)}[len(coeffs)]
+
+
+def config_for(name, coeffs=None, **more):
+    """config(name) with mpc.braking_dist.degree set to the degree of the given coefficients."""
+    if coeffs is not None:
+        more = dict(more, mpc__braking_dist__degree=degree_of(coeffs))
+    return config(name, **more)
 
 
 def problem(cfg, q, B, N, seed):

@@ -158,9 +158,9 @@ def _net(oracle_lib, q):
     return oracle_lib.Net(W.DEFAULT_SPEC, W.siren_weights(W.DEFAULT_SPEC, 0))
 
 
-def _problem(oracle_lib, name, B, N, seed, noise=0.05):
-    cfg = F.config(name, mpc__N=N)
-    q = F.quad(name, cfg)
+def _problem(oracle_lib, name, B, N, seed, noise=0.05, coeffs=None):
+    cfg = F.config_for(name, coeffs, mpc__N=N)
+    q = F.quad(name, cfg, coeffs=coeffs)
     # the flight along the camera's view (hard fov rows: random v0 can leave the cone before any input acts,
     # which makes a hard row infeasible -- for the reference's HPIPM too); sets with hard rows on the scene net
     prob = F.problem(cfg, q, B, N, seed)
@@ -313,3 +313,187 @@ def test_segment_edges_serial_vs_segmented_c_ipm(oracle_lib, N, P):
         assert np.abs(a["iters"] - b["iters"]).max() <= 1, (name, a["iters"], b["iters"])
         gap = np.abs(a["du"] - b["du"]).max(axis=(1, 2))
         assert (gap <= 5e-6).mean() >= 0.9, (name, gap)
+
+
+# ---- the references of tests/test_gpu_lin_general.py, held on the CPU before the GPU sees them
+LIN_GEN_RTOL, LIN_GEN_ATOL = 1e-9, 1e-11   # the GPU bars there (test_gpu_flags.test_linearisation_per_flag_set's)
+FLAG_VALUES = (0.0, 1.0, 0.3)
+
+
+@pytest.mark.parametrize("deg", range(7))
+def test_terminal_extras_oracle_dense_polynomial(oracle_lib, fg, deg):
+    """orc_quad_term with every monomial of polynomial_3variate live, degrees 0..6 (the reference-pinned dense
+    coefficients and velocities of flags_golden.npz, |v| up to 4 m/s, poly up to 8.9e3) and flags {0, 1, 0.3}:
+    values against the numpy restatement on the reference-pinned poly_eval, and the polynomial's gradient columns
+    of JhE[0] against poly_eval's analytic gradient, to a tenth of the GPU test's bars (relative 1e-10, absolute
+    1e-12 max(1, |poly|)); JhE against central differences at test_terminal_extras_oracle's bars.  Measured worst
+    value error 3e-15 max(1, |poly|) (printed)."""
+    coeffs = F.dense_braking(deg)
+    cfg = F.config_for("stability", coeffs)
+    q = F.quad("stability", cfg, coeffs=coeffs)
+    assert q.poly_deg == deg and len(q.poly) == len(poly_terms(deg)) and np.array_equal(q.poly, fg[f"poly/deg{deg}/coeffs"])
+    m = oracle_lib.quad_model(cfg)
+    rng = np.random.default_rng(20 + deg)
+    R_off = np.asarray(cfg.sensor.B_R_C).T @ np.asarray(cfg.sensor.B_p_C) + np.array([cfg.mpc.fov_const_offset, 0, 0])
+    worst = worst_g = 0.0
+    for i, v in enumerate(fg[f"poly/deg{deg}/v"]):
+        x = np.concatenate([rng.uniform(-2, 2, 3), synth.euler2quat(rng.uniform(-0.5, 0.5, 3)), v])
+        p = np.zeros(145)
+        p[0] = flag = FLAG_VALUES[i % 3]
+        R = synth.quat2rot(synth.euler2quat(rng.uniform(-1, 1, 3)))
+        p[1:4], p[4:13] = rng.uniform(-1, 1, 3), R.ravel()
+        hE, JhE, yN5, JyN5 = oracle_lib.term_extras(m, x, p, q)
+        pv, gv = poly_eval(q.poly, deg, v)
+        np.testing.assert_allclose(pv, fg[f"poly/deg{deg}/val"][i], rtol=1e-12, atol=1e-12)
+        sc = max(1.0, abs(pv))
+        E = R.T @ (x[:3] + pv * v / np.sqrt(v @ v + 1e-4) - p[1:4]) + R_off
+        want = np.array([-flag * pv, flag * np.arctan2(E[1], E[0]), flag * np.arctan2(E[2], np.hypot(E[0], E[1])), *v])
+        worst = max(worst, np.abs(hE - want).max() / sc)
+        np.testing.assert_allclose(hE, want, rtol=LIN_GEN_RTOL / 10, atol=LIN_GEN_ATOL / 10 * sc)
+        gs = max(1.0, np.abs(gv).max())
+        worst_g = max(worst_g, np.abs(JhE[0, 7:] + flag * gv).max() / gs)
+        np.testing.assert_allclose(JhE[0, 7:], -flag * gv, rtol=LIN_GEN_RTOL / 10, atol=LIN_GEN_ATOL / 10 * gs)
+        assert (JhE[0, :7] == 0).all() and np.array_equal(JhE[3:], np.eye(10)[7:])
+        if flag == 0:
+            assert (hE[:3] == 0).all() and (JhE[:3] == 0).all() and (yN5 == 0).all() and (JyN5 == 0).all()
+            assert np.array_equal(hE[3:], v)
+        for j in range(10):
+            d = np.zeros(10); d[j] = 1e-6
+            hp, _, yp, _ = oracle_lib.term_extras(m, x + d, p, q)
+            hm, _, ym, _ = oracle_lib.term_extras(m, x - d, p, q)
+            np.testing.assert_allclose(JhE[:, j], (hp - hm) / 2e-6, rtol=1e-5, atol=1e-6)
+            np.testing.assert_allclose(JyN5[:, j], (yp - ym) / 2e-6, rtol=1e-5, atol=1e-6)
+    print(f"\ndense polynomial deg {deg}: worst |hE - numpy| / max(1, |poly|) = {worst:.2e}, "
+          f"worst |dpoly/dv - poly_eval's| / max(1, |grad|) = {worst_g:.2e}")
+
+
+def test_noisy_braking_is_seen_and_converges(oracle_lib):
+    """The problems of test_gpu_lin_general's QP, phase-split and controller runs (flag_sets.noisy_braking: the
+    physical law plus N(0, 2e-3) on every monomial; B = 8, N = 20, seed 11) at degrees 2, 4 and 6 on the four
+    rec_feas sets: the C IPM on the checker's linearisation converges on every instance (the GPU tests ask for
+    status 0), and at degree 4 the noise is visible in the solution -- du differs from the noise-free
+    polynomial's by more than 1e-3, two hundred times the GPU bar (measured 0.02; 0.18 for stability).  The
+    segmented run's problem (flag_sets.NOISY_QP_RUNS, N = 40) converges in the four-segment recursion."""
+    B, N, seed = 8, 20, 11
+    for name in F.NOISY_SETS:
+        base = oracle_lib.qp_ipm_batch(*_lin_prob(oracle_lib, name, B, N, seed, None), tol=QP_TOL)
+        assert (base["status"] == 0).all(), (name, base["status"])
+        for deg in (2, 4, 6):
+            cfg = F.config(name)
+            coeffs = F.noisy_braking(cfg, deg, F.NOISY_SEEDS.get((name, deg, N), 1))
+            r = oracle_lib.qp_ipm_batch(*_lin_prob(oracle_lib, name, B, N, seed, coeffs), tol=QP_TOL)
+            assert (r["status"] == 0).all(), (name, deg, r["status"], r["iters"])
+            if deg == 4:
+                gap = np.abs(r["du"] - base["du"]).max()
+                print(f"\nnoisy braking {name} deg 4: |du - du_noise_free| = {gap:.3e}, iters {r['iters'].tolist()}")
+                assert gap > 1e-3, (name, gap)
+    for name, deg, B, N, kernel in F.NOISY_QP_RUNS:
+        if kernel != "segmented":
+            assert (name, deg, B, N) in [(n, d, 8, 20) for n in F.NOISY_SETS for d in (2, 4, 6)]  # shown above
+            continue
+        coeffs = F.noisy_braking(F.config(name), deg, F.NOISY_SEEDS.get((name, deg, N), 1))
+        r = oracle_lib.qp_ipm_batch(*_lin_prob(oracle_lib, name, B, N, seed, coeffs), tol=QP_TOL, start=dict(seg=4))
+        assert (r["status"] == 0).all(), (name, deg, N, r["status"], r["iters"])
+
+
+def _lin_prob(oracle_lib, name, B, N, seed, coeffs):
+    """qp_ipm_batch's leading arguments for a flag set's problem with the given braking coefficients."""
+    cfg, q, prob, x0, lin = _problem(oracle_lib, name, B, N, seed, coeffs=coeffs)
+    return lin, prob, x0, q
+
+
+ATT_WIDE_SHAPES = [(1, 20, True), (7, 40, False), (3, 60, True)]  # (B, N, uniform grid)
+
+
+def att_wide_problem(cfg, B, N, seed, dt=None):
+    """synth.make_problem's problem for the 'att' model away from the hover-ish iterate: at every node roll and
+    pitch within +-1.2 rad and any yaw, the quaternion scaled by U(0.5, 2) and by +-1 (f_expl normalises it;
+    the sign leaves the yaw's rotation as it is); commands alternately at a corner of the input box (thrust 0 or 1,
+    the others +-1) and drawn from U(box); the flag off at every third node."""
+    prob = synth.make_problem(cfg, B, N, seed=seed, dt=dt)
+    rng = np.random.default_rng(2000 + seed)
+    eul = np.stack([rng.uniform(-1.2, 1.2, (B, N + 1)), rng.uniform(-1.2, 1.2, (B, N + 1)),
+                    rng.uniform(-np.pi, np.pi, (B, N + 1))], -1)
+    prob["x"][..., 3:7] = (synth.euler2quat(eul) * rng.uniform(0.5, 2.0, (B, N + 1, 1))
+                           * rng.choice([-1.0, 1.0], (B, N + 1, 1)))
+    lbu, ubu = Quad(cfg).lbu, Quad(cfg).ubu
+    corner = np.where(rng.integers(0, 2, (B, N, 4)) == 1, ubu, lbu)
+    inside = rng.uniform(lbu, ubu, (B, N, 4))
+    at_corner = (np.arange(B * N).reshape(B, N) % 2 == 0)[..., None]
+    prob["u"] = np.where(at_corner, corner, inside)
+    prob["p"][:, ::3, 0] = 0.0
+    return prob
+
+
+@pytest.mark.parametrize("B,N,uniform", ATT_WIDE_SHAPES)
+def test_att_wide_problem_referees(oracle_lib, cfg, B, N, uniform):
+    """The checker on test_gpu_lin_general's widened 'att' inputs (att_wide_problem at that test's shapes and
+    seeds): orc_quad_rk4 against synth.rk4 (independent numpy) to a tenth of lin_close's bar, its [A | B] against
+    central differences at this module's FD bars (the differences' own limit, ~3e-10, is far inside them); and the
+    problem holds what it promises (commands at the box, non-unit and sign-flipped quaternions, the grid)."""
+    from tolerances import LIN_RTOL, lin_close
+    _, dt = oracle_lib.shooting_grid(N, float(cfg.mpc.T), uniform)
+    prob = att_wide_problem(cfg, B, N, seed=B * 100 + N, dt=dt)
+    m, lim = oracle_lib.quad_model(cfg), cfg.robot.limits
+    x, u = prob["x"], prob["u"]
+    nrm = np.linalg.norm(x[..., 3:7], axis=-1)
+    assert nrm.min() < 0.7 and nrm.max() > 1.5 and (x[..., 3] < 0).any() and (x[..., 3] > 0).any()
+    at_box = ((u == Quad(cfg).lbu) | (u == Quad(cfg).ubu)).all(-1)
+    assert at_box[:, ::2].any() and not at_box.all() and (prob["p"][:, ::3, 0] == 0).all() and (prob["p"][:, 1::3, 0] == 1).all()
+    assert uniform == (np.ptp(prob["dt"]) < 1e-12)
+    want = np.stack([synth.rk4(x[:, k], u[:, k], prob["dt"][k], lim) for k in range(N)], 1)
+    got, worst_fd = np.empty_like(want), 0.0
+    for b in range(B):
+        for k in range(N):
+            got[b, k], AB = oracle_lib.rk4(m, x[b, k], u[b, k], prob["dt"][k])
+            if (b * N + k) % 7:  # central differences on every seventh row
+                continue
+            z = np.concatenate([x[b, k], u[b, k]])
+            fd = np.empty((10, 14))
+            for j in range(14):
+                d = np.zeros(14); d[j] = 1e-6
+                fd[:, j] = (synth.rk4((z + d)[:10], (z + d)[10:], prob["dt"][k], lim)
+                            - synth.rk4((z - d)[:10], (z - d)[10:], prob["dt"][k], lim)) / 2e-6
+            worst_fd = max(worst_fd, np.abs(AB - fd).max())
+            np.testing.assert_allclose(AB, fd, rtol=1e-5, atol=1e-6)
+    err = np.abs(got - want).max() / max(1.0, np.abs(want).max())
+    print(f"\natt wide ({B}, {N}): |rk4_C - rk4_numpy| / max(1, |x+|) = {err:.2e}, worst |AB - FD| = {worst_fd:.2e}")
+    assert lin_close(got, want, rtol=LIN_RTOL / 10)
+
+
+def s03_zero_problem(cfg):
+    """Rows of the 'att' model with x3 = x6 = 0 (q = [0, qx, qy, 0]: a half turn about a horizontal axis, where
+    the yaw atan2(q3, q0) is atan2(0, 0) = 0): B = 6 instances of N = 2 nodes on dt = 0.075, instance 0 the point
+    x = [0, 0, 1, 0, 0.6, 0.8, 0, 1, 0, 0], u = [0.5, 0.1, 0.1, 0.2], the others with (qx, qy) at any angle, unit
+    (instances 0..2) and scaled by U(0.5, 2) (3..5), and synth.make_problem's commands."""
+    B, N = 6, 2
+    prob = synth.make_problem(cfg, B, N, seed=61, dt=np.full(N, 0.075))
+    rng = np.random.default_rng(62)
+    ang = rng.uniform(-np.pi, np.pi, (B, N + 1))
+    scale = np.where(np.arange(B) < 3, 1.0, rng.uniform(0.5, 2.0, B))[:, None]
+    prob["x"][..., 3], prob["x"][..., 6] = 0.0, 0.0
+    prob["x"][..., 4], prob["x"][..., 5] = np.cos(ang) * scale, np.sin(ang) * scale
+    prob["x"][0, 0] = [0, 0, 1, 0, 0.6, 0.8, 0, 1, 0, 0]
+    prob["u"][0, 0] = [0.5, 0.1, 0.1, 0.2]
+    return prob
+
+
+def test_s03_zero_point_in_the_checker(oracle_lib, cfg):
+    """At x3 = x6 = 0 the checker's x+ and y are numpy's (atan2(0, 0) = 0 on both sides), to a tenth of lin_close's
+    bar; its [A | B] is not finite there (the derivative of atan2 at (0, 0) is 0 / 0), so it referees values only:
+    test_gpu_lin_general.test_att_s03_zero_branch claims nothing about the kernel's q and u columns."""
+    from tolerances import LIN_RTOL, lin_close
+    prob = s03_zero_problem(cfg)
+    m, lim = oracle_lib.quad_model(cfg), cfg.robot.limits
+    B, N = prob["u"].shape[:2]
+    for b in range(B):
+        for k in range(N):
+            x, u = prob["x"][b, k], prob["u"][b, k]
+            xn, AB = oracle_lib.rk4(m, x, u, prob["dt"][k])
+            assert lin_close(xn, synth.rk4(x, u, prob["dt"][k], lim), rtol=LIN_RTOL / 10)
+            assert xn[3] == 0 and xn[6] == 0  # the whole step stays on the branch
+            assert not np.isfinite(AB[:, 3:7]).all()
+            y = oracle_lib.cost(m, x, u, prob["p"][b, k])[0]
+            f = synth.f_expl(x, u, lim)
+            want = np.concatenate([x[:3], [y[3]], x[7:], [u[1] * lim.roll, u[2] * lim.pitch, u[3] * lim.wz, f[9]]])  # y[10] = W_a[2]
+            assert np.isfinite(y).all() and lin_close(y, want, rtol=LIN_RTOL / 10), (y, want)

@@ -10,6 +10,7 @@ from sdf_nmpc_amd import weights as W
 from sdf_nmpc_amd.config import Config
 from sdf_nmpc_amd.controller import Nmpc
 from sdf_nmpc_amd.reference import Ref, yaw2quat
+from tolerances import sdf_df_ok
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore:no SDF weights")]
 
@@ -41,6 +42,18 @@ def scenario(n, rng):
             r.use_weights(r.W_on)
             n.set_ref(r, k, b=None if n.B == 1 else b)
     return sq(x0)
+
+
+def eval_sdf_ref(onet, n, k):
+    """What column 0 of Nmpc.eval(k) is: the checker's network (fp64 evaluation of the fp32 weights) at node k of the
+    controller's iterate, at the fp32 input the device kernel reads -- the camera-frame position W_R_Co^T (p_k -
+    W_p_Co) and the latent of node k's parameters (gen_model.py:64, flag = 1)."""
+    idx = n.cfg.mpc.p_idx
+    x = n.ocp.download("x")[:, k]
+    pk = (n.p if n.B > 1 else n.p[None])[:, k]
+    Co_p_B = np.einsum("bji,bj->bi", pk[:, idx.W_R_Co].reshape(-1, 3, 3), x[:, :3] - pk[:, idx.W_p_Co])
+    inp = np.concatenate([Co_p_B.astype(np.float32).astype(np.float64), pk[:, idx.latent:].astype(np.float32)], 1)
+    return onet.f64(inp)[0]
 
 
 def oracle_u0(n, x0, oracle_lib):
@@ -76,7 +89,10 @@ def test_nmpc_rti_step_matches_oracle(oracle_lib, B, sdf_cost):
     x, uu = n.get_matrices()
     np.testing.assert_array_equal(np.atleast_2d(u), np.atleast_2d(uu[..., 0, :]))
     np.testing.assert_allclose(x[..., 0, :], x0, atol=1e-12)
-    assert np.atleast_1d(n.eval(3)).shape == ((1,) if B == 1 else (B, 1))
+    ev = np.atleast_1d(n.eval(3))
+    assert ev.shape == ((1,) if B == 1 else (B, 1))
+    onet = oracle_lib.Net(W.DEFAULT_SPEC, W.siren_weights(W.DEFAULT_SPEC, seed=0))
+    assert sdf_df_ok(ev.reshape(-1), eval_sdf_ref(onet, n, 3))  # by value: the network's df at node 3, flag = 1
     n.ocp.close()
 
 

@@ -21,15 +21,17 @@ LIN = ("xn", "AB", "y", "Jy", "yN", "JyN", "h", "Jh", "hE", "JhE")
 OUT = LIN + ("dx", "du", "slack", "status", "iters", "res")
 
 
-def _config(name, N):
-    """The flag set's config at horizon N, at the reference's bounds (default.yaml)."""
-    return F.config(name, mpc__N=N)
+def _config(name, N, coeffs=None):
+    """The flag set's config at horizon N, at the reference's bounds (default.yaml); with braking coefficients,
+    at their degree."""
+    return F.config_for(name, coeffs, mpc__N=N)
 
 
-def _setup(gpu_ctx, name, B, N, seed, noise=0.05):
+def _setup(gpu_ctx, name, B, N, seed, noise=0.05, coeffs=None):
+    """coeffs: the braking polynomial of a rec_feas set (default: flag_sets.braking, four non-zero terms)."""
     import torch
-    cfg = _config(name, N)
-    q = F.quad(name, cfg)
+    cfg = _config(name, N, coeffs)
+    q = F.quad(name, cfg, coeffs=coeffs)
     dev = torch.device("cuda", gpu_ctx.device)
     # v0 along the camera's view: the braking point of the rec_feas rows lies in the field of view; sets with
     # a hard row carry the scene latent (flag_sets.problem)
@@ -270,7 +272,7 @@ def test_serial_qp_upper_end_refusals(gpu_ctx, oracle_lib):
 
 
 def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_frac=1.0, n_exact=None, nseg=4, seed=12,
-              dense=True):
+              dense=True, coeffs=None):
     """n_exact: the exact solution (a dense KKT solve, ~2 s per instance at N = 40) for the first n_exact
     instances and every instance whose du is off the C IPM's by more than the bar (None: all).  nseg: the
     segments of the segmented kernel at this N (the C IPM runs lqr_seg over the same partition).  dense=False
@@ -279,7 +281,7 @@ def _check_qp(gpu_ctx, oracle_lib, name, B, N, kernel, need_active=True, iters_f
     the input boxes directly.  Returns the problem, its device buffers and the C IPM's result (whole batch)."""
     import qp_oracle
     from test_gpu_qp import _agree
-    cfg, q, prob, x0, t = _setup(gpu_ctx, name, B, N, seed=seed)
+    cfg, q, prob, x0, t = _setup(gpu_ctx, name, B, N, seed=seed, coeffs=coeffs)
     _lib.linearize(gpu_ctx, _net(gpu_ctx, q), _lib.quad_model(cfg, q), B, N, q.np, t, nyN=q.nyN, no_sdf=not q.need_sdf)
     opts = _lib.qp_opts(q, tol=QP_TOL)
     gpu_ctx.set_qp_kernel(kernel)
@@ -368,8 +370,12 @@ def test_phase_split_bitwise_per_flag_set(gpu_ctx, name, B, N, kernel, seed):
     (flag_sets.PHASE_SPLIT_RUNS).  (A segmented kernel that patches with sdf_row == -1 writes J_h[:, 2] over
     g_x[4..9] and g_u of every stage record: status 0 everywhere and du off by 0.39 on the two rec_feas sets
     without a stage sdf row.)"""
-    cfg, q, prob, x0, ta = _setup(gpu_ctx, name, B, N, seed=seed)
-    _, _, _, _, tb = _setup(gpu_ctx, name, B, N, seed=seed)
+    _phase_split(gpu_ctx, name, B, N, kernel, seed)
+
+
+def _phase_split(gpu_ctx, name, B, N, kernel, seed, coeffs=None):
+    cfg, q, prob, x0, ta = _setup(gpu_ctx, name, B, N, seed=seed, coeffs=coeffs)
+    _, _, _, _, tb = _setup(gpu_ctx, name, B, N, seed=seed, coeffs=coeffs)
     net, qm, opts = _net(gpu_ctx, q), _lib.quad_model(cfg, q), _lib.qp_opts(q)
     gpu_ctx.set_qp_kernel(kernel)
     try:
@@ -409,11 +415,11 @@ def test_capacity_and_refusals(gpu_ctx):
         _lib.linearize(gpu_ctx, None, _lib.quad_model(cfg, q), B, N, q.np, t)
 
 
-def _nmpc(name, B, N, seed):
+def _nmpc(name, B, N, seed, coeffs=None):
     from sdf_nmpc_amd.controller import Nmpc
     from sdf_nmpc_amd.reference import Ref, yaw2quat
-    cfg = _config(name, N)
-    q = F.quad(name, cfg)
+    cfg = _config(name, N, coeffs)
+    q = F.quad(name, cfg, coeffs=coeffs)
     scene = F.uses_scene(q)
     if scene:
         import scene_setup as S
@@ -442,8 +448,13 @@ def test_controller_rti_step_per_flag_set(oracle_lib, name, N):
     """Nmpc.solve (host setters, solver object) for a flag set: one SQP-RTI step against the oracle pipeline
     (oracle linearisation + the C IPM) on the same iterate; u0 within 2e-5.  At N = 40 AUTO runs the segmented
     kernel on the solver object's split pack -- for rec_feas_no_sdf_row with no stage sdf row to patch."""
+    _controller_step(oracle_lib, name, N)
+
+
+def _controller_step(oracle_lib, name, N, coeffs=None, check=None):
+    """check(n, q, x0, xbar, glin, lin, onet): further assertions on the open controller after its step."""
     B = 6
-    n, q, x0 = _nmpc(name, B, N, seed=21)
+    n, q, x0 = _nmpc(name, B, N, seed=21, coeffs=coeffs)
     assert n.ocp.ctx.qp_kernel(N, B, _lib.qp_opts(q)) == ("segmented" if N >= 36 else "serial")
     xbar, ubar = n.ocp.download("x").copy(), n.ocp.download("u").copy()
     xbar[:, 0] = x0
@@ -467,4 +478,6 @@ def test_controller_rti_step_per_flag_set(oracle_lib, name, N):
         assert ev.shape == (B, 3 if q.rec_feas else 1)
     else:
         assert (n.eval(0) == 0).all()
+    if check is not None:
+        check(n, q, x0, xbar, glin, lin, onet)
     n.ocp.close()
