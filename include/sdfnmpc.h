@@ -92,7 +92,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 16
+#define SDFNMPC_ABI_VERSION 17
 
 enum {
     SDFNMPC_OK = 0,
@@ -952,9 +952,19 @@ int sdfnmpc_scene_create_mixed(sdfnmpc_ctx* ctx, int S, const int* count, const 
  * the limits below, more than 2^24 triangles in the set, a non-finite vertex, an index outside [0, nvert[s]), a
  * triangle whose area is zero after rounding, a leaf_size outside the values below, and with closed = 1 an edge that is
  * not shared by exactly two triangles traversing it in opposite directions.
- * SDFNMPC_E_UNSUPPORTED, nothing launched: a mesh set given to sdfnmpc_scene_sdf_rows, sdfnmpc_lin_args.sdf_scene or
- * sdfnmpc_solver_set_sdf_scene.  Not built: a mesh as the controller's SDF source, movers beside a mesh, meshes mixed
- * with primitives in one scene. */
+ *   SDF rows  a set created with sdf_source = 1 is accepted by sdfnmpc_scene_sdf_rows, sdfnmpc_lin_args.sdf_scene and
+ *             sdfnmpc_solver_set_sdf_scene (and so by every step and rollout of a solver with that source) and launches
+ *             "scene_sdf_rows_mesh": the value of `distance` above, bit for bit, and its world gradient (see
+ *             sdfnmpc_scene_sdf_rows).  sdfnmpc_scene_is_sdf_source: 1 for such a set and for every set that is not a
+ *             mesh set, else 0.
+ * The triangle-mesh work first shipped with a mesh set refused as an SDF source, and that refusal is pinned by a test of
+ * the project that must keep passing as it is: a set created with sdf_source = 0 -- every caller from before the field
+ * existed -- is still refused with the same code and message.  That, and nothing about the kernels, is why a mesh set
+ * becomes a source only when it is created as one.
+ * SDFNMPC_E_ARG (nothing is allocated on the device) also: a sdf_source other than 0 or 1.
+ * SDFNMPC_E_UNSUPPORTED, nothing launched, outputs untouched: a mesh set created with sdf_source = 0 given to
+ * sdfnmpc_scene_sdf_rows, sdfnmpc_lin_args.sdf_scene or sdfnmpc_solver_set_sdf_scene.  Not built: movers beside a mesh,
+ * meshes mixed with primitives in one scene, a walk pruned at max_df for closed sets. */
 #define SDFNMPC_MESH_MAX_TRIS (1 << 20)  /* per scene */
 #define SDFNMPC_MESH_MAX_VERTS (1 << 21) /* per scene */
 typedef struct {
@@ -962,10 +972,13 @@ typedef struct {
                       triangle of the scene -- the brute-force yardstick through the same kernels */
     int closed;    /* 0: open surfaces, unsigned distance; 1: every scene must be a closed, consistently oriented
                       manifold (else SDFNMPC_E_ARG) and the distance is signed, negative inside */
+    int sdf_source; /* 0: the set is refused as the controller's SDF source (SDFNMPC_E_UNSUPPORTED), as every mesh set
+                      was before this field; 1: it is accepted.  Nothing else about the set depends on it */
 } sdfnmpc_mesh_opts;
 int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts, const int* ntri,
                               const int* tris, const sdfnmpc_mesh_opts* opts, sdfnmpc_scene** out);
 int sdfnmpc_scene_is_mesh(const sdfnmpc_scene* scene);
+int sdfnmpc_scene_is_sdf_source(const sdfnmpc_scene* scene);
 
 /* sdfnmpc_solver_rollout with perception inside the loop.  Before step k with (k + phase) % every == 0 it enqueues, on the
  * solver's stream and in this order: (a) sdfnmpc_scene_pose from the solver's x0 field; (b) sdfnmpc_scene_render of
@@ -1019,9 +1032,18 @@ int sdfnmpc_solver_rollout_perceive_at(sdfnmpc_solver* s, const sdfnmpc_rollout_
  * positive excesses outside and the axis of the largest excess inside.  At a kink it is one of the one-sided values,
  * finite and of norm <= 1.  Columns 0 and 1 of h and Jh are not touched.  A set that is not dynamic takes the static
  * kernel whatever the time.  fp64, no atomics: a row does not depend on its place in the batch.  "scene_sdf_rows" in
- * sdfnmpc_ctx_kernel_stats.  x [B][N+1][10], p [B][N+1][np], h [B][N+1][3], Jh [B][N+1][10][3] device float64.
+ * sdfnmpc_ctx_kernel_stats.
+ * A mesh set created with sdfnmpc_mesh_opts.sdf_source = 1 ("scene_sdf_rows_mesh"; t0 and tau are accepted and not
+ * read): d is the value sdfnmpc_scene_distance returns for the position, bit for bit, from the same search.  grad =
+ * (p - c) / |p - c| for the closest point c of the nearest triangle (the lowest index on a tie), negated where a closed
+ * set's d is negative: a unit vector away from the surface outside, towards it inside.  At d = 0: the normalised
+ * pseudonormal of the feature c lies on (closed sets), the winning triangle's unit face normal (open sets), one-sided
+ * values.  A row whose position is not finite gives (max_df, 0).  The rows of an open set are searched only within
+ * max_df (the same bits as the full search followed by the truncation); a closed set takes the full search.
+ * x [B][N+1][10], p [B][N+1][np], h [B][N+1][3], Jh [B][N+1][10][3] device float64.
  * Asynchronous on the context stream; B == 0 is a no-op.  SDFNMPC_E_ARG (nothing is launched, outputs untouched): NULL
- * arguments, B < 0, N < 1, np < 17, max_df not > 0 or not finite, a non-finite t0, a scene on another context. */
+ * arguments, B < 0, N < 1, np < 17, max_df not > 0 or not finite, a non-finite t0, a scene on another context.
+ * SDFNMPC_E_UNSUPPORTED (the same): a mesh set created with sdf_source = 0. */
 int sdfnmpc_scene_sdf_rows(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* opts, int B, int N, int np, const double* x,
                            const double* p, double* h, double* Jh);
 

@@ -165,7 +165,9 @@ class Nmpc:
         a learned one is measured against.  ``solve`` and ``rollout`` use it from the next call on; the scene is seen at
         the time of ``set_scene_time`` (``rollout`` sets it per step).  predict: node k of the horizon sees a moving
         scene at that time + the node's own time on the shooting grid, not as a static world.  None restores the
-        network, and so does closing the scene while it is the source.  ValueError, before anything is enqueued: a batch split over several devices, a scene on another
+        network, and so does closing the scene while it is the source.  A mesh scene is taken when it was created with
+        ``Scene.mesh(..., sdf_source=True)`` (else SdfnmpcError, error -4); it is static, so ``predict`` changes nothing.
+        ValueError, before anything is enqueued: a batch split over several devices, a scene on another
         context, a ``scene_of`` that does not fit the batch, a model whose flags read no SDF."""
         if len(self.ocp.parts) != 1:
             raise ValueError("set_sdf_scene(): the batch is split over several devices; sharded batches are not built")

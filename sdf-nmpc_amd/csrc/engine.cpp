@@ -1169,8 +1169,11 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
     return SDFNMPC_OK;
 }
 
-// the scene's rows kernel: an indexed set takes the grid kernel, everything else the launch it has always taken
+// the scene's rows kernel: a mesh set takes its own, an indexed set the grid kernel, everything else the launch it has
+// always taken
 static hipError_t scene_sdf_rows_enqueue(sdfnmpc_ctx* ctx, const SceneSdfArgs& a) {
+    if (a.mesh.hdr)  // a mesh set created as an SDF source
+        return timed(ctx, "scene_sdf_rows_mesh", [&] { return launch_scene_sdf_rows_mesh(a, ctx->stream); });
     if (a.sc.ghdr && a.dyn)  // a mixed set: the grid plus movers
         return timed(ctx, "scene_sdf_rows_mixed", [&] { return launch_scene_sdf_rows_mixed(a, ctx->stream); });
     if (a.sc.ghdr) return timed(ctx, "scene_sdf_rows_grid", [&] { return launch_scene_sdf_rows_grid(a, ctx->stream); });
@@ -2936,10 +2939,11 @@ extern "C" int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nve
     if (!ctx || !nvert || !ntri || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create_mesh");
     *out = nullptr;
     if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "mesh: S must be 1..2^20");
-    const sdfnmpc_mesh_opts o = opts ? *opts : sdfnmpc_mesh_opts{0, 0};
+    const sdfnmpc_mesh_opts o = opts ? *opts : sdfnmpc_mesh_opts{0, 0, 0};
     if (!(o.leaf_size == -1 || (o.leaf_size >= 0 && o.leaf_size <= MESH_LEAF_MAX)))
         return fail(SDFNMPC_E_ARG, "mesh: leaf_size must be 1..8, 0 (the default) or -1 (no hierarchy)");
     if (o.closed != 0 && o.closed != 1) return fail(SDFNMPC_E_ARG, "mesh: closed must be 0 or 1");
+    if (o.sdf_source != 0 && o.sdf_source != 1) return fail(SDFNMPC_E_ARG, "mesh: sdf_source must be 0 or 1");
     const int leaf = o.leaf_size == 0 ? MESH_LEAF_DEFAULT : o.leaf_size;
     long long tv = 0, tt = 0;
     for (int s = 0; s < S; ++s) {
@@ -3021,6 +3025,7 @@ extern "C" int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nve
     sc->dev = SceneDev{};
     sc->dev.S = S;
     sc->is_mesh = true;
+    sc->sdf_source = o.sdf_source != 0;
     sc->mesh = MeshDev{(const MeshHdr*)d, (const MeshNode*)(d + o_nodes), (const MeshTriF*)(d + o_tf),
                        (const MeshTriD*)(d + o_td), o.closed ? (const MeshTriN*)(d + o_tn) : nullptr};
     sc->vmax.assign((size_t)S, 0.0);
@@ -3029,6 +3034,8 @@ extern "C" int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nve
 }
 
 extern "C" int sdfnmpc_scene_is_mesh(const sdfnmpc_scene* sc) { return sc && sc->is_mesh; }
+
+extern "C" int sdfnmpc_scene_is_sdf_source(const sdfnmpc_scene* sc) { return sc && (!sc->is_mesh || sc->sdf_source); }
 
 extern "C" int sdfnmpc_scene_is_indexed(const sdfnmpc_scene* sc) { return sc && sc->dev.ghdr; }
 
@@ -3247,7 +3254,7 @@ int sdfn::scene_sdf_args(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int 
         return fail(SDFNMPC_E_ARG, "scene_sdf_rows: max_df must be positive and finite");
     if (!std::isfinite(o->t0)) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: the time t0 must be finite");
     if (o->scene->ctx != ctx) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: the scene lives on another context");
-    if (o->scene->is_mesh)
+    if (o->scene->is_mesh && !o->scene->sdf_source)  // a mesh set is a source only when it was created as one
         return fail(SDFNMPC_E_UNSUPPORTED, "scene_sdf_rows: a mesh set cannot be the SDF source (meshes are rendered and "
                                            "measured, not linearised)");
     if (B > 0 && (!x || !p || !h || !Jh)) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: NULL x, p, h or Jh");
@@ -3256,6 +3263,7 @@ int sdfn::scene_sdf_args(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int 
     a.rows = (long long)B * (N + 1); a.N1 = N + 1; a.np = np;
     a.x = x; a.p = p; a.h = h; a.Jh = Jh;
     a.max_df = o->max_df; a.t0 = o->t0; a.tau = o->tau;
+    if (o->scene->is_mesh) a.mesh = o->scene->mesh;
     out = a;
     return SDFNMPC_OK;
 }

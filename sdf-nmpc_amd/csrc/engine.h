@@ -208,6 +208,7 @@ struct sdfnmpc_scene {
     // a mesh set (sdfnmpc_scene_create_mesh): MeshHdr [S] | MeshNode [nodes] | MeshTriF [tris] | MeshTriD [tris] | closed:
     // MeshTriN [tris], every block at a multiple of 16 bytes; dev carries S alone, dyn and mcount stay NULL
     bool is_mesh = false;
+    bool sdf_source = false;  // a mesh set created with sdfnmpc_mesh_opts.sdf_source = 1: accepted as the SDF source
     sdfn::MeshDev mesh{};
 };
 

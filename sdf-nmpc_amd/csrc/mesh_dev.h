@@ -1,6 +1,8 @@
 // Device code of the mesh kernels (scene_mesh.hip, and scene_swept.hip's kernel over mesh_distance): the ray's hit with
 // one triangle, the closest point of a triangle, and the two stackless walks of a scene's hierarchy (mesh_bvh.h: the
-// layout, the boxes and why the walks end).
+// layout, the boxes and why the walks end).  The distance walk is one search (mesh_search) with two epilogues: the
+// value (mesh_value) that Scene.distance, the swept kernel and the SDF rows kernel share to the bit, and its gradient
+// (mesh_gradient) for the rows kernel.
 //
 // Neither walk (nor the descent to a first leaf that precedes the distance walk) holds an array that is indexed at run
 // time: a lane carries the index of its node and nothing else of the tree, so nothing lives in scratch memory.  The trip count of the node loop is bounded by the node count before
@@ -147,22 +149,34 @@ __device__ __forceinline__ double mesh_box_d2(const MeshNode& nd, double px, dou
     return ex * ex + ey * ey + ez * ez;
 }
 
-// The distance from p to scene h: the triangle of the smallest (squared distance, original index), a node rejected
-// only when its box's squared distance is strictly greater than the best, so ties are always visited and the result
-// does not depend on the hierarchy.  An open set: sqrt(d2).  A closed set: with the sign of (p - c) . n for the
-// pseudonormal n of the winner's region, a point on the surface counted as outside (+0).  No triangles: +inf.
+// The winner of the search for the triangle nearest to p: its squared distance, the closest point c on it, the Voronoi
+// region of the triangle c lies in (tri_closest) and the triangle's place in the scene's reordered list; pos = -1 and
+// d2 = +inf when there is none.
+struct MeshHit {
+    double d2, cx, cy, cz;
+    int region, pos;
+};
+
+// The search over scene h: the triangle of the smallest (squared distance, original index) among those with a squared
+// distance <= bound, a node rejected only when its box's squared distance is strictly greater than the best, so ties
+// are always visited and the result does not depend on the hierarchy.  bound = +inf is the full search.  A finite
+// bound starts the walk with best = bound and no winner: a triangle or a node beyond it is never opened, one at or
+// below it is treated as in the full search (best never falls below the winner's d2, so neither the winner nor a box
+// above it is ever rejected), and the winner is that of the full search whenever that one's d2 <= bound -- else there
+// is none.
 //
 // A preorder walk meets the left child first wherever the point is, and with best = inf it would open most of the
 // tree before it has a bound.  So the walk is preceded by a descent to one leaf, at every inner node into the child
 // whose box is nearer (the right child of i is skip of i + 1; at most nnodes steps, no stack): the triangles of that
 // leaf give the first bound.  They are candidates like any other -- the result is still the smallest (d2, index) over a
 // set that holds every triangle with d2 <= the final best -- and the walk meets them again without effect.
-__device__ __forceinline__ double mesh_distance(const MeshDev& M, const MeshHdr& h, double px, double py, double pz) {
+__device__ __forceinline__ MeshHit mesh_search(const MeshDev& M, const MeshHdr& h, double px, double py, double pz,
+                                               double bound) {
 #pragma clang fp contract(off)
     const MeshNode* N = M.nodes + h.node_off;
     const MeshTriD* T = M.td + h.tri_off;
     const int nn = h.nnodes;
-    double best = INFINITY, bx = 0.0, by = 0.0, bz = 0.0;
+    double best = bound, bx = 0.0, by = 0.0, bz = 0.0;
     int bidx = 0x7fffffff, bpos = -1, breg = 0;
     auto leaf = [&](const MeshNode& nd) {
         const int e = min(nd.first + nd.count, h.ntri);
@@ -204,11 +218,61 @@ __device__ __forceinline__ double mesh_distance(const MeshDev& M, const MeshHdr&
         leaf(nd);
         i = nd.skip;
     }
-    const double d = sqrt(best);
-    if (!M.tn || bpos < 0) return d;
-    const double* n = M.tn[h.tri_off + bpos].n + 3 * breg;
-    const double sgn = (px - bx) * n[0] + (py - by) * n[1] + (pz - bz) * n[2];
+    return MeshHit{bpos < 0 ? (double)INFINITY : best, bx, by, bz, breg, bpos};
+}
+
+// The value of the distance at p from the winner w.  An open set: sqrt(d2).  A closed set: with the sign of (p - c) . n
+// for the pseudonormal n of the winner's region, a point on the surface counted as outside (+0).  No winner: +inf.
+__device__ __forceinline__ double mesh_value(const MeshDev& M, const MeshHdr& h, const MeshHit& w, double px, double py,
+                                             double pz) {
+#pragma clang fp contract(off)
+    const double d = sqrt(w.d2);
+    if (!M.tn || w.pos < 0) return d;
+    const double* n = M.tn[h.tri_off + w.pos].n + 3 * w.region;
+    const double sgn = (px - w.cx) * n[0] + (py - w.cy) * n[1] + (pz - w.cz) * n[2];
     return sgn < 0.0 ? -d : d;
+}
+
+// The world gradient of mesh_value at p, d the value it returned.  d2 > 0: (p - c) / sqrt(d2), negated where d < 0 -- a
+// unit vector away from the surface outside and towards it inside.  On the surface (d2 = 0) of a closed set: the
+// pseudonormal of the winner's region, normalised (the triangle's unit face normal should it vanish); of an open set:
+// the winner's unit face normal (b - a) x (c - a) / |.|, formed here from the fp64 vertices -- a one-sided value.  Always
+// finite and of norm <= 1 up to rounding; zero without a winner.
+__device__ __forceinline__ void mesh_gradient(const MeshDev& M, const MeshHdr& h, const MeshHit& w, double d, double px,
+                                              double py, double pz, double& gx, double& gy, double& gz) {
+#pragma clang fp contract(off)
+    gx = gy = gz = 0.0;
+    if (w.pos < 0) return;
+    if (w.d2 > 0.0) {
+        const double r = d < 0.0 ? -sqrt(w.d2) : sqrt(w.d2);
+        gx = (px - w.cx) / r;
+        gy = (py - w.cy) / r;
+        gz = (pz - w.cz) / r;
+        return;
+    }
+    double nx, ny, nz;
+    if (M.tn) {
+        const double* n = M.tn[h.tri_off + w.pos].n;
+        nx = n[3 * w.region], ny = n[3 * w.region + 1], nz = n[3 * w.region + 2];
+        if (!(nx * nx + ny * ny + nz * nz > 0.0)) nx = n[0], ny = n[1], nz = n[2];
+    } else {
+        const double* v = M.td[h.tri_off + w.pos].v;
+        const double ux = v[3] - v[0], uy = v[4] - v[1], uz = v[5] - v[2];
+        const double wx = v[6] - v[0], wy = v[7] - v[1], wz = v[8] - v[2];
+        nx = uy * wz - uz * wy;
+        ny = uz * wx - ux * wz;
+        nz = ux * wy - uy * wx;
+    }
+    const double l = sqrt(nx * nx + ny * ny + nz * nz);
+    if (!(l > 0.0)) return;
+    gx = nx / l;
+    gy = ny / l;
+    gz = nz / l;
+}
+
+// The distance from p to scene h (Scene.distance, the swept kernel): the full search and its value.
+__device__ __forceinline__ double mesh_distance(const MeshDev& M, const MeshHdr& h, double px, double py, double pz) {
+    return mesh_value(M, h, mesh_search(M, h, px, py, pz, INFINITY), px, py, pz);
 }
 
 }  // namespace sdfn

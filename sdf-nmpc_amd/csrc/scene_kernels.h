@@ -141,6 +141,8 @@ struct SceneSdfArgs {
     double max_df, t0;
     const double* tau;       // [N1] or nullptr: node k at time t0 + tau[k] (dynamic sets)
     const int* mcount;       // [S]: the movers of a mixed set (SceneRenderDynArgs), or nullptr
+    MeshDev mesh;            // a mesh set (launch_scene_sdf_rows_mesh; sc carries S only); last: the other kernels'
+                             // arguments stay where they were
 };
 
 // scene_swept.hip: the minimum of the scene's distance over n segments of space-time (p0, t0) -> (p1, t1), one lane each
@@ -198,9 +200,10 @@ hipError_t launch_scene_swept(const SceneSweptArgs& a, hipStream_t s);
 hipError_t launch_scene_swept_dyn(const SceneSweptArgs& a, hipStream_t s);
 hipError_t launch_scene_swept_grid(const SceneSweptArgs& a, hipStream_t s);
 hipError_t launch_scene_swept_mixed(const SceneSweptArgs& a, hipStream_t s);
-// scene_mesh.hip, and scene_swept.hip's kernel over its distance function: the three queries of a mesh set
+// scene_mesh.hip, and scene_swept.hip's kernel over its distance function: the queries of a mesh set
 hipError_t launch_scene_render_mesh(const MeshRenderArgs& a, hipStream_t s);
 hipError_t launch_scene_distance_mesh(const MeshDistArgs& a, hipStream_t s);
 hipError_t launch_scene_swept_mesh(const SceneSweptArgs& a, hipStream_t s);
+hipError_t launch_scene_sdf_rows_mesh(const SceneSdfArgs& a, hipStream_t s);  // a.mesh.hdr != nullptr
 
 }  // namespace sdfn

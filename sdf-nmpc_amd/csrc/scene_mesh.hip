@@ -1,6 +1,6 @@
-// Triangle-mesh scenes: the render and the distance of a mesh set (sdfnmpc_scene_create_mesh), each scene a static
-// triangle mesh behind a bounding-volume hierarchy that the host built once (mesh_bvh.h).  The swept clearance of a
-// mesh set is scene_swept.hip's kernel over mesh_distance.
+// Triangle-mesh scenes: the render, the distance and the SDF rows of a mesh set (sdfnmpc_scene_create_mesh), each scene
+// a static triangle mesh behind a bounding-volume hierarchy that the host built once (mesh_bvh.h).  The swept clearance
+// of a mesh set is scene_swept.hip's kernel over mesh_distance.
 //
 //   scene_render_mesh_kernel    fp32, one pixel per lane: the pixel grid, pose rounding, range and depth values, clipping
 //                               at dmax, scale and block shape of scene_render_kernel; the nearest hit over the
@@ -9,6 +9,8 @@
 //                               image is bitwise reproducible and independent of the instance's place in the batch.
 //   scene_distance_mesh_kernel  fp64, one point per lane: the distance to the nearest triangle, unsigned for an open
 //                               set, signed by the pseudonormal of the nearest feature for a closed one.
+//   scene_sdf_rows_mesh_kernel  fp64, one node row per lane: that distance and its gradient as the preparation phase's SDF
+//                               row, in scene_sdf_rows_kernel's contract (a set created with sdf_source = 1).
 //
 // A mesh is a surface, not a solid: hits are double-sided (front and back faces) with t >= 0, and there is no "camera
 // inside sees zero" convention as the primitives have -- a camera inside a closed mesh sees its inner walls.  The hit
@@ -80,7 +82,52 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_distance_mesh_kernel(MeshDi
     A.out[j] = mesh_distance(D.mesh, hd, A.points[j * 3], A.points[j * 3 + 1], A.points[j * 3 + 2]);
 }
 
+// The rows contract of scene_sdf_rows_kernel (scene_sdf.hip) from a mesh set: truncation at max_df, the flag, column 2
+// of h and of the ten Jacobian columns and nothing else.  t0 and tau are not read: a mesh set is static.
+//
+// An open set prunes at max_df: the search starts at the bound b0 = max_df^2 (1 + 2^-50) with no winner.  b0 as
+// rounded is still > max_df^2 (two roundings of 2^-53 each against 2^-50), so a triangle with d2 > b0 has an exact
+// root > max_df, its rounded root is >= max_df and the row would be truncated anyway; every triangle with d2 <= b0 is
+// searched as in the full walk (mesh_search).  So the row is that of the full search followed by the truncation, bit
+// for bit and for every hierarchy, and a row in free space opens no node beyond max_df.  A closed set takes the full
+// walk: a point deeper than max_df inside a solid has d < max_df and keeps its value, and telling it from a point far
+// outside needs the sign, which needs the nearest triangle.
+__global__ __launch_bounds__(SCENE_BLOCK) void scene_sdf_rows_mesh_kernel(SceneSdfArgs A) {
+#pragma clang fp contract(off)
+    const long long r = (long long)blockIdx.x * SCENE_BLOCK + threadIdx.x;
+    if (r >= A.rows) return;
+    const long long b = r / A.N1;
+    const long long s = A.scene_of ? (long long)min(max(A.scene_of[b], 0), A.sc.S - 1) : 0;
+    const MeshHdr hd = A.mesh.hdr[s];
+    const double* xr = A.x + r * 10;
+    const double px = xr[0], py = xr[1], pz = xr[2];
+    const double b0 = A.max_df * A.max_df * (1.0 + 0x1p-50);
+    const MeshHit w = mesh_search(A.mesh, hd, px, py, pz, A.mesh.tn ? (double)INFINITY : b0);
+    const double d = mesh_value(A.mesh, hd, w, px, py, pz);
+    // not near without a winner (d2 = +inf: no triangles, none within b0, a NaN in the row) and for an infinite
+    // coordinate, whose d2 is +inf or NaN and whose sign means nothing
+    const bool near = w.d2 < INFINITY && d < A.max_df;
+    const double df = near ? d : A.max_df;
+    double gx = 0.0, gy = 0.0, gz = 0.0;
+    if (near) mesh_gradient(A.mesh, hd, w, d, px, py, pz, gx, gy, gz);
+    const double flag = A.p[r * A.np];
+    A.h[r * 3 + 2] = flag * df + (1.0 - flag) * A.max_df;
+    double* J = A.Jh + r * 30 + 2;
+    J[0] = flag * gx;
+    J[3] = flag * gy;
+    J[6] = flag * gz;
+#pragma unroll
+    for (int j = 3; j < 10; ++j) J[j * 3] = 0.0;
+}
+
 }  // namespace
+
+hipError_t launch_scene_sdf_rows_mesh(const SceneSdfArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scene_sdf_rows_mesh_kernel, dim3((unsigned)((a.rows + SCENE_BLOCK - 1) / SCENE_BLOCK)),
+                       dim3(SCENE_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_scene_render_mesh(const MeshRenderArgs& a, hipStream_t s) {
     if (a.r.B <= 0) return hipSuccess;

@@ -631,7 +631,7 @@ extern "C" int sdfnmpc_solver_set_sdf_scene(sdfnmpc_solver* s, const sdfnmpc_sce
         return fail(SDFNMPC_E_ARG, "set_sdf_scene: no row or cost of the solver's constraint set reads the SDF");
     if (scene->ctx != s->ctx)
         return fail(SDFNMPC_E_ARG, "set_sdf_scene: the scene must live on the solver's context");
-    if (scene->is_mesh)
+    if (scene->is_mesh && !scene->sdf_source)  // a mesh set is a source only when it was created as one
         return fail(SDFNMPC_E_UNSUPPORTED, "set_sdf_scene: a mesh set cannot be the SDF source (meshes are rendered and "
                                            "measured, not linearised)");
     if (!(max_df > 0.0) || !std::isfinite(max_df))

@@ -25,7 +25,8 @@ moving obstacles go beside it: ``Scene(ctx, forest, grid=True, movers=Scene.crow
 
 A world that is a surface -- a cave, a building, terrain -- is a triangle mesh: ``Scene.mesh(ctx, Mesh.tunnel(path, 1.2))``
 holds one static ``mesh.Mesh`` per scene behind a bounding-volume hierarchy (csrc/scene_mesh.hip); ``render``,
-``distance``, ``swept_distance`` and the rollouts take it like any other scene, ``Nmpc.set_sdf_scene`` does not.
+``distance``, ``swept_distance`` and the rollouts take it like any other scene, and so does ``Nmpc.set_sdf_scene`` when
+the scene is created with ``sdf_source=True`` (csrc/scene_mesh.hip: scene_sdf_rows_mesh_kernel).
 
 World frame z up; camera frame x forward, y left, z up, the pixel grid of ``ColChecker``.  There is no CPU path.
 """
@@ -203,10 +204,11 @@ class Scene:
         self.is_dynamic = bool(_lib.load().sdfnmpc_scene_is_dynamic(self.h))
         self.is_indexed = bool(_lib.load().sdfnmpc_scene_is_indexed(self.h))
         self.is_mesh = False
+        self.is_sdf_source = bool(_lib.load().sdfnmpc_scene_is_sdf_source(self.h))  # every set that is not a mesh set
         self._set_scene_of(scene_of)
 
     @classmethod
-    def mesh(cls, ctx: "_lib.Context", meshes, scene_of=None, closed=False, leaf_size=None):
+    def mesh(cls, ctx: "_lib.Context", meshes, scene_of=None, closed=False, leaf_size=None, sdf_source=False):
         """A scene set of triangle meshes: one ``mesh.Mesh`` or a list of them (S scenes, ``scene_of`` [B] as above), each
         a static surface behind a bounding-volume hierarchy that the library builds when the scene is created
         (csrc/mesh_bvh.h) -- ``is_mesh``.  closed=False: open surfaces, ``distance`` is unsigned.  closed=True: every mesh
@@ -214,18 +216,29 @@ class Scene:
         leaf_size: 1..8 triangles per leaf (None: the library's default, 4), or -1 for no hierarchy at all -- every
         result is the same bit for bit, only slower.  ``render``, ``render_from_state``, ``distance``,
         ``swept_distance``, ``speed_bound`` (0) and ``Nmpc.rollout(scene=)`` take it like any other scene; hits are
-        double-sided, and a camera inside a closed mesh sees its inner walls.  ``Nmpc.set_sdf_scene`` refuses it
-        (SdfnmpcError), and so does the library for a malformed mesh: a non-finite vertex, an index out of range, a
-        triangle of zero area, closed=True on a surface with a boundary or a flipped triangle."""
+        double-sided, and a camera inside a closed mesh sees its inner walls.
+
+        sdf_source=True: ``Nmpc.set_sdf_scene`` (and ``_lib.scene_sdf_rows``, ``lin_args.sdf_scene``) accept the scene
+        as the controller's exact SDF -- ``is_sdf_source``: the value of ``distance`` bit for bit, truncated at max_df,
+        with the gradient (p - c) / |p - c| to the closest point c (negated inside a closed mesh); an open scene is
+        searched only within max_df of each node.  With the default False they refuse it (SdfnmpcError, error -4), as
+        they refused every mesh scene when meshes were first built: a test of the project pins that refusal for a
+        scene made by ``Scene.mesh(ctx, mesh, closed=True)`` and must keep passing as it is, so a mesh scene is a
+        source only when it is created as one.  Nothing else about the scene depends on the option.
+
+        The library refuses a malformed mesh (SdfnmpcError): a non-finite vertex, an index out of range, a triangle
+        of zero area, closed=True on a surface with a boundary or a flipped triangle, an sdf_source other than a
+        boolean (0 or 1)."""
         from .mesh import Mesh
         ms = [meshes] if isinstance(meshes, Mesh) else list(meshes)
         self = cls.__new__(cls)
         self.ctx, self.S = ctx, len(ms)
         self._sdf_users = weakref.WeakSet()
         self.h = _lib.scene_create_mesh(ctx, [m.verts for m in ms], [m.tris for m in ms],
-                                        0 if leaf_size is None else int(leaf_size), bool(closed))
+                                        0 if leaf_size is None else int(leaf_size), bool(closed), sdf_source)
         self.is_dynamic = self.is_indexed = False
         self.is_mesh = bool(_lib.load().sdfnmpc_scene_is_mesh(self.h))
+        self.is_sdf_source = bool(_lib.load().sdfnmpc_scene_is_sdf_source(self.h))
         self._set_scene_of(scene_of)
         return self
 

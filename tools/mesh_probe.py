@@ -9,7 +9,15 @@ with the hierarchy (the default leaf size, and --leaf) against leaf_size = -1, t
 every triangle -- and checks that both give the same bits.  Beside them the same three queries of a forest of as many
 cylinders behind the grid index (Scene.forest, grid=True): another world, so the comparison says what a scene of that
 many elements costs in either representation, not which is better.  The library has no diagnostic build that counts
-node visits, so none are printed.  The last line is the JSON of everything printed."""
+node visits, so none are printed.  The last line is the JSON of everything printed.
+
+--sdf: what does the mesh as the controller's exact SDF cost (scene_sdf_rows_mesh)?  On the same tunnel and heightfield,
+at N = 40 and B = 256 and 1024, the node positions are the iterate of a short rollout with the mesh source, so the rows
+of an instance are neighbours on a trajectory.  It times scene_sdf_rows_mesh on them -- the open set (searched within
+max_df only) and the same surface closed by cones over its boundary loops (the full search) -- at leaf sizes 1, 4 and -1,
+beside scene_dist_mesh on the same points and sets, the yardstick; then the time per step of a rollout with the network
+(perceiving the tunnel through the encoder, default weights) and with the mesh source, and the minimum clearance of both
+arms.  Writes profiles/mesh_sdf_probe.json."""
 import argparse
 import json
 import os
@@ -78,6 +86,138 @@ def time_scene(ctx, cfg, scene, q, a, names):
     return out, (img.numpy(), dist.numpy(), dmin.numpy(), s.numpy(), gap.numpy(), evals.numpy())
 
 
+def closed_by_cones(mesh, flip=False, apex_shift=(0.0, 0.0, 0.0)):
+    """The surface made a closed, consistently oriented manifold: every boundary loop coned to one new vertex (the mean
+    of the loop, shifted by apex_shift).  flip: every triangle reversed first."""
+    t = mesh.tris[:, ::-1] if flip else mesh.tris
+    e = set()
+    for a, b, c in t.tolist():
+        e.update(((a, b), (b, c), (c, a)))
+    nxt = {a: b for a, b in e if (b, a) not in e}
+    verts, tris = [mesh.verts], [t]
+    nv = mesh.verts.shape[0]
+    while nxt:
+        a0 = next(iter(nxt))
+        loop = [a0]
+        while True:
+            b = nxt.pop(loop[-1])
+            if b == a0:
+                break
+            loop.append(b)
+        verts.append(mesh.verts[loop].mean(0, keepdims=True) + np.asarray(apex_shift, float))
+        tris.append(np.array([(v, u, nv) for u, v in zip(loop, loop[1:] + loop[:1])], np.int32))
+        nv += 1
+    out = Mesh(np.concatenate(verts, 0), np.concatenate(tris, 0))
+    assert out.is_closed()
+    return out
+
+
+def sdf_starts(rng, B, kind):
+    """Start states [B, 10] flying along +x at 1.5 m/s, and a goal 8 m ahead: on the tunnel's axis, or 1 m above the terrain"""
+    x0 = np.zeros((B, 10))
+    x0[:, 3], x0[:, 7] = 1.0, 1.5
+    if kind == "tunnel":
+        s = rng.uniform(2.0, 45.0, B)
+        axis = lambda s: np.stack([s, 2.0 * np.sin(0.2 * s), 0.8 * np.cos(0.15 * s)], 1)
+        x0[:, :3] = axis(s) + rng.uniform(-0.8, 0.8, (B, 3))
+        goal = axis(s + 8.0)
+    else:
+        x0[:, :2] = rng.uniform(-8.0, 0.0, (B, 2))
+        x0[:, 2] = -0.4 + rng.uniform(-0.2, 0.2, B)
+        goal = x0[:, :3] + np.array([8.0, 0.0, 0.0])
+    return x0, goal
+
+
+def sdf_main(a):
+    import time
+    import torch
+    from sdf_nmpc_amd.controller import Nmpc
+    from sdf_nmpc_amd.reference import yaw2quat
+    from sdf_nmpc_amd.vae import VaeWrapper
+    N, K, max_df, name, yard = 40, 6, 1.0, "scene_sdf_rows_mesh", "scene_dist_mesh"
+    cfg = Config(mpc__N=N)
+    ter = terrain(a.grid)
+    opens = {"tunnel": tunnel(ter.tris.shape[0]), "heightfield": ter}
+    closeds = {"tunnel": closed_by_cones(opens["tunnel"], flip=True),  # the free space inside the tube is outside the solid
+               "heightfield": closed_by_cones(ter, apex_shift=(0.0, 0.0, -8.0))}
+    res = dict(N=N, max_df=max_df, reps=a.reps, rollout_steps=K, cases=[], steps=[])
+    for kind in ("tunnel", "heightfield"):
+        for B in (256, 1024):
+            n = Nmpc(cfg, batch=B)
+            ctx = n.ocp.ctx
+            ctx.enable_timing(True)
+            x0, goal = sdf_starts(np.random.default_rng(3), B, kind)
+            wps = (goal[:, None, :], np.tile(yaw2quat(0.0), (B, 1, 1)))
+            n.set_sdf_flag(1.0)
+            src = Scene.mesh(ctx, opens[kind], sdf_source=True)
+            n.set_sdf_scene(src, max_df=max_df)
+            n.set_x0(x0)
+            n.rollout(2, refs="wps", wps=wps)  # warm-up
+            n.set_x0(x0)
+            ctx.synchronize()
+            t = time.perf_counter()
+            r = n.rollout(K, refs="wps", wps=wps)
+            mesh_ms = 1e3 * (time.perf_counter() - t) / K
+            clear_mesh = r.clearance.min(1)
+            x = n.ocp.download("x")                      # the iterate: [B, N+1, 10]
+            dx = _lib.DeviceArray.from_numpy(ctx, x)
+            dpts = _lib.DeviceArray.from_numpy(ctx, np.ascontiguousarray(x[..., :3]).reshape(-1, 3))
+            rows = B * (N + 1)
+            p = np.zeros((B, N + 1, 17))
+            p[..., 0] = 1.0
+            dp, dh, dJ = _lib.DeviceArray.from_numpy(ctx, p), _lib.DeviceArray(ctx, (B, N + 1, 3)), _lib.DeviceArray(ctx, (B, N + 1, 10, 3))
+            dist = _lib.DeviceArray(ctx, (rows,))
+            n.set_sdf_scene(None)
+            src.close()
+            base = {}
+            for closed, meshes in ((False, opens), (True, closeds)):
+                for leaf in (1, 4, -1):
+                    sc = Scene.mesh(ctx, meshes[kind], closed=closed, leaf_size=leaf, sdf_source=True)
+                    ms, sp = each_ms(ctx, name, lambda: _lib.scene_sdf_rows(ctx, sc.h, B, N, 17, dx, dp, dh, dJ, max_df), a.reps)
+                    yms, ysp = each_ms(ctx, yard, lambda: _lib.scene_distance(ctx, sc.h, dpts, None, rows, dist), a.reps)
+                    h2, d = dh.numpy()[..., 2].ravel(), dist.numpy()
+                    assert np.array_equal(h2, np.where(d < max_df, d, max_df)), "rows differ from Scene.distance"
+                    got = (h2, dJ.numpy()[..., 2])
+                    if leaf == 1:
+                        base[closed] = got
+                    else:
+                        assert all(np.array_equal(u, v) for u, v in zip(got, base[closed])), f"leaf_size {leaf} differs from 1"
+                    sc.close()
+                    case = dict(scene=kind, B=B, rows=rows, closed=closed, pruned=not closed, leaf=leaf,
+                                triangles=int(meshes[kind].tris.shape[0]), rows_ms=ms, rows_spread_ms=sp, dist_ms=yms,
+                                dist_spread_ms=ysp, near_share=float((h2 < max_df).mean()))
+                    res["cases"].append(case)
+                    print(f"{kind:11s} B={B:4d} {'closed' if closed else 'open, pruned':12s} leaf {leaf:2d}: {name} {ms:9.4f} ms "
+                          f"(max - min {sp:.4f})   {yard} {yms:9.4f} ms ({ysp:.4f})   {100 * case['near_share']:.0f} % of the rows near")
+            if kind == "tunnel":  # the two arms flying the tunnel: the mesh source above, and the network perceiving the mesh
+                vae = VaeWrapper(cfg, batch=B, ctx=ctx)
+                view = Scene.mesh(ctx, opens[kind])
+                n.reset()
+                n.set_sdf_flag(1.0)
+                n.set_x0(x0)
+                n.rollout(2, refs="wps", wps=wps, scene=view, vae=vae)
+                n.set_x0(x0)
+                ctx.synchronize()
+                t = time.perf_counter()
+                r = n.rollout(K, refs="wps", wps=wps, scene=view, vae=vae)
+                net_ms = 1e3 * (time.perf_counter() - t) / K
+                pc = lambda c: [float(v) for v in np.percentile(c, (0, 5, 50))]
+                step = dict(scene=kind, B=B, K=K, mesh_source_ms_per_step=mesh_ms, network_ms_per_step=net_ms,
+                            min_clearance_p0_p5_p50_mesh_source=pc(clear_mesh), min_clearance_p0_p5_p50_network=pc(r.clearance.min(1)))
+                res["steps"].append(step)
+                print(f"{kind} B={B}: {mesh_ms:.3f} ms per step with the mesh source, {net_ms:.3f} ms with the network (perceiving every "
+                      f"step); minimum clearance p0 / p5 / p50 [m]: mesh source {np.round(pc(clear_mesh), 3).tolist()}, network "
+                      f"{np.round(step['min_clearance_p0_p5_p50_network'], 3).tolist()}")
+                view.close()
+            ctx.enable_timing(False)
+            n.ocp.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(a.out or os.path.join(ROOT, "profiles", "mesh_sdf_probe.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=101, help="vertices per side of the heightfield: 2 (grid - 1)^2 triangles")
@@ -88,8 +228,12 @@ def main():
     ap.add_argument("--leaf", type=int, nargs="*", default=[1, 8], help="leaf sizes timed beside the default")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-brute", action="store_true", help="skip leaf_size = -1 (and the check against it)")
+    ap.add_argument("--sdf", action="store_true", help="the mesh as the controller's SDF source: scene_sdf_rows_mesh")
+    ap.add_argument("--out", default=None, help="--sdf: where the JSON goes (profiles/mesh_sdf_probe.json)")
     a = ap.parse_args()
     warnings.filterwarnings("ignore")
+    if a.sdf:
+        return sdf_main(a)
     import torch
     cfg = Config()
     ctx = _lib.Context(0, stream=torch.cuda.current_stream().cuda_stream)
