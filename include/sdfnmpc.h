@@ -92,7 +92,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 17
+#define SDFNMPC_ABI_VERSION 18
 
 enum {
     SDFNMPC_OK = 0,
@@ -963,8 +963,9 @@ int sdfnmpc_scene_create_mixed(sdfnmpc_ctx* ctx, int S, const int* count, const 
  * becomes a source only when it is created as one.
  * SDFNMPC_E_ARG (nothing is allocated on the device) also: a sdf_source other than 0 or 1.
  * SDFNMPC_E_UNSUPPORTED, nothing launched, outputs untouched: a mesh set created with sdf_source = 0 given to
- * sdfnmpc_scene_sdf_rows, sdfnmpc_lin_args.sdf_scene or sdfnmpc_solver_set_sdf_scene.  Not built: movers beside a mesh,
- * meshes mixed with primitives in one scene, a walk pruned at max_df for closed sets. */
+ * sdfnmpc_scene_sdf_rows, sdfnmpc_lin_args.sdf_scene or sdfnmpc_solver_set_sdf_scene.  Movers beside a mesh:
+ * sdfnmpc_scene_create_mesh_mixed below.  Not built: moving or deforming meshes, meshes mixed with static primitives in
+ * one scene, a walk pruned at max_df (or at the movers' distance) for closed sets. */
 #define SDFNMPC_MESH_MAX_TRIS (1 << 20)  /* per scene */
 #define SDFNMPC_MESH_MAX_VERTS (1 << 21) /* per scene */
 typedef struct {
@@ -979,6 +980,36 @@ int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nvert, const d
                               const int* tris, const sdfnmpc_mesh_opts* opts, sdfnmpc_scene** out);
 int sdfnmpc_scene_is_mesh(const sdfnmpc_scene* scene);
 int sdfnmpc_scene_is_sdf_source(const sdfnmpc_scene* scene);
+
+/* ---- a mesh world with a few moving obstacles: mesh sets with movers (csrc/scene_mesh.hip) ----
+ * sdfnmpc_scene_create_mesh_mixed is sdfnmpc_scene_create_mesh (nvert, verts, ntri, tris, opts: the same arguments,
+ * checks, rounding and hierarchy) with a mover set beside every scene, exactly as sdfnmpc_scene_create_mixed puts one
+ * beside a grid: mcount [S] primitives per scene, 0..SDFNMPC_SCENE_MAX_PRIMS, mprims [sum of mcount] and mmotion [sum
+ * of mcount] as sdfnmpc_scene_create_moving takes and checks them (mmotion == NULL: no motion; such primitives are
+ * still movers).  The movers are not in the hierarchy: they may be anywhere, overlap the mesh, or be all a scene has
+ * (ntri[s] == 0).
+ * Every query of such a handle is the minimum over the mesh and the movers at the query's time, bit for bit the
+ * combination of the mesh set alone (sdfnmpc_scene_create_mesh, the same options) and of the movers as a dynamic set
+ * of their own (sdfnmpc_scene_create_moving): the pixelwise minimum of the images, the minimum of the distances
+ * (times [j] per point), and in the SDF row the movers' (h, J_h) only where their h is strictly below the mesh's -- on
+ * a tie the mesh comes before a mover; within the mesh the lowest original triangle index wins, within the movers the
+ * lowest mover index.  A closed mesh gives a signed value, a point inside a mover a negative one: the minimum is the
+ * union.  sdfnmpc_scene_render(_at), sdfnmpc_scene_distance(_at), sdfnmpc_scene_swept_distance (its Lipschitz constant
+ * takes the movers' speed bound), and for a set created with opts->sdf_source = 1 sdfnmpc_scene_sdf_rows,
+ * sdfnmpc_lin_args.sdf_scene, sdfnmpc_solver_set_sdf_scene (predict as for a dynamic set) and every rollout of such a
+ * solver take the handle; with sdf_source = 0 those three refuse it as they refuse a mesh set.  The kernels are
+ * "scene_render_mesh_mixed", "scene_dist_mesh_mixed", "scene_sdf_rows_mesh_mixed" and "scene_swept_mesh_mixed" in
+ * sdfnmpc_ctx_kernel_stats: they evaluate the movers first and start the walk of the hierarchy from what they give (an
+ * open set's distance walk is pruned at the movers' distance; a closed set takes the full walk, for the sign).
+ * With a mover in some scene sdfnmpc_scene_is_mesh and sdfnmpc_scene_is_dynamic are 1, sdfnmpc_scene_is_indexed is 0 and
+ * sdfnmpc_scene_speed_bound gives the movers' bound per scene.  With every mcount[s] == 0 the handle is what
+ * sdfnmpc_scene_create_mesh returns (not dynamic, the mesh kernels under their names).
+ * SDFNMPC_E_ARG (nothing is allocated on the device): what sdfnmpc_scene_create_mesh refuses of the mesh arguments, what
+ * sdfnmpc_scene_create_moving refuses of the movers, an mcount[s] outside 0..SDFNMPC_SCENE_MAX_PRIMS, NULL mcount.
+ * Not built: more than 32 movers per scene. */
+int sdfnmpc_scene_create_mesh_mixed(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts, const int* ntri,
+                                    const int* tris, const sdfnmpc_mesh_opts* opts, const int* mcount,
+                                    const sdfnmpc_prim* mprims, const sdfnmpc_prim_motion* mmotion, sdfnmpc_scene** out);
 
 /* sdfnmpc_solver_rollout with perception inside the loop.  Before step k with (k + phase) % every == 0 it enqueues, on the
  * solver's stream and in this order: (a) sdfnmpc_scene_pose from the solver's x0 field; (b) sdfnmpc_scene_render of

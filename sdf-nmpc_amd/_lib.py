@@ -51,6 +51,7 @@ SYMBOLS = [
     "sdfnmpc_vehicle_x_true", "sdfnmpc_plant_step_vehicle", "sdfnmpc_vehicle_set_body", "sdfnmpc_vehicle_body_state",
     "sdfnmpc_scene_swept_distance", "sdfnmpc_scene_speed_bound",
     "sdfnmpc_scene_create_mesh", "sdfnmpc_scene_is_mesh", "sdfnmpc_scene_is_sdf_source",
+    "sdfnmpc_scene_create_mesh_mixed",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -310,6 +311,8 @@ def load():
         "sdfnmpc_scene_swept_distance": (i, [vp, vp, vp, vp, vp, vp, vp, ll, d, i, vp, vp, vp, vp]),
         "sdfnmpc_scene_speed_bound": (i, [vp, P(d)]),
         "sdfnmpc_scene_create_mesh": (i, [vp, i, P(i), P(d), P(i), P(i), P(MeshOptsC), P(vp)]),
+        "sdfnmpc_scene_create_mesh_mixed": (i, [vp, i, P(i), P(d), P(i), P(i), P(MeshOptsC), P(i), P(PrimC),
+                                                P(PrimMotionC), P(vp)]),
         "sdfnmpc_scene_is_mesh": (i, [vp]),
         "sdfnmpc_scene_is_sdf_source": (i, [vp]),
         "sdfnmpc_solver_rollout_perceive_at": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d]),
@@ -338,7 +341,7 @@ def load():
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 17:
+    if lib.sdfnmpc_abi_version() != 18:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -902,11 +905,14 @@ def scene_create_large(ctx: "Context", counts, prims, cell: float = 0.0):
     return h
 
 
-def scene_create_mesh(ctx: "Context", verts, tris, leaf_size: int = 0, closed: bool = False, sdf_source=False):
+def scene_create_mesh(ctx: "Context", verts, tris, leaf_size: int = 0, closed: bool = False, sdf_source=False,
+                      mcounts=None, mprims=None, mmotion=None):
     """sdfnmpc_scene_create_mesh: one (verts [nv, 3] float64, tris [nt, 3] int32) pair per scene, the indices local to
     the scene; leaf_size 1..8, 0 (the default) or -1 (no hierarchy); closed: signed distance, and the library checks
     that every scene is a closed, consistently oriented manifold; sdf_source: the set is accepted as a controller's SDF
-    source (False, True or the integer the library is to see: it refuses all but 0 and 1).  Returns the handle."""
+    source (False, True or the integer the library is to see: it refuses all but 0 and 1).  Returns the handle.
+    mcounts [S] (not None): sdfnmpc_scene_create_mesh_mixed, with mcounts movers per scene (at most 32 each) beside the
+    meshes, mprims / mmotion as scene_create takes prims / motion (mmotion None: no motion records)."""
     vs = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3) for v in verts]
     ts = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1, 3) for t in tris]
     nv = (C.c_int * len(vs))(*[v.shape[0] for v in vs])
@@ -915,6 +921,12 @@ def scene_create_mesh(ctx: "Context", verts, tris, leaf_size: int = 0, closed: b
     ta = np.ascontiguousarray(np.concatenate(ts, 0)) if ts else np.zeros((0, 3), np.int32)
     o = MeshOptsC(int(leaf_size), int(bool(closed)), int(sdf_source))
     h = C.c_void_p()
+    if mcounts is not None:
+        mc = (C.c_int * len(mcounts))(*[int(c) for c in mcounts])
+        _check(load().sdfnmpc_scene_create_mesh_mixed(
+            ctx.h, len(vs), nv, va.ctypes.data_as(C.POINTER(C.c_double)), nt, ta.ctypes.data_as(C.POINTER(C.c_int)),
+            C.byref(o), mc, _prims_c(mprims), None if mmotion is None else _motion_c(mmotion, len(mprims)), C.byref(h)))
+        return h
     _check(load().sdfnmpc_scene_create_mesh(ctx.h, len(vs), nv, va.ctypes.data_as(C.POINTER(C.c_double)), nt,
                                             ta.ctypes.data_as(C.POINTER(C.c_int)), C.byref(o), C.byref(h)))
     return h

@@ -166,7 +166,8 @@ class Nmpc:
         the time of ``set_scene_time`` (``rollout`` sets it per step).  predict: node k of the horizon sees a moving
         scene at that time + the node's own time on the shooting grid, not as a static world.  None restores the
         network, and so does closing the scene while it is the source.  A mesh scene is taken when it was created with
-        ``Scene.mesh(..., sdf_source=True)`` (else SdfnmpcError, error -4); it is static, so ``predict`` changes nothing.
+        ``Scene.mesh(..., sdf_source=True)`` (else SdfnmpcError, error -4); without ``movers=`` it is static, so
+        ``predict`` changes nothing, with them ``predict`` shows every node the movers at its own time.
         ValueError, before anything is enqueued: a batch split over several devices, a scene on another
         context, a ``scene_of`` that does not fit the batch, a model whose flags read no SDF."""
         if len(self.ocp.parts) != 1:

@@ -1172,6 +1172,8 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
 // the scene's rows kernel: a mesh set takes its own, an indexed set the grid kernel, everything else the launch it has
 // always taken
 static hipError_t scene_sdf_rows_enqueue(sdfnmpc_ctx* ctx, const SceneSdfArgs& a) {
+    if (a.mesh.hdr && a.dyn)  // a mesh set with movers, created as an SDF source
+        return timed(ctx, "scene_sdf_rows_mesh_mixed", [&] { return launch_scene_sdf_rows_mesh_mixed(a, ctx->stream); });
     if (a.mesh.hdr)  // a mesh set created as an SDF source
         return timed(ctx, "scene_sdf_rows_mesh", [&] { return launch_scene_sdf_rows_mesh(a, ctx->stream); });
     if (a.sc.ghdr && a.dyn)  // a mixed set: the grid plus movers
@@ -2934,8 +2936,12 @@ extern "C" int sdfnmpc_scene_create_mixed(sdfnmpc_ctx* ctx, int S, const int* co
 
 // Mesh sets (scene_mesh.hip): S static triangle meshes, each checked, rounded to fp32 and put behind a hierarchy here on
 // the host (mesh_bvh.h: the layout, the split rule, the boxes and their margin)
-extern "C" int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts, const int* ntri,
-                                         const int* tris, const sdfnmpc_mesh_opts* opts, sdfnmpc_scene** out) {
+// mcount == NULL: the mesh set of sdfnmpc_scene_create_mesh.  Otherwise mcount [S] in 0..32, mprims and mmotion (or
+// NULL) already checked by the caller: the movers of sdfnmpc_scene_create_mesh_mixed, appended to the device image as
+// mcount [S] | ScenePrimDyn [S][32] | vmax [S], as scene_create_indexed appends them to a grid's
+static int scene_create_mesh_set(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts, const int* ntri,
+                                 const int* tris, const sdfnmpc_mesh_opts* opts, const int* mcount,
+                                 const sdfnmpc_prim* mprims, const sdfnmpc_prim_motion* mmotion, sdfnmpc_scene** out) {
     if (!ctx || !nvert || !ntri || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create_mesh");
     *out = nullptr;
     if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "mesh: S must be 1..2^20");
@@ -3003,7 +3009,21 @@ extern "C" int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nve
     const size_t o_tf = up16(o_nodes + nodes.size() * sizeof(MeshNode));
     const size_t o_td = up16(o_tf + tf.size() * sizeof(MeshTriF));
     const size_t o_tn = up16(o_td + td.size() * sizeof(MeshTriD));
-    const size_t bytes = up16(o_tn + tn.size() * sizeof(MeshTriN)) + 16;
+    const size_t o_mc = up16(o_tn + tn.size() * sizeof(MeshTriN)) + 16;  // the mesh set's image ends here
+    const size_t o_dyn = up16(o_mc + (size_t)S * sizeof(int));
+    const size_t o_vmax = o_dyn + (size_t)S * SCENE_MAX_PRIMS * sizeof(ScenePrimDyn);  // the movers' speed bounds [S]
+    static_assert(SCENE_MAX_PRIMS * sizeof(ScenePrimDyn) % 16 == 0, "fp64 alignment of the speed bounds");
+    const size_t bytes = mcount ? o_vmax + (size_t)S * sizeof(double) : o_mc;
+    std::vector<double> vmax((size_t)S, 0.0);
+    std::vector<ScenePrimDyn> hm;
+    if (mcount) {
+        hm.assign((size_t)S * SCENE_MAX_PRIMS, ScenePrimDyn{});
+        const sdfnmpc_prim* q = mprims;
+        for (int s = 0; s < S; ++s)
+            for (int i = 0; i < mcount[s]; ++i, ++q)
+                scene_dyn_fill(hm[(size_t)s * SCENE_MAX_PRIMS + i], q, mmotion ? mmotion + (q - mprims) : nullptr);
+        scene_speed_bounds(hm.data(), S, mcount, vmax.data());
+    }
     ScopedDevice sd(ctx->device);
     auto* sc = new sdfnmpc_scene();
     sc->device = ctx->device; sc->ctx = ctx; sc->S = S;
@@ -3017,6 +3037,11 @@ extern "C" int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nve
     put(o_tf, tf.data(), tf.size() * sizeof(MeshTriF));
     put(o_td, td.data(), td.size() * sizeof(MeshTriD));
     put(o_tn, tn.data(), tn.size() * sizeof(MeshTriN));
+    if (mcount) {
+        put(o_mc, mcount, (size_t)S * sizeof(int));
+        put(o_dyn, hm.data(), hm.size() * sizeof(ScenePrimDyn));
+        put(o_vmax, vmax.data(), (size_t)S * sizeof(double));
+    }
     if (e != hipSuccess) {
         if (sc->dmem) (void)hipFree(sc->dmem);
         delete sc;
@@ -3028,9 +3053,47 @@ extern "C" int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nve
     sc->sdf_source = o.sdf_source != 0;
     sc->mesh = MeshDev{(const MeshHdr*)d, (const MeshNode*)(d + o_nodes), (const MeshTriF*)(d + o_tf),
                        (const MeshTriD*)(d + o_td), o.closed ? (const MeshTriN*)(d + o_tn) : nullptr};
-    sc->vmax.assign((size_t)S, 0.0);
+    sc->vmax = std::move(vmax);
+    if (mcount) {
+        sc->mcount = (const int*)(d + o_mc);
+        sc->dyn = (const ScenePrimDyn*)(d + o_dyn);
+        sc->dvmax = (const double*)(d + o_vmax);
+    }
     *out = sc;
     return SDFNMPC_OK;
+}
+
+extern "C" int sdfnmpc_scene_create_mesh(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts, const int* ntri,
+                                         const int* tris, const sdfnmpc_mesh_opts* opts, sdfnmpc_scene** out) {
+    return scene_create_mesh_set(ctx, S, nvert, verts, ntri, tris, opts, nullptr, nullptr, nullptr, out);
+}
+
+// A mesh set plus up to 32 movers per scene (scene_mesh.hip's *_mesh_mixed kernels).  The movers are checked here as
+// sdfnmpc_scene_create_mixed checks its own, the mesh by the builder of sdfnmpc_scene_create_mesh; without a mover in
+// any scene the handle is that function's
+extern "C" int sdfnmpc_scene_create_mesh_mixed(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts,
+                                               const int* ntri, const int* tris, const sdfnmpc_mesh_opts* opts,
+                                               const int* mcount, const sdfnmpc_prim* mprims,
+                                               const sdfnmpc_prim_motion* mmotion, sdfnmpc_scene** out) {
+    if (!ctx || !nvert || !ntri || !mcount || !out)
+        return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create_mesh_mixed");
+    *out = nullptr;
+    if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "mesh: S must be 1..2^20");
+    long long mtotal = 0;
+    for (int s = 0; s < S; ++s) {
+        if (mcount[s] < 0 || mcount[s] > SCENE_MAX_PRIMS)
+            return fail(SDFNMPC_E_ARG, "scene: at most 32 movers per scene (and no negative count)");
+        mtotal += mcount[s];
+    }
+    if (mtotal > 0 && !mprims) return fail(SDFNMPC_E_ARG, "scene: NULL movers");
+    bool dynamic = false;
+    if (int rc = scene_motion_check(mmotion, mtotal, &dynamic)) return rc;
+    for (long long i = 0; i < mtotal; ++i) {
+        int na;
+        if (int rc = scene_prim_check(mprims + i, &na)) return rc;
+    }
+    // a mover without motion still takes the mover path: the set has movers as soon as it holds one
+    return scene_create_mesh_set(ctx, S, nvert, verts, ntri, tris, opts, mtotal > 0 ? mcount : nullptr, mprims, mmotion, out);
 }
 
 extern "C" int sdfnmpc_scene_is_mesh(const sdfnmpc_scene* sc) { return sc && sc->is_mesh; }
@@ -3091,6 +3154,12 @@ static int scene_render_static(sdfnmpc_ctx* ctx, const SceneRenderArgs& a) {
 
 // the scene at time t: a static set takes the launch above whatever t is, a dynamic one its own kernel
 int sdfn::scene_render_launch(sdfnmpc_ctx* ctx, const sdfnmpc_scene& sc, const SceneRenderArgs& a, double t) {
+    if (sc.is_mesh && sc.dyn) {  // a mesh set with movers, at time t
+        const MeshRenderMixedArgs ma{a, sc.mesh, sc.dyn, sc.mcount, t};
+        ScopedDevice sd(ctx->device);
+        HIPCHK(timed(ctx, "scene_render_mesh_mixed", [&] { return launch_scene_render_mesh_mixed(ma, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (sc.is_mesh) {  // a mesh set is static: the time does not matter
         const MeshRenderArgs ma{a, sc.mesh};
         ScopedDevice sd(ctx->device);
@@ -3169,6 +3238,11 @@ extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* 
     if (!points || !out) return fail(SDFNMPC_E_ARG, "scene_distance: NULL points or output");
     SceneDistArgs a{sc->dev, points, p_to_scene, n, std::max(1LL, n / sc->S), out};
     ScopedDevice sd(ctx->device);
+    if (sc->is_mesh && sc->dyn) {  // a mesh set with movers, at the points' times
+        const MeshDistMixedArgs ma{a, sc->mesh, sc->dyn, sc->mcount, times};
+        HIPCHK(timed(ctx, "scene_dist_mesh_mixed", [&] { return launch_scene_distance_mesh_mixed(ma, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (sc->is_mesh) {  // a mesh set is static: the times do not matter
         const MeshDistArgs ma{a, sc->mesh};
         HIPCHK(timed(ctx, "scene_dist_mesh", [&] { return launch_scene_distance_mesh(ma, ctx->stream); }));
@@ -3217,6 +3291,11 @@ extern "C" int sdfnmpc_scene_swept_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scen
     a.eps = eps; a.max_evals = max_evals;
     a.dmin = dmin; a.s = s; a.gap = gap; a.evals = evals;
     ScopedDevice sd(ctx->device);
+    if (sc->is_mesh && sc->dyn) {
+        a.mesh = sc->mesh;
+        HIPCHK(timed(ctx, "scene_swept_mesh_mixed", [&] { return launch_scene_swept_mesh_mixed(a, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (sc->is_mesh) {
         a.mesh = sc->mesh;
         HIPCHK(timed(ctx, "scene_swept_mesh", [&] { return launch_scene_swept_mesh(a, ctx->stream); }));

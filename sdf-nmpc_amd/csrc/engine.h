@@ -206,7 +206,9 @@ struct sdfnmpc_scene {
     // | ScenePrimF [total] | cell_start | cell_items, every block at a multiple of 16 bytes; a mixed set
     // (sdfnmpc_scene_create_mixed; dev.ghdr and dyn both non-NULL) appends mcount [S] | ScenePrimDyn [S][32] | vmax [S]
     // a mesh set (sdfnmpc_scene_create_mesh): MeshHdr [S] | MeshNode [nodes] | MeshTriF [tris] | MeshTriD [tris] | closed:
-    // MeshTriN [tris], every block at a multiple of 16 bytes; dev carries S alone, dyn and mcount stay NULL
+    // MeshTriN [tris], every block at a multiple of 16 bytes; dev carries S alone, dyn and mcount stay NULL; a mesh set
+    // with movers (sdfnmpc_scene_create_mesh_mixed; is_mesh and dyn non-NULL) appends mcount [S] | ScenePrimDyn [S][32] |
+    // vmax [S]
     bool is_mesh = false;
     bool sdf_source = false;  // a mesh set created with sdfnmpc_mesh_opts.sdf_source = 1: accepted as the SDF source
     sdfn::MeshDev mesh{};

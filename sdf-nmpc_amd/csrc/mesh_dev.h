@@ -63,13 +63,16 @@ __device__ __forceinline__ float mesh_tri_hit(float best, const MeshTriF& T, flo
 
 // The nearest hit of the ray over scene h: preorder, to skip when the node's slab interval (clipped to t >= 0) is empty
 // or begins beyond the best hit, to the next node when it is inner, through its triangles when it is a leaf.
+// best: what the walk starts from, the hit of something that is not in the hierarchy (the movers of
+// scene_render_mesh_mixed_kernel); the result is fminf(best, the walk's own result from +inf).  A smaller best only
+// rejects more nodes and triangles, each because its interval begins beyond best, and a triangle's hit is clamped into
+// its interval, so what is rejected could not have lowered best.
 __device__ __forceinline__ float mesh_ray_cast(const MeshDev& M, const MeshHdr& h, float ox, float oy, float oz, float dx,
-                                               float dy, float dz, float ix, float iy, float iz) {
+                                               float dy, float dz, float ix, float iy, float iz, float best = INFINITY) {
     const MeshNode* N = M.nodes + h.node_off;
     const MeshTriF* T = M.tf + h.tri_off;
     const int nn = h.nnodes;
     const float m = h.margin;
-    float best = INFINITY;
     int i = 0;
     for (int it = 0; it < nn && i < nn; ++it) {
         const MeshNode nd = N[i];
@@ -273,6 +276,24 @@ __device__ __forceinline__ void mesh_gradient(const MeshDev& M, const MeshHdr& h
 // The distance from p to scene h (Scene.distance, the swept kernel): the full search and its value.
 __device__ __forceinline__ double mesh_distance(const MeshDev& M, const MeshHdr& h, double px, double py, double pz) {
     return mesh_value(M, h, mesh_search(M, h, px, py, pz, INFINITY), px, py, pz);
+}
+
+// The distance from p at time t to scene h of a mesh set with movers (scene_distance_mesh_mixed_kernel, the swept
+// kernel): the minimum of mesh_distance and of frame_distance over the scene's mcnt movers P, the bits of
+// fmin(mesh_distance, the movers' minimum).  The movers come first and give d_m.  An open set is searched only up to
+// d_m: with d_m < 0 not at all (its distance is >= 0), else with the bound d_m^2 (1 + 2^-50), which as rounded is still
+// > d_m^2 -- a triangle beyond it has a correctly rounded root strictly above d_m and can neither lower the minimum nor
+// tie with it, and every triangle at or below it is treated as in the full search (mesh_search).  A closed set takes
+// the full walk: its sign needs the nearest triangle, however far that is.
+__device__ __forceinline__ double mesh_mixed_distance(const MeshDev& M, const MeshHdr& h, const ScenePrimDyn* P, int mcnt,
+                                                      double t, double px, double py, double pz) {
+#pragma clang fp contract(off)
+    double dm = INFINITY;
+    for (int i = 0; i < mcnt; ++i) dm = fmin(dm, frame_distance(P[i], t, px, py, pz));
+    if (M.tn) return fmin(mesh_distance(M, h, px, py, pz), dm);
+    if (dm < 0.0) return dm;
+    const MeshHit w = mesh_search(M, h, px, py, pz, dm * dm * (1.0 + 0x1p-50));
+    return fmin(sqrt(w.d2), dm);
 }
 
 }  // namespace sdfn

@@ -175,6 +175,23 @@ struct MeshDistArgs {
     SceneDistArgs d;
     MeshDev mesh;
 };
+// scene_mesh.hip: a mesh set with movers (sdfnmpc_scene_create_mesh_mixed): dyn holds mcount[s] <= SCENE_MAX_PRIMS movers
+// per scene beside the mesh.  Structures of their own: the mesh kernels' arguments stay where they were.  The rows and
+// the swept kernel of such a set read dyn, mcount and mesh of SceneSdfArgs / SceneSweptArgs, all three non-null
+struct MeshRenderMixedArgs {
+    SceneRenderArgs r;
+    MeshDev mesh;
+    const ScenePrimDyn* dyn; // [S][SCENE_MAX_PRIMS]
+    const int* mcount;       // [S]
+    double t;
+};
+struct MeshDistMixedArgs {
+    SceneDistArgs d;
+    MeshDev mesh;
+    const ScenePrimDyn* dyn; // [S][SCENE_MAX_PRIMS]
+    const int* mcount;       // [S]
+    const double* times;     // [n] or nullptr (t = 0)
+};
 
 inline size_t scene_render_lds_bytes(int h, int w, int is_spherical) {
     return is_spherical ? (size_t)2 * ((size_t)h + (size_t)w) * sizeof(float) : 0;
@@ -205,5 +222,10 @@ hipError_t launch_scene_render_mesh(const MeshRenderArgs& a, hipStream_t s);
 hipError_t launch_scene_distance_mesh(const MeshDistArgs& a, hipStream_t s);
 hipError_t launch_scene_swept_mesh(const SceneSweptArgs& a, hipStream_t s);
 hipError_t launch_scene_sdf_rows_mesh(const SceneSdfArgs& a, hipStream_t s);  // a.mesh.hdr != nullptr
+// the same four of a mesh set with movers: the minimum over the mesh and the movers at the query's time
+hipError_t launch_scene_render_mesh_mixed(const MeshRenderMixedArgs& a, hipStream_t s);
+hipError_t launch_scene_distance_mesh_mixed(const MeshDistMixedArgs& a, hipStream_t s);
+hipError_t launch_scene_swept_mesh_mixed(const SceneSweptArgs& a, hipStream_t s);
+hipError_t launch_scene_sdf_rows_mesh_mixed(const SceneSdfArgs& a, hipStream_t s);  // a.mesh.hdr, a.dyn, a.mcount
 
 }  // namespace sdfn

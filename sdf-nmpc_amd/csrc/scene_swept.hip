@@ -103,6 +103,18 @@ struct EvalMesh {  // scene_distance_mesh_kernel: a static set of triangles, sig
     __device__ double operator()(double px, double py, double pz, double) const { return mesh_distance(M, h, px, py, pz); }
 };
 
+struct EvalMeshMixed {  // scene_distance_mesh_mixed_kernel: the movers first, then the mesh searched from what they give
+    const MeshDev& M;
+    MeshHdr h;
+    const ScenePrimDyn* P;
+    int mcnt;
+    __device__ EvalMeshMixed(const SceneSweptArgs& A, long long s)
+        : M(A.mesh), h(A.mesh.hdr[s]), P(A.dyn + s * SCENE_MAX_PRIMS), mcnt(min(max(A.mcount[s], 0), SCENE_MAX_PRIMS)) {}
+    __device__ double operator()(double px, double py, double pz, double t) const {
+        return mesh_mixed_distance(M, h, P, mcnt, t, px, py, pz);
+    }
+};
+
 __device__ __forceinline__ bool finite3(const double* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
 
 // TIMED: the set is dynamic, so the times are read and the movers' speed bound enters L
@@ -194,5 +206,8 @@ hipError_t launch_scene_swept_dyn(const SceneSweptArgs& a, hipStream_t s) { retu
 hipError_t launch_scene_swept_grid(const SceneSweptArgs& a, hipStream_t s) { return launch_swept<EvalGrid, false>(a, s); }
 hipError_t launch_scene_swept_mixed(const SceneSweptArgs& a, hipStream_t s) { return launch_swept<EvalMixed, true>(a, s); }
 hipError_t launch_scene_swept_mesh(const SceneSweptArgs& a, hipStream_t s) { return launch_swept<EvalMesh, false>(a, s); }
+hipError_t launch_scene_swept_mesh_mixed(const SceneSweptArgs& a, hipStream_t s) {
+    return launch_swept<EvalMeshMixed, true>(a, s);
+}
 
 }  // namespace sdfn

@@ -26,7 +26,8 @@ moving obstacles go beside it: ``Scene(ctx, forest, grid=True, movers=Scene.crow
 A world that is a surface -- a cave, a building, terrain -- is a triangle mesh: ``Scene.mesh(ctx, Mesh.tunnel(path, 1.2))``
 holds one static ``mesh.Mesh`` per scene behind a bounding-volume hierarchy (csrc/scene_mesh.hip); ``render``,
 ``distance``, ``swept_distance`` and the rollouts take it like any other scene, and so does ``Nmpc.set_sdf_scene`` when
-the scene is created with ``sdf_source=True`` (csrc/scene_mesh.hip: scene_sdf_rows_mesh_kernel).
+the scene is created with ``sdf_source=True`` (csrc/scene_mesh.hip: scene_sdf_rows_mesh_kernel).  Something crossing
+the vehicle's path goes beside it: ``Scene.mesh(ctx, tunnel, movers=[Scene.moving(Scene.sphere(c, 0.4), v=v)])``.
 
 World frame z up; camera frame x forward, y left, z up, the pixel grid of ``ColChecker``.  There is no CPU path.
 """
@@ -44,6 +45,35 @@ def _three(a, name):
     if len(a) != 3:
         raise ValueError(f"Scene.moving: {name} has three components")
     return a
+
+
+def _is_prim(p):
+    return isinstance(p, tuple) and len(p) in (2, 3) and isinstance(p[0], (str, int))
+
+
+def _flatten(scenes):
+    """lists of primitives, one per scene -> (flat list of (kind, values), one motion dict or None per primitive)"""
+    flat, motion = [], []
+    for s in scenes:
+        for kind, vals, *mo in s:
+            vals = list(vals)
+            if len(vals) > 6:
+                raise ValueError(f"primitive {kind!r}: at most 6 values, got {len(vals)}")
+            # an unknown kind goes to the library as it is (it refuses it)
+            flat.append((_lib.PRIM_KINDS.get(kind, kind if isinstance(kind, int) else -1), vals))
+            motion.append(mo[0] if mo else None)
+    return flat, motion
+
+
+def _mover_lists(movers, S):
+    """``movers`` as Scene and Scene.mesh take it -> one list per scene: an empty list is no mover anywhere, a flat list
+    of primitives the movers of a single scene, else one list per scene (ValueError when their number is not S)"""
+    movers = list(movers)
+    mlists = [[] for _ in range(S)] if not movers else \
+        [movers] if all(_is_prim(p) for p in movers) else [list(m) for m in movers]
+    if len(mlists) != S:
+        raise ValueError(f"Scene: movers holds {len(mlists)} lists for {S} scenes")
+    return mlists
 
 
 class Swept:
@@ -157,22 +187,8 @@ class Scene:
         return out
 
     def __init__(self, ctx: "_lib.Context", prims, scene_of=None, grid=False, cell=None, movers=None):
-        is_prim = lambda p: isinstance(p, tuple) and len(p) in (2, 3) and isinstance(p[0], (str, int))
-
-        def flatten(scenes):
-            flat, motion = [], []
-            for s in scenes:
-                for kind, vals, *mo in s:
-                    vals = list(vals)
-                    if len(vals) > 6:
-                        raise ValueError(f"primitive {kind!r}: at most 6 values, got {len(vals)}")
-                    # an unknown kind goes to the library as it is (it refuses it)
-                    flat.append((_lib.PRIM_KINDS.get(kind, kind if isinstance(kind, int) else -1), vals))
-                    motion.append(mo[0] if mo else None)
-            return flat, motion
-
-        scenes = [list(prims)] if all(is_prim(p) for p in prims) else [list(s) for s in prims]
-        flat, motion = flatten(scenes)
+        scenes = [list(prims)] if all(_is_prim(p) for p in prims) else [list(s) for s in prims]
+        flat, motion = _flatten(scenes)
         self.ctx, self.S = ctx, len(scenes)
         self._sdf_users = weakref.WeakSet()  # controllers whose SDF source this scene is (Nmpc.set_sdf_scene)
         if movers is not None and not grid:
@@ -187,12 +203,8 @@ class Scene:
             if movers is None:  # the call an indexed scene has always made
                 self.h = _lib.scene_create_large(ctx, [len(s) for s in scenes], flat, cell)
             else:
-                movers = list(movers)
-                mlists = [[] for _ in scenes] if not movers else \
-                    [movers] if all(is_prim(p) for p in movers) else [list(m) for m in movers]
-                if len(mlists) != len(scenes):
-                    raise ValueError(f"Scene: movers holds {len(mlists)} lists for {len(scenes)} scenes")
-                mflat, mmotion = flatten(mlists)
+                mlists = _mover_lists(movers, len(scenes))
+                mflat, mmotion = _flatten(mlists)
                 self.h = _lib.scene_create_mixed(ctx, [len(s) for s in scenes], flat, cell, [len(m) for m in mlists],
                                                  mflat, mmotion if any(m is not None for m in mmotion) else None)
         else:
@@ -208,7 +220,7 @@ class Scene:
         self._set_scene_of(scene_of)
 
     @classmethod
-    def mesh(cls, ctx: "_lib.Context", meshes, scene_of=None, closed=False, leaf_size=None, sdf_source=False):
+    def mesh(cls, ctx: "_lib.Context", meshes, scene_of=None, closed=False, leaf_size=None, sdf_source=False, movers=None):
         """A scene set of triangle meshes: one ``mesh.Mesh`` or a list of them (S scenes, ``scene_of`` [B] as above), each
         a static surface behind a bounding-volume hierarchy that the library builds when the scene is created
         (csrc/mesh_bvh.h) -- ``is_mesh``.  closed=False: open surfaces, ``distance`` is unsigned.  closed=True: every mesh
@@ -226,17 +238,33 @@ class Scene:
         scene made by ``Scene.mesh(ctx, mesh, closed=True)`` and must keep passing as it is, so a mesh scene is a
         source only when it is created as one.  Nothing else about the scene depends on the option.
 
+        movers: moving obstacles beside the meshes, parsed as ``Scene(..., grid=True, movers=)`` parses them -- one flat
+        list of at most 32 plain or ``Scene.moving`` primitives for a single scene (``Scene.crowd(...)`` as it is), or
+        a list of lists, one per mesh (another number of lists: ValueError).  Every query then is the minimum over the
+        mesh and the movers at its time (csrc/scene_mesh.hip's *_mesh_mixed kernels): ``render(t=)``,
+        ``distance(t=)``, ``swept_distance(t0=, t1=)``, ``speed_bound`` (the movers') and, with sdf_source=True, the
+        SDF rows, where the mesh keeps a tie with a mover; the scene is ``is_mesh`` and ``is_dynamic``, and
+        ``Nmpc.rollout`` runs its scene clock.  None: the call ``Scene.mesh`` has always made; [] (or no mover in any
+        list): the plain mesh scene.
+
         The library refuses a malformed mesh (SdfnmpcError): a non-finite vertex, an index out of range, a triangle
         of zero area, closed=True on a surface with a boundary or a flipped triangle, an sdf_source other than a
-        boolean (0 or 1)."""
+        boolean (0 or 1); and of the movers what ``Scene`` refuses of its own."""
         from .mesh import Mesh
         ms = [meshes] if isinstance(meshes, Mesh) else list(meshes)
         self = cls.__new__(cls)
         self.ctx, self.S = ctx, len(ms)
         self._sdf_users = weakref.WeakSet()
+        extra = {}
+        if movers is not None:
+            mlists = _mover_lists(movers, len(ms))
+            mflat, mmotion = _flatten(mlists)
+            extra = dict(mcounts=[len(m) for m in mlists], mprims=mflat,
+                         mmotion=mmotion if any(m is not None for m in mmotion) else None)
         self.h = _lib.scene_create_mesh(ctx, [m.verts for m in ms], [m.tris for m in ms],
-                                        0 if leaf_size is None else int(leaf_size), bool(closed), sdf_source)
-        self.is_dynamic = self.is_indexed = False
+                                        0 if leaf_size is None else int(leaf_size), bool(closed), sdf_source, **extra)
+        self.is_dynamic = bool(_lib.load().sdfnmpc_scene_is_dynamic(self.h))
+        self.is_indexed = bool(_lib.load().sdfnmpc_scene_is_indexed(self.h))
         self.is_mesh = bool(_lib.load().sdfnmpc_scene_is_mesh(self.h))
         self.is_sdf_source = bool(_lib.load().sdfnmpc_scene_is_sdf_source(self.h))
         self._set_scene_of(scene_of)

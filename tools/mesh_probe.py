@@ -17,7 +17,16 @@ of an instance are neighbours on a trajectory.  It times scene_sdf_rows_mesh on 
 max_df only) and the same surface closed by cones over its boundary loops (the full search) -- at leaf sizes 1, 4 and -1,
 beside scene_dist_mesh on the same points and sets, the yardstick; then the time per step of a rollout with the network
 (perceiving the tunnel through the encoder, default weights) and with the mesh source, and the minimum clearance of both
-arms.  Writes profiles/mesh_sdf_probe.json."""
+arms.  Writes profiles/mesh_sdf_probe.json.
+
+--movers m: what do m movers beside the mesh cost (Scene.mesh(..., movers=), the four *_mesh_mixed kernels)?  On the same
+tunnel and heightfield with a Scene.crowd of m inside the mesh's bounds: --B images at t = 0.7, --points points with
+times, rows at B = 1024, N = 40 with tau, --chords chords with times.  Each of scene_render_mesh_mixed,
+scene_dist_mesh_mixed and scene_sdf_rows_mesh_mixed is set against the composition it replaces, from kernels the feature
+left alone in the same process: the *_mesh kernel on the mesh alone, the dynamic kernel on the movers alone and the
+combining pass, timed with torch -- after an assertion that both give the same bits.  The swept kernel has no
+composition: it stands beside scene_swept_mesh on the mesh alone, with the evaluations per chord.  Also printed: how often
+a mover is the nearest thing.  Writes profiles/mesh_mixed_probe.json (one file for every m it is run with)."""
 import argparse
 import json
 import os
@@ -33,7 +42,7 @@ from sdf_nmpc_amd import _lib
 from sdf_nmpc_amd.config import Config
 from sdf_nmpc_amd.mesh import Mesh
 from sdf_nmpc_amd.scene import Scene
-from large_scene_probe import each_ms
+from large_scene_probe import each_ms, torch_ms
 
 
 def terrain(g):
@@ -218,6 +227,117 @@ def sdf_main(a):
     print(json.dumps(res))
 
 
+def movers_main(a):
+    import torch
+    N, RB, NP, T, max_df, m = 40, 1024, 17, 0.7, 1.0, a.movers
+    cfg = Config(mpc__N=N)
+    h, w = (int(v) for v in cfg.sensor.shape_imgs[-2:])
+    ctx = _lib.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+    ctx.enable_timing(True)
+    dev = torch.device("cuda:0")
+    ia, ib = torch.rand(a.B, h, w, device=dev), torch.rand(a.B, h, w, device=dev)
+    da, db = (torch.rand(a.points, device=dev, dtype=torch.float64) for _ in range(2))
+    ha, hb = (torch.rand(RB * (N + 1), device=dev, dtype=torch.float64) for _ in range(2))
+    Ja, Jb = (torch.rand(RB * (N + 1), 3, device=dev, dtype=torch.float64) for _ in range(2))
+
+    def rows_min():
+        lower = hb < ha
+        return torch.where(lower, hb, ha), torch.where(lower[:, None], Jb, Ja)
+
+    comb = dict(render=torch_ms(lambda: torch.minimum(ia, ib), a.reps), dist=torch_ms(lambda: torch.minimum(da, db), a.reps),
+                rows=torch_ms(rows_min, a.reps))
+    res = dict(movers=m, B=a.B, shape=[h, w], points=a.points, rows=RB * (N + 1), N=N, chords=a.chords, max_evals=a.max_evals,
+               reps=a.reps, t=T, max_df=max_df, combine_pass_ms=comb, scenes={})
+    print(f"{m} movers; {a.B} images of {h} x {w}, {a.points} points, {RB * (N + 1)} rows, {a.chords} chords; one combining pass: "
+          f"render {comb['render']:.4f} ms, distance {comb['dist']:.4f} ms, rows {comb['rows']:.4f} ms; mean (max - min) of {a.reps} "
+          f"launches [ms]")
+    ter = terrain(a.grid)
+    names = dict(render=dict(mixed="scene_render_mesh_mixed", mesh="scene_render_mesh", dyn="scene_render_dyn"),
+                 dist=dict(mixed="scene_dist_mesh_mixed", mesh="scene_dist_mesh", dyn="scene_dist_dyn"),
+                 rows=dict(mixed="scene_sdf_rows_mesh_mixed", mesh="scene_sdf_rows_mesh", dyn="scene_sdf_rows"),
+                 swept=dict(mixed="scene_swept_mesh_mixed", mesh="scene_swept_mesh"))
+    for kind, mesh in (("tunnel", tunnel(ter.tris.shape[0])), ("heightfield", ter)):
+        rng = np.random.default_rng(2)
+        cam, R, pts, p0, p1 = queries(rng, a, kind)
+        lo, hi = mesh.verts.min(0), mesh.verts.max(0)
+        if kind == "tunnel":  # the crowd walks the tunnel's floor region, inside the tube
+            lo, hi = np.array([lo[0], -1.5, -1.5]), np.array([hi[0], 1.5, 1.0])
+        else:
+            hi = np.array([hi[0], hi[1], hi[2] + 2.0])
+        movers = Scene.crowd(m, lo, hi, seed=1)
+        dv = lambda x, dt=np.float64: _lib.DeviceArray.from_numpy(ctx, np.ascontiguousarray(x, dtype=dt))
+        dP, dR, dpts, d0, d1 = dv(cam), dv(R.reshape(-1, 9)), dv(pts), dv(p0), dv(p1)
+        times = dv(rng.uniform(0.0, 2.0, a.points))
+        c0 = rng.uniform(0.0, 2.0, a.chords)
+        dc0, dc1 = dv(c0), dv(c0 + 0.1)
+        x = rng.normal(0, 1, (RB, N + 1, 10))
+        x[..., :3] = pts[rng.integers(0, a.points, RB)][:, None, :] + 0.075 * np.arange(N + 1)[None, :, None] * np.array([1.0, 0.0, 0.0])
+        dx, dp = dv(x), dv(np.ones((RB, N + 1, NP)))
+        tau = dv(0.05 * np.arange(N + 1))
+        scenes = dict(mixed=Scene.mesh(ctx, mesh, sdf_source=True, movers=movers), mesh=Scene.mesh(ctx, mesh, sdf_source=True),
+                      dyn=Scene(ctx, movers))
+        out = {k: dict(img=_lib.DeviceArray(ctx, (a.B, h, w), np.float32), dist=_lib.DeviceArray(ctx, (a.points,)),
+                       h=_lib.DeviceArray(ctx, (RB, N + 1, 3)), J=_lib.DeviceArray(ctx, (RB, N + 1, 10, 3)),
+                       sw=[_lib.DeviceArray(ctx, (a.chords,)) for _ in range(3)] + [_lib.DeviceArray(ctx, (a.chords,), np.int32)])
+               for k in scenes}
+        launch = dict(
+            render=lambda k: scenes[k].render(dP, dR, cfg, out=out[k]["img"], t=T),
+            dist=lambda k: _lib.scene_distance_at(ctx, scenes[k].h, dpts, None, times, a.points, out[k]["dist"]),
+            rows=lambda k: _lib.scene_sdf_rows(ctx, scenes[k].h, RB, N, NP, dx, dp, out[k]["h"], out[k]["J"], max_df, t0=T, tau=tau),
+            swept=lambda k: _lib.scene_swept_distance(ctx, scenes[k].h, d0, d1, None, dc0, dc1, a.chords, 1e-3, a.max_evals,
+                                                      *out[k]["sw"]))
+        row = dict(triangles=int(mesh.tris.shape[0]))
+        for q in ("render", "dist", "rows", "swept"):
+            for k in names[q]:
+                row[f"{q}_{k}_ms"], row[f"{q}_{k}_spread_ms"] = each_ms(ctx, names[q][k], lambda: launch[q](k), a.reps)
+            if q != "swept":
+                row[f"{q}_composition_ms"] = row[f"{q}_mesh_ms"] + row[f"{q}_dyn_ms"] + comb[q]
+                row[f"{q}_composition_spread_ms"] = row[f"{q}_mesh_spread_ms"] + row[f"{q}_dyn_spread_ms"]
+        img = {k: out[k]["img"].numpy() for k in scenes}
+        d = {k: out[k]["dist"].numpy() for k in scenes}
+        hh = {k: out[k]["h"].numpy()[..., 2] for k in scenes}
+        JJ = {k: out[k]["J"].numpy()[..., 2] for k in scenes}
+        lower = hh["dyn"] < hh["mesh"]
+        assert (np.array_equal(img["mixed"], np.minimum(img["mesh"], img["dyn"])) and
+                np.array_equal(d["mixed"], np.minimum(d["mesh"], d["dyn"])) and
+                np.array_equal(hh["mixed"], np.where(lower, hh["dyn"], hh["mesh"])) and
+                np.array_equal(JJ["mixed"], np.where(lower[..., None], JJ["dyn"], JJ["mesh"]))), \
+            f"{kind}: the mesh-with-movers kernels and the composition differ"
+        row.update(bitwise_equal=True, pixels_from_movers=float((img["dyn"] < img["mesh"]).mean()),
+                   points_from_movers=float((d["dyn"] < d["mesh"]).mean()), rows_from_movers=float(lower.mean()),
+                   rows_near=float((hh["mixed"] < max_df).mean()),
+                   swept_evals_mixed=float(out["mixed"]["sw"][3].numpy().mean()), swept_evals_mesh=float(out["mesh"]["sw"][3].numpy().mean()))
+        for s in scenes.values():
+            s.close()
+        res["scenes"][kind] = row
+        print(f"{kind}: {row['triangles']} triangles")
+        for q in ("render", "dist", "rows"):
+            g = lambda k: f"{row[f'{q}_{k}_ms']:.4f} ({row[f'{q}_{k}_spread_ms']:.4f})"
+            over = row[f"{q}_mixed_ms"] - row[f"{q}_composition_ms"]
+            verdict = "within" if over <= row[f"{q}_composition_spread_ms"] else f"ABOVE the composition by {over:.4f} ms, beyond"
+            print(f"  {q:>6}: mixed {g('mixed'):>18}   composition {row[f'{q}_composition_ms']:.4f} = mesh {g('mesh')} + dyn {g('dyn')} + "
+                  f"pass {comb[q]:.4f}   ratio {row[f'{q}_mixed_ms'] / row[f'{q}_composition_ms']:.2f}: {verdict} its max - min "
+                  f"{row[f'{q}_composition_spread_ms']:.4f}")
+        print(f"   swept: mixed {row['swept_mixed_ms']:.4f} ({row['swept_mixed_spread_ms']:.4f}), {row['swept_evals_mixed']:.1f} evaluations "
+              f"per chord; scene_swept_mesh on the mesh alone {row['swept_mesh_ms']:.4f} ({row['swept_mesh_spread_ms']:.4f}), "
+              f"{row['swept_evals_mesh']:.1f} evaluations")
+        print(f"  bitwise equal; a mover is the nearest thing in {100 * row['pixels_from_movers']:.1f} % of the pixels, "
+              f"{100 * row['points_from_movers']:.1f} % of the points and {100 * row['rows_from_movers']:.1f} % of the rows "
+              f"({100 * row['rows_near']:.0f} % of the rows are within max_df)")
+    ctx.enable_timing(False)
+    path = a.out or os.path.join(ROOT, "profiles", "mesh_mixed_probe.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    allres = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            allres = json.load(f)
+    allres[f"movers_{m}"] = res
+    with open(path, "w") as f:
+        json.dump(allres, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=101, help="vertices per side of the heightfield: 2 (grid - 1)^2 triangles")
@@ -229,11 +349,15 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-brute", action="store_true", help="skip leaf_size = -1 (and the check against it)")
     ap.add_argument("--sdf", action="store_true", help="the mesh as the controller's SDF source: scene_sdf_rows_mesh")
-    ap.add_argument("--out", default=None, help="--sdf: where the JSON goes (profiles/mesh_sdf_probe.json)")
+    ap.add_argument("--movers", type=int, default=None, help="movers beside the mesh: the four *_mesh_mixed kernels")
+    ap.add_argument("--out", default=None, help="--sdf, --movers: where the JSON goes (profiles/mesh_sdf_probe.json, "
+                                                "profiles/mesh_mixed_probe.json)")
     a = ap.parse_args()
     warnings.filterwarnings("ignore")
     if a.sdf:
         return sdf_main(a)
+    if a.movers is not None:
+        return movers_main(a)
     import torch
     cfg = Config()
     ctx = _lib.Context(0, stream=torch.cuda.current_stream().cuda_stream)
