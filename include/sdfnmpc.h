@@ -92,7 +92,7 @@
 extern "C" {
 #endif
 
-#define SDFNMPC_ABI_VERSION 18
+#define SDFNMPC_ABI_VERSION 19
 
 enum {
     SDFNMPC_OK = 0,
@@ -964,8 +964,10 @@ int sdfnmpc_scene_create_mixed(sdfnmpc_ctx* ctx, int S, const int* count, const 
  * SDFNMPC_E_ARG (nothing is allocated on the device) also: a sdf_source other than 0 or 1.
  * SDFNMPC_E_UNSUPPORTED, nothing launched, outputs untouched: a mesh set created with sdf_source = 0 given to
  * sdfnmpc_scene_sdf_rows, sdfnmpc_lin_args.sdf_scene or sdfnmpc_solver_set_sdf_scene.  Movers beside a mesh:
- * sdfnmpc_scene_create_mesh_mixed below.  Not built: moving or deforming meshes, meshes mixed with static primitives in
- * one scene, a walk pruned at max_df (or at the movers' distance) for closed sets. */
+ * sdfnmpc_scene_create_mesh_mixed below.  Moving meshes, several meshes in one scene and more than 32 moving objects:
+ * sdfnmpc_scene_create_instanced below.  Not built: deforming or scaled meshes, meshes mixed with static primitives in
+ * one scene, a walk pruned at max_df (or at the movers' distance) for closed sets, a hierarchy over the instances of an
+ * instanced set (or more than SDFNMPC_SCENE_MAX_INSTANCES of them per scene). */
 #define SDFNMPC_MESH_MAX_TRIS (1 << 20)  /* per scene */
 #define SDFNMPC_MESH_MAX_VERTS (1 << 21) /* per scene */
 typedef struct {
@@ -1010,6 +1012,54 @@ int sdfnmpc_scene_is_sdf_source(const sdfnmpc_scene* scene);
 int sdfnmpc_scene_create_mesh_mixed(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts, const int* ntri,
                                     const int* tris, const sdfnmpc_mesh_opts* opts, const int* mcount,
                                     const sdfnmpc_prim* mprims, const sdfnmpc_prim_motion* mmotion, sdfnmpc_scene** out);
+
+/* ---- instanced mesh scenes: rigid, moving copies of shared meshes (csrc/scene_inst.hip, csrc/inst_dev.h) ----
+ * sdfnmpc_scene_create_instanced makes a pool of nparts parts and S scenes of instances that place them.  A part is a
+ * triangle mesh in its own coordinates, given, checked, rounded to fp32 and put behind a hierarchy exactly as a scene of
+ * sdfnmpc_scene_create_mesh is (nvert [nparts], verts, ntri [nparts], tris: that function's arguments with nparts for
+ * S; opts: closed, leaf_size and sdf_source mean what they mean there), and stored once however often it is placed.
+ * Scene s holds icount[s] instances, 0..SDFNMPC_SCENE_MAX_INSTANCES, instances [sum of icount] scene after scene.
+ * Instance i is a part under the rigid frame of sdfnmpc_scene_create_moving about the part's origin,
+ *   c(t) = p + v t + amp sin(omega t + phase),   R(t) = Rz(yaw_rate t) R(q),
+ * formed in fp64; there is no scale.  With x' = R(t)^T (x - c(t)):
+ *   distance  min over i of the part's distance at x'_i, fp64: unsigned for closed = 0; for closed = 1 every part must be
+ *             a closed, consistently oriented manifold and the value is the minimum of the instances' signed distances,
+ *             the union -- instances may overlap.
+ *   render    the smallest hit t >= 0 over the instances, fp32; instance i's ray has the origin R(t)^T (W_p_C - c(t))
+ *             and the axes R(t)^T W_R_C, formed in fp64 and rounded to fp32 once per image.  Hit rule (double-sided,
+ *             edge-consistent, no "inside sees zero"), pixel grid, clipping, depth / range and scale: a mesh set's.
+ *   SDF rows  (sdf_source = 1) the value and the gradient R(t) g' of the minimising instance, g' the mesh row's gradient
+ *             in the part's frame; the lowest instance index wins a tie, within a part the lowest original triangle
+ *             index.  Truncation, flag and row contract: a mesh set's.  Node k of a source with tau at t0 + tau[k].
+ *   swept     sdfnmpc_scene_swept_distance over the distance above; the speed bound V of a scene is the maximum over its
+ *             instances of |v| + |omega| |amp| + |yaw_rate| rho, rho the largest |vertex| of the part, inflated by
+ *             1 + 1e-12 (sdfnmpc_scene_speed_bound).
+ * A scene without instances renders a miss everywhere and is at distance +inf.  Results depend neither on the parts'
+ * hierarchies (leaf_size) nor on the order of the instances or on which of them a query skips, bit for bit, except for
+ * the tie rule of the rows.  An instance with p = 0, q = identity and no motion gives the bits of the mesh set of its
+ * part.  The top level is a linear pass over the scene's instances in every query.
+ * For such a handle sdfnmpc_scene_is_instanced is 1, sdfnmpc_scene_is_mesh and sdfnmpc_scene_is_indexed are 0,
+ * sdfnmpc_scene_is_dynamic is 1 exactly when some instance has a non-zero v, amp or yaw_rate, and
+ * sdfnmpc_scene_is_sdf_source is opts->sdf_source.  sdfnmpc_scene_render(_at), sdfnmpc_scene_distance(_at),
+ * sdfnmpc_scene_swept_distance and every rollout that renders a scene take it, and with sdf_source = 1
+ * sdfnmpc_scene_sdf_rows, sdfnmpc_lin_args.sdf_scene and sdfnmpc_solver_set_sdf_scene; with sdf_source = 0 those three
+ * refuse it (SDFNMPC_E_UNSUPPORTED, nothing launched, outputs untouched).  The kernels are "scene_render_inst",
+ * "scene_dist_inst", "scene_sdf_rows_inst" and "scene_swept_inst" in sdfnmpc_ctx_kernel_stats.  A spherical image of
+ * an instanced set needs H + W <= 4096 (SDFNMPC_E_ARG otherwise).
+ * SDFNMPC_E_ARG (nothing is allocated on the device): nparts or S outside 1..2^20, a part index outside [0, nparts), an
+ * icount[s] outside 0..SDFNMPC_SCENE_MAX_INSTANCES, a zero quaternion, a non-finite position or motion value, what
+ * sdfnmpc_scene_create_mesh refuses of a part (closed = 1 with a part that is not closed among it), a NULL argument.
+ * Not built: a hierarchy over the instances, scaled or deforming instances, primitives in an instanced set. */
+#define SDFNMPC_SCENE_MAX_INSTANCES 256
+typedef struct {
+    int part;                      /* index into the pool, 0..nparts-1 */
+    double p[3];                   /* the position of the part's origin at t = 0 (without the harmonic term) */
+    sdfnmpc_prim_motion motion;    /* q, yaw_rate, v, amp, omega, phase */
+} sdfnmpc_mesh_instance;
+int sdfnmpc_scene_create_instanced(sdfnmpc_ctx* ctx, int nparts, const int* nvert, const double* verts, const int* ntri,
+                                   const int* tris, const sdfnmpc_mesh_opts* opts, int S, const int* icount,
+                                   const sdfnmpc_mesh_instance* instances, sdfnmpc_scene** out);
+int sdfnmpc_scene_is_instanced(const sdfnmpc_scene* scene);
 
 /* sdfnmpc_solver_rollout with perception inside the loop.  Before step k with (k + phase) % every == 0 it enqueues, on the
  * solver's stream and in this order: (a) sdfnmpc_scene_pose from the solver's x0 field; (b) sdfnmpc_scene_render of

@@ -52,6 +52,7 @@ SYMBOLS = [
     "sdfnmpc_scene_swept_distance", "sdfnmpc_scene_speed_bound",
     "sdfnmpc_scene_create_mesh", "sdfnmpc_scene_is_mesh", "sdfnmpc_scene_is_sdf_source",
     "sdfnmpc_scene_create_mesh_mixed",
+    "sdfnmpc_scene_create_instanced", "sdfnmpc_scene_is_instanced",
 ]
 L4C_SYMBOLS = [
     f"{p}sdf_l4c{s}" for p in ("", "jac_", "adj1_")
@@ -192,6 +193,13 @@ class PrimMotionC(C.Structure):
                 ("omega", C.c_double), ("phase", C.c_double)]
 
 
+SCENE_MAX_INSTANCES = 256  # SDFNMPC_SCENE_MAX_INSTANCES
+
+
+class MeshInstanceC(C.Structure):  # sdfnmpc_mesh_instance
+    _fields_ = [("part", C.c_int), ("p", C.c_double * 3), ("motion", PrimMotionC)]
+
+
 class PerceiveArgsC(C.Structure):
     _fields_ = [("scene", C.c_void_p), ("scene_of", C.c_void_p), ("img", ImgOptsC), ("h", C.c_int), ("w", C.c_int),
                 ("scale", C.c_float), ("B_p_C", C.c_double * 3), ("B_R_C", C.c_double * 9), ("vae", C.c_void_p),
@@ -314,6 +322,9 @@ def load():
         "sdfnmpc_scene_create_mesh_mixed": (i, [vp, i, P(i), P(d), P(i), P(i), P(MeshOptsC), P(i), P(PrimC),
                                                 P(PrimMotionC), P(vp)]),
         "sdfnmpc_scene_is_mesh": (i, [vp]),
+        "sdfnmpc_scene_create_instanced": (i, [vp, i, P(i), P(d), P(i), P(i), P(MeshOptsC), i, P(i), P(MeshInstanceC),
+                                               P(vp)]),
+        "sdfnmpc_scene_is_instanced": (i, [vp]),
         "sdfnmpc_scene_is_sdf_source": (i, [vp]),
         "sdfnmpc_solver_rollout_perceive_at": (i, [vp, P(RolloutArgsC), P(PerceiveArgsC), d, d]),
         "sdfnmpc_morph": (i, [vp, i, vp, i, i, i, vp, i, i, i, vp]),
@@ -341,7 +352,7 @@ def load():
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sdfnmpc_abi_version() != 18:
+    if lib.sdfnmpc_abi_version() != 19:
         raise SdfnmpcError("libsdfnmpc.so ABI version mismatch")
     _lib = lib
     return lib
@@ -929,6 +940,33 @@ def scene_create_mesh(ctx: "Context", verts, tris, leaf_size: int = 0, closed: b
         return h
     _check(load().sdfnmpc_scene_create_mesh(ctx.h, len(vs), nv, va.ctypes.data_as(C.POINTER(C.c_double)), nt,
                                             ta.ctypes.data_as(C.POINTER(C.c_int)), C.byref(o), C.byref(h)))
+    return h
+
+
+def scene_create_instanced(ctx: "Context", verts, tris, counts, instances, leaf_size: int = 0, closed: bool = False,
+                           sdf_source=False):
+    """sdfnmpc_scene_create_instanced: one (verts [nv, 3] float64, tris [nt, 3] int32) pair per part of the pool, as
+    scene_create_mesh takes them per scene, with leaf_size, closed and sdf_source of that function; counts [S] instances
+    per scene and instances, a flat list scene after scene of (part, p, motion) with motion a dict as scene_create takes
+    it (None: no motion).  Returns the handle; the library refuses malformed parts and instances."""
+    vs = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3) for v in verts]
+    ts = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1, 3) for t in tris]
+    nv = (C.c_int * max(len(vs), 1))(*[v.shape[0] for v in vs])
+    nt = (C.c_int * max(len(ts), 1))(*[t.shape[0] for t in ts])
+    va = np.ascontiguousarray(np.concatenate(vs, 0)) if vs else np.zeros((0, 3))
+    ta = np.ascontiguousarray(np.concatenate(ts, 0)) if ts else np.zeros((0, 3), np.int32)
+    o = MeshOptsC(int(leaf_size), int(bool(closed)), int(sdf_source))
+    cn = (C.c_int * max(len(counts), 1))(*[int(c) for c in counts])
+    ins = (MeshInstanceC * max(len(instances), 1))()
+    mo = _motion_c([m for _, _, m in instances], len(instances))
+    for k, (part, pos, _) in enumerate(instances):
+        ins[k].part = int(part)
+        ins[k].p[:] = [float(v) for v in pos]
+        ins[k].motion = mo[k]
+    h = C.c_void_p()
+    _check(load().sdfnmpc_scene_create_instanced(ctx.h, len(vs), nv, va.ctypes.data_as(C.POINTER(C.c_double)), nt,
+                                                 ta.ctypes.data_as(C.POINTER(C.c_int)), C.byref(o), len(counts), cn, ins,
+                                                 C.byref(h)))
     return h
 
 

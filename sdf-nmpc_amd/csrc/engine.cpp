@@ -1171,7 +1171,11 @@ extern "C" int sdfnmpc_sdf_eval_host(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, i
 
 // the scene's rows kernel: a mesh set takes its own, an indexed set the grid kernel, everything else the launch it has
 // always taken
-static hipError_t scene_sdf_rows_enqueue(sdfnmpc_ctx* ctx, const SceneSdfArgs& a) {
+static hipError_t scene_sdf_rows_enqueue(sdfnmpc_ctx* ctx, const SceneSdfArgs& a, const sdfnmpc_scene* sc) {
+    if (sc->is_inst) {  // an instanced set created as an SDF source
+        const InstSdfArgs ia{a, sc->inst};
+        return timed(ctx, "scene_sdf_rows_inst", [&] { return launch_scene_sdf_rows_inst(ia, ctx->stream); });
+    }
     if (a.mesh.hdr && a.dyn)  // a mesh set with movers, created as an SDF source
         return timed(ctx, "scene_sdf_rows_mesh_mixed", [&] { return launch_scene_sdf_rows_mesh_mixed(a, ctx->stream); });
     if (a.mesh.hdr)  // a mesh set created as an SDF source
@@ -1316,7 +1320,7 @@ static int lin_impl(sdfnmpc_ctx* ctx, const sdfnmpc_net* net, const sdfnmpc_quad
     if (no_sdf) {  // no constraint or cost reads the network: the linearisation alone, then the pack
         HIPCHK(timed(ctx, "linearize", [&] { return launch_linearize(la, ctx->stream); }, ctx->stream));
         if (a->sdf_scene)  // the SDF row from the scene's closed forms, between the linearisation and the pack
-            HIPCHK(scene_sdf_rows_enqueue(ctx, ssa));
+            HIPCHK(scene_sdf_rows_enqueue(ctx, ssa, a->sdf_scene->scene));
         if (a->sdf_image)  // or from the field of the camera image
             if (int rc_ = img_sdf_launch(ctx, isa)) return rc_;
         return finish_pack();
@@ -2939,9 +2943,19 @@ extern "C" int sdfnmpc_scene_create_mixed(sdfnmpc_ctx* ctx, int S, const int* co
 // mcount == NULL: the mesh set of sdfnmpc_scene_create_mesh.  Otherwise mcount [S] in 0..32, mprims and mmotion (or
 // NULL) already checked by the caller: the movers of sdfnmpc_scene_create_mesh_mixed, appended to the device image as
 // mcount [S] | ScenePrimDyn [S][32] | vmax [S], as scene_create_indexed appends them to a grid's
+//
+// inst != NULL: the set of sdfnmpc_scene_create_instanced.  The S "scenes" built here are then the parts of its pool,
+// and the handle's scenes are the inst->S lists of instances, already checked by the caller and appended to the image as
+// icount [S] | ioff [S] | ScenePrimDyn [sum of icount] | vmax [S]
+struct InstHost {
+    int S;
+    const int* icount;                // [S]
+    const sdfnmpc_mesh_instance* in;  // [sum of icount]
+};
 static int scene_create_mesh_set(sdfnmpc_ctx* ctx, int S, const int* nvert, const double* verts, const int* ntri,
                                  const int* tris, const sdfnmpc_mesh_opts* opts, const int* mcount,
-                                 const sdfnmpc_prim* mprims, const sdfnmpc_prim_motion* mmotion, sdfnmpc_scene** out) {
+                                 const sdfnmpc_prim* mprims, const sdfnmpc_prim_motion* mmotion, sdfnmpc_scene** out,
+                                 const InstHost* inst = nullptr) {
     if (!ctx || !nvert || !ntri || !out) return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create_mesh");
     *out = nullptr;
     if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "mesh: S must be 1..2^20");
@@ -2968,6 +2982,7 @@ static int scene_create_mesh_set(sdfnmpc_ctx* ctx, int S, const int* nvert, cons
     std::vector<MeshTriF> tf((size_t)tt);
     std::vector<MeshTriD> td((size_t)tt);
     std::vector<MeshTriN> tn(o.closed ? (size_t)tt : 0);
+    std::vector<double> rho((size_t)S, 0.0);  // the largest |vertex| of each mesh, of its fp32 vertices
     {
         const double* v = verts;
         const int* t = tris;
@@ -2979,6 +2994,9 @@ static int scene_create_mesh_set(sdfnmpc_ctx* ctx, int S, const int* nvert, cons
         for (int s = 0; s < S; v += (size_t)nvert[s] * 3, t += (size_t)ntri[s] * 3, ++s) {
             if (const char* why = mesh_check(v, nvert[s], t, ntri[s], o.closed != 0, vf)) return fail(SDFNMPC_E_ARG, why);
             const float m = mesh_margin(vf.data(), nvert[s]);
+            for (int i = 0; i < nvert[s]; ++i)
+                rho[s] = std::max(rho[s], std::hypot((double)vf[(size_t)i * 3], (double)vf[(size_t)i * 3 + 1],
+                                                     (double)vf[(size_t)i * 3 + 2]));
             mesh_bvh_build(vf.data(), t, ntri[s], leaf, m, bvh);
             mesh_face_normals(vf.data(), t, ntri[s], fn);
             if (o.closed) mesh_pseudonormals(vf.data(), nvert[s], t, ntri[s], fn, pn);
@@ -3013,9 +3031,46 @@ static int scene_create_mesh_set(sdfnmpc_ctx* ctx, int S, const int* nvert, cons
     const size_t o_dyn = up16(o_mc + (size_t)S * sizeof(int));
     const size_t o_vmax = o_dyn + (size_t)S * SCENE_MAX_PRIMS * sizeof(ScenePrimDyn);  // the movers' speed bounds [S]
     static_assert(SCENE_MAX_PRIMS * sizeof(ScenePrimDyn) % 16 == 0, "fp64 alignment of the speed bounds");
-    const size_t bytes = mcount ? o_vmax + (size_t)S * sizeof(double) : o_mc;
-    std::vector<double> vmax((size_t)S, 0.0);
+    size_t bytes = mcount ? o_vmax + (size_t)S * sizeof(double) : o_mc;
+    const int HS = inst ? inst->S : S;  // the scenes of the handle
+    std::vector<double> vmax((size_t)HS, 0.0);
     std::vector<ScenePrimDyn> hm;
+    // an instanced set: the records (the frame of a primitive at c0 = p, the part in `kind`) and the speed bounds
+    std::vector<int> ioff;
+    bool inst_moves = false;
+    size_t o_ic = 0, o_io = 0, o_rec = 0, o_iv = 0;
+    if (inst) {
+        ioff.assign((size_t)HS, 0);
+        long long total = 0;
+        for (int s = 0; s < HS; ++s) {
+            ioff[s] = (int)total;
+            total += inst->icount[s];
+        }
+        hm.assign((size_t)total, ScenePrimDyn{});
+        for (int s = 0; s < HS; ++s)
+            for (int i = 0; i < inst->icount[s]; ++i) {
+                const sdfnmpc_mesh_instance& q = inst->in[(size_t)ioff[s] + i];
+                ScenePrimDyn& y = hm[(size_t)ioff[s] + i];
+                const sdfnmpc_prim centre = {SDFNMPC_PRIM_SPHERE, {q.p[0], q.p[1], q.p[2], 1.0, 0.0, 0.0}};
+                scene_dyn_fill(y, &centre, &q.motion);
+                y.kind = q.part;
+                y.h[0] = rho[(size_t)q.part];
+                y.h[1] = y.h[2] = 0.0;
+                const sdfnmpc_prim_motion& m = q.motion;
+                inst_moves = inst_moves || m.yaw_rate != 0.0;
+                for (int k = 0; k < 3; ++k) inst_moves = inst_moves || m.v[k] != 0.0 || m.amp[k] != 0.0;
+                // scene_dyn_speed's bound with rho the largest |vertex| of the part, inflated like scene_speed_bounds
+                vmax[s] = std::max(vmax[s], std::hypot(y.v[0], y.v[1], y.v[2]) +
+                                                std::fabs(y.omega) * std::hypot(y.amp[0], y.amp[1], y.amp[2]) +
+                                                std::fabs(y.yaw_rate) * y.h[0]);
+            }
+        for (int s = 0; s < HS; ++s) vmax[s] *= 1.0 + 1e-12;
+        o_ic = o_mc;
+        o_io = up16(o_ic + (size_t)HS * sizeof(int));
+        o_rec = up16(o_io + (size_t)HS * sizeof(int));
+        o_iv = up16(o_rec + hm.size() * sizeof(ScenePrimDyn));
+        bytes = o_iv + (size_t)HS * sizeof(double);
+    }
     if (mcount) {
         hm.assign((size_t)S * SCENE_MAX_PRIMS, ScenePrimDyn{});
         const sdfnmpc_prim* q = mprims;
@@ -3026,7 +3081,7 @@ static int scene_create_mesh_set(sdfnmpc_ctx* ctx, int S, const int* nvert, cons
     }
     ScopedDevice sd(ctx->device);
     auto* sc = new sdfnmpc_scene();
-    sc->device = ctx->device; sc->ctx = ctx; sc->S = S;
+    sc->device = ctx->device; sc->ctx = ctx; sc->S = HS;
     hipError_t e = hipMalloc(&sc->dmem, bytes);
     char* d = (char*)sc->dmem;
     auto put = [&](size_t off, const void* src, size_t n) {
@@ -3042,14 +3097,20 @@ static int scene_create_mesh_set(sdfnmpc_ctx* ctx, int S, const int* nvert, cons
         put(o_dyn, hm.data(), hm.size() * sizeof(ScenePrimDyn));
         put(o_vmax, vmax.data(), (size_t)S * sizeof(double));
     }
+    if (inst) {
+        put(o_ic, inst->icount, (size_t)HS * sizeof(int));
+        put(o_io, ioff.data(), (size_t)HS * sizeof(int));
+        put(o_rec, hm.data(), hm.size() * sizeof(ScenePrimDyn));
+        put(o_iv, vmax.data(), (size_t)HS * sizeof(double));
+    }
     if (e != hipSuccess) {
         if (sc->dmem) (void)hipFree(sc->dmem);
         delete sc;
         return fail(SDFNMPC_E_HIP, std::string("mesh upload: ") + hipGetErrorString(e));
     }
     sc->dev = SceneDev{};
-    sc->dev.S = S;
-    sc->is_mesh = true;
+    sc->dev.S = HS;
+    sc->is_mesh = !inst;
     sc->sdf_source = o.sdf_source != 0;
     sc->mesh = MeshDev{(const MeshHdr*)d, (const MeshNode*)(d + o_nodes), (const MeshTriF*)(d + o_tf),
                        (const MeshTriD*)(d + o_td), o.closed ? (const MeshTriN*)(d + o_tn) : nullptr};
@@ -3058,6 +3119,12 @@ static int scene_create_mesh_set(sdfnmpc_ctx* ctx, int S, const int* nvert, cons
         sc->mcount = (const int*)(d + o_mc);
         sc->dyn = (const ScenePrimDyn*)(d + o_dyn);
         sc->dvmax = (const double*)(d + o_vmax);
+    }
+    if (inst) {
+        sc->is_inst = true;
+        sc->inst_moves = inst_moves;
+        sc->inst = InstDev{S, (const int*)(d + o_ic), (const int*)(d + o_io), (const ScenePrimDyn*)(d + o_rec)};
+        sc->dvmax = (const double*)(d + o_iv);
     }
     *out = sc;
     return SDFNMPC_OK;
@@ -3096,9 +3163,44 @@ extern "C" int sdfnmpc_scene_create_mesh_mixed(sdfnmpc_ctx* ctx, int S, const in
     return scene_create_mesh_set(ctx, S, nvert, verts, ntri, tris, opts, mtotal > 0 ? mcount : nullptr, mprims, mmotion, out);
 }
 
+// An instanced set (scene_inst.hip): nparts meshes, built as the scenes of a mesh set are, and S lists of instances
+// that place them.  The instances are checked here, the parts by the builder of sdfnmpc_scene_create_mesh
+extern "C" int sdfnmpc_scene_create_instanced(sdfnmpc_ctx* ctx, int nparts, const int* nvert, const double* verts,
+                                              const int* ntri, const int* tris, const sdfnmpc_mesh_opts* opts, int S,
+                                              const int* icount, const sdfnmpc_mesh_instance* instances,
+                                              sdfnmpc_scene** out) {
+    if (!ctx || !nvert || !ntri || !icount || !out)
+        return fail(SDFNMPC_E_ARG, "NULL argument to sdfnmpc_scene_create_instanced");
+    *out = nullptr;
+    if (nparts < 1 || nparts > (1 << 20)) return fail(SDFNMPC_E_ARG, "instanced: nparts must be 1..2^20");
+    if (S < 1 || S > (1 << 20)) return fail(SDFNMPC_E_ARG, "instanced: S must be 1..2^20");
+    long long total = 0;
+    for (int s = 0; s < S; ++s) {
+        if (icount[s] < 0 || icount[s] > SCENE_MAX_INSTANCES)
+            return fail(SDFNMPC_E_ARG, "instanced: at most 256 instances per scene (and no negative count)");
+        total += icount[s];
+    }
+    if (total > 0 && !instances) return fail(SDFNMPC_E_ARG, "instanced: NULL instances");
+    for (long long i = 0; i < total; ++i) {
+        const sdfnmpc_mesh_instance& q = instances[i];
+        if (q.part < 0 || q.part >= nparts) return fail(SDFNMPC_E_ARG, "instanced: a part index outside [0, nparts)");
+        if (!(std::isfinite(q.p[0]) && std::isfinite(q.p[1]) && std::isfinite(q.p[2])))
+            return fail(SDFNMPC_E_ARG, "instanced: an instance needs a finite position");
+        bool dynamic = false;
+        if (int rc = scene_motion_check(&q.motion, 1, &dynamic)) return rc;
+    }
+    const InstHost ih{S, icount, instances};
+    return scene_create_mesh_set(ctx, nparts, nvert, verts, ntri, tris, opts, nullptr, nullptr, nullptr, out, &ih);
+}
+
+extern "C" int sdfnmpc_scene_is_instanced(const sdfnmpc_scene* sc) { return sc && sc->is_inst; }
+
 extern "C" int sdfnmpc_scene_is_mesh(const sdfnmpc_scene* sc) { return sc && sc->is_mesh; }
 
-extern "C" int sdfnmpc_scene_is_sdf_source(const sdfnmpc_scene* sc) { return sc && (!sc->is_mesh || sc->sdf_source); }
+// a mesh set or an instanced set is a source only when it was created as one
+extern "C" int sdfnmpc_scene_is_sdf_source(const sdfnmpc_scene* sc) {
+    return sc && (!(sc->is_mesh || sc->is_inst) || sc->sdf_source);
+}
 
 extern "C" int sdfnmpc_scene_is_indexed(const sdfnmpc_scene* sc) { return sc && sc->dev.ghdr; }
 
@@ -3109,7 +3211,7 @@ extern "C" void sdfnmpc_scene_free(sdfnmpc_scene* sc) {
     delete sc;
 }
 
-extern "C" int sdfnmpc_scene_is_dynamic(const sdfnmpc_scene* sc) { return sc && sc->dyn; }
+extern "C" int sdfnmpc_scene_is_dynamic(const sdfnmpc_scene* sc) { return sc && (sc->dyn || sc->inst_moves); }
 
 // the option checks of the two launches a rollout repeats, split from the launches as the plant's are
 int sdfn::scene_render_args(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int* scene_of, const sdfnmpc_img_opts* o,
@@ -3127,6 +3229,10 @@ int sdfn::scene_render_args(sdfnmpc_ctx* ctx, const sdfnmpc_scene* sc, const int
         return fail(SDFNMPC_E_ARG, "scene_render: a pinhole image needs hfov and vfov below pi / 2");
     if (scene_render_lds_bytes(H, W, o->is_spherical != 0) > SCENE_LDS_MAX)
         return fail(SDFNMPC_E_ARG, "scene_render: spherical image too large (H + W <= 6144)");
+    // an instanced set stages its 256 frames (16 KB) beside the spherical tables
+    if (sc->is_inst && scene_render_lds_bytes(H, W, o->is_spherical != 0) + SCENE_MAX_INSTANCES * sizeof(SceneInstFrame) >
+                           SCENE_LDS_MAX)
+        return fail(SDFNMPC_E_ARG, "scene_render: spherical image too large for an instanced set (H + W <= 4096)");
     if (B > 0 && (!W_p_C || !W_R_C || !img)) return fail(SDFNMPC_E_ARG, "scene_render: NULL pose or image");
     SceneRenderArgs a{};
     a.sc = sc->dev; a.scene_of = scene_of; a.B = B; a.H = H; a.W = W; a.W_p_C = W_p_C; a.W_R_C = W_R_C;
@@ -3154,6 +3260,12 @@ static int scene_render_static(sdfnmpc_ctx* ctx, const SceneRenderArgs& a) {
 
 // the scene at time t: a static set takes the launch above whatever t is, a dynamic one its own kernel
 int sdfn::scene_render_launch(sdfnmpc_ctx* ctx, const sdfnmpc_scene& sc, const SceneRenderArgs& a, double t) {
+    if (sc.is_inst) {  // an instanced set, its frames at time t
+        const InstRenderArgs ia{a, sc.mesh, sc.inst, t};
+        ScopedDevice sd(ctx->device);
+        HIPCHK(timed(ctx, "scene_render_inst", [&] { return launch_scene_render_inst(ia, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (sc.is_mesh && sc.dyn) {  // a mesh set with movers, at time t
         const MeshRenderMixedArgs ma{a, sc.mesh, sc.dyn, sc.mcount, t};
         ScopedDevice sd(ctx->device);
@@ -3238,6 +3350,11 @@ extern "C" int sdfnmpc_scene_distance_at(sdfnmpc_ctx* ctx, const sdfnmpc_scene* 
     if (!points || !out) return fail(SDFNMPC_E_ARG, "scene_distance: NULL points or output");
     SceneDistArgs a{sc->dev, points, p_to_scene, n, std::max(1LL, n / sc->S), out};
     ScopedDevice sd(ctx->device);
+    if (sc->is_inst) {  // an instanced set, at the points' times
+        const InstDistArgs ia{a, sc->mesh, sc->inst, times};
+        HIPCHK(timed(ctx, "scene_dist_inst", [&] { return launch_scene_distance_inst(ia, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (sc->is_mesh && sc->dyn) {  // a mesh set with movers, at the points' times
         const MeshDistMixedArgs ma{a, sc->mesh, sc->dyn, sc->mcount, times};
         HIPCHK(timed(ctx, "scene_dist_mesh_mixed", [&] { return launch_scene_distance_mesh_mixed(ma, ctx->stream); }));
@@ -3291,6 +3408,13 @@ extern "C" int sdfnmpc_scene_swept_distance(sdfnmpc_ctx* ctx, const sdfnmpc_scen
     a.eps = eps; a.max_evals = max_evals;
     a.dmin = dmin; a.s = s; a.gap = gap; a.evals = evals;
     ScopedDevice sd(ctx->device);
+    if (sc->is_inst) {  // the times only when some instance moves: a set that is not dynamic does not read them
+        a.mesh = sc->mesh;
+        a.t0 = sc->inst_moves ? t0 : nullptr; a.t1 = sc->inst_moves ? t1 : nullptr;
+        const InstSweptArgs ia{a, sc->inst};
+        HIPCHK(timed(ctx, "scene_swept_inst", [&] { return launch_scene_swept_inst(ia, ctx->stream); }));
+        return SDFNMPC_OK;
+    }
     if (sc->is_mesh && sc->dyn) {
         a.mesh = sc->mesh;
         HIPCHK(timed(ctx, "scene_swept_mesh_mixed", [&] { return launch_scene_swept_mesh_mixed(a, ctx->stream); }));
@@ -3336,13 +3460,16 @@ int sdfn::scene_sdf_args(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_opts* o, int 
     if (o->scene->is_mesh && !o->scene->sdf_source)  // a mesh set is a source only when it was created as one
         return fail(SDFNMPC_E_UNSUPPORTED, "scene_sdf_rows: a mesh set cannot be the SDF source (meshes are rendered and "
                                            "measured, not linearised)");
+    if (o->scene->is_inst && !o->scene->sdf_source)
+        return fail(SDFNMPC_E_UNSUPPORTED, "scene_sdf_rows: an instanced set created with sdf_source = 0 cannot be the "
+                                           "SDF source");
     if (B > 0 && (!x || !p || !h || !Jh)) return fail(SDFNMPC_E_ARG, "scene_sdf_rows: NULL x, p, h or Jh");
     SceneSdfArgs a{};
     a.sc = o->scene->dev; a.dyn = o->scene->dyn; a.mcount = o->scene->mcount; a.scene_of = o->scene_of;
     a.rows = (long long)B * (N + 1); a.N1 = N + 1; a.np = np;
     a.x = x; a.p = p; a.h = h; a.Jh = Jh;
     a.max_df = o->max_df; a.t0 = o->t0; a.tau = o->tau;
-    if (o->scene->is_mesh) a.mesh = o->scene->mesh;
+    if (o->scene->is_mesh || o->scene->is_inst) a.mesh = o->scene->mesh;
     out = a;
     return SDFNMPC_OK;
 }
@@ -3353,7 +3480,7 @@ extern "C" int sdfnmpc_scene_sdf_rows(sdfnmpc_ctx* ctx, const sdfnmpc_scene_sdf_
     if (int rc = scene_sdf_args(ctx, o, B, N, np, x, p, h, Jh, a)) return rc;
     if (B == 0) return SDFNMPC_OK;
     ScopedDevice sd(ctx->device);
-    HIPCHK(scene_sdf_rows_enqueue(ctx, a));
+    HIPCHK(scene_sdf_rows_enqueue(ctx, a, o->scene));
     return SDFNMPC_OK;
 }
 

@@ -212,6 +212,12 @@ struct sdfnmpc_scene {
     bool is_mesh = false;
     bool sdf_source = false;  // a mesh set created with sdfnmpc_mesh_opts.sdf_source = 1: accepted as the SDF source
     sdfn::MeshDev mesh{};
+    // an instanced set (sdfnmpc_scene_create_instanced): the image of a mesh set over the nparts parts of the pool (mesh:
+    // hdr [nparts] | ...), then icount [S] | ioff [S] | ScenePrimDyn [sum of icount] | vmax [S]; is_mesh stays false, dyn
+    // and mcount stay NULL, dev carries S alone
+    bool is_inst = false;
+    bool inst_moves = false;  // some instance has a non-zero v, amp or yaw_rate: the set is dynamic
+    sdfn::InstDev inst{};
 };
 
 namespace sdfn {

@@ -193,6 +193,47 @@ struct MeshDistMixedArgs {
     const double* times;     // [n] or nullptr (t = 0)
 };
 
+// scene_inst.hip: an instanced set (sdfnmpc_scene_create_instanced).  The MeshDev beside it is the pool of parts:
+// hdr[part] says where a part lies in the arrays, each part stored once in its own coordinates.  Scene s holds the
+// instances rec[ioff[s] .. ioff[s] + icount[s]), icount[s] <= SCENE_MAX_INSTANCES; an instance is a ScenePrimDyn record
+// read for its frame alone (prim_frame), with the part's index in `kind` and nothing in h.
+constexpr int SCENE_MAX_INSTANCES = 256;  // SDFNMPC_SCENE_MAX_INSTANCES
+struct InstDev {
+    int nparts;
+    const int* icount;         // [S]
+    const int* ioff;           // [S]
+    const ScenePrimDyn* rec;   // [sum of icount]
+};
+// what a block of the instanced render kernel stages per instance: the camera in the instance's frame at time t,
+// o' = R(t)^T (W_p_C - c(t)) and M = R(t)^T W_R_C, formed in fp64 and rounded once, and the part
+struct SceneInstFrame {  // 64 bytes: four 16-byte LDS reads
+    float o[3];
+    int part;
+    float M[9];
+    int pad[3];
+};
+// structures of their own: every other kernel's arguments stay where they were.  r.sc / d.sc carry S only
+struct InstRenderArgs {
+    SceneRenderArgs r;
+    MeshDev mesh;
+    InstDev inst;
+    double t;
+};
+struct InstDistArgs {
+    SceneDistArgs d;
+    MeshDev mesh;
+    InstDev inst;
+    const double* times;     // [n] or nullptr (t = 0)
+};
+struct InstSdfArgs {         // a.mesh: the pool of parts; a.dyn and a.mcount are not read
+    SceneSdfArgs a;
+    InstDev inst;
+};
+struct InstSweptArgs {       // a.mesh: the pool of parts; a.vmax [S]: the instances' speed bound; a.dyn, a.mcount not read
+    SceneSweptArgs a;
+    InstDev inst;
+};
+
 inline size_t scene_render_lds_bytes(int h, int w, int is_spherical) {
     return is_spherical ? (size_t)2 * ((size_t)h + (size_t)w) * sizeof(float) : 0;
 }
@@ -227,5 +268,10 @@ hipError_t launch_scene_render_mesh_mixed(const MeshRenderMixedArgs& a, hipStrea
 hipError_t launch_scene_distance_mesh_mixed(const MeshDistMixedArgs& a, hipStream_t s);
 hipError_t launch_scene_swept_mesh_mixed(const SceneSweptArgs& a, hipStream_t s);
 hipError_t launch_scene_sdf_rows_mesh_mixed(const SceneSdfArgs& a, hipStream_t s);  // a.mesh.hdr, a.dyn, a.mcount
+// scene_inst.hip, and scene_swept.hip's kernel over its distance function: the queries of an instanced set
+hipError_t launch_scene_render_inst(const InstRenderArgs& a, hipStream_t s);
+hipError_t launch_scene_distance_inst(const InstDistArgs& a, hipStream_t s);
+hipError_t launch_scene_swept_inst(const InstSweptArgs& a, hipStream_t s);
+hipError_t launch_scene_sdf_rows_inst(const InstSdfArgs& a, hipStream_t s);
 
 }  // namespace sdfn

@@ -22,6 +22,7 @@
 //
 // The stack is indexed at run time and lives in scratch memory: 24 entries of 24 bytes per lane, touched once per
 // interval beside an evaluation that costs hundreds of fp64 operations per primitive.
+#include "inst_dev.h"
 #include "mesh_dev.h"
 #include "scene_dev.h"
 
@@ -115,11 +116,26 @@ struct EvalMeshMixed {  // scene_distance_mesh_mixed_kernel: the movers first, t
     }
 };
 
+struct EvalInst {  // scene_distance_inst_kernel: the linear pass over the scene's instances at the point's time (inst_dev.h)
+    const MeshDev& M;
+    const InstDev& I;
+    InstRange r;
+    __device__ EvalInst(const InstSweptArgs& D, long long s) : M(D.a.mesh), I(D.inst), r(inst_range(D.inst, s)) {}
+    __device__ double operator()(double px, double py, double pz, double t) const {
+        return inst_distance(M, I, r, t, px, py, pz);
+    }
+};
+
+// the kernel's argument block is SceneSweptArgs, or a structure of its own that holds one (an instanced set)
+__host__ __device__ __forceinline__ const SceneSweptArgs& swept_base(const SceneSweptArgs& a) { return a; }
+__host__ __device__ __forceinline__ const SceneSweptArgs& swept_base(const InstSweptArgs& a) { return a.a; }
+
 __device__ __forceinline__ bool finite3(const double* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
 
 // TIMED: the set is dynamic, so the times are read and the movers' speed bound enters L
-template <class Eval, bool TIMED>
-__global__ __launch_bounds__(SCENE_BLOCK) void scene_swept_kernel(SceneSweptArgs A) {
+template <class Eval, bool TIMED, class Args>
+__global__ __launch_bounds__(SCENE_BLOCK) void scene_swept_kernel(Args AA) {
+    const SceneSweptArgs& A = swept_base(AA);
     const long long j = (long long)blockIdx.x * SCENE_BLOCK + threadIdx.x;
     if (j >= A.n) return;
     const long long s = A.p_to_scene ? (long long)min(max(A.p_to_scene[j], 0), A.sc.S - 1) : j / A.per_scene;
@@ -145,7 +161,7 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_swept_kernel(SceneSweptArgs
     }
     // rounded up by more than the norm's own rounding: L is to be a bound
     const double L = (sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) + (TIMED ? A.vmax[s] * fabs(te) : 0.0)) * (1.0 + 0x1p-50);
-    const Eval D(A, s);
+    const Eval D(AA, s);
     auto at = [&](double u) { return D(px + u * e[0], py + u * e[1], pz + u * e[2], ta + u * te); };
 
     double best = at(0.0), sbest = 0.0;
@@ -191,10 +207,11 @@ __global__ __launch_bounds__(SCENE_BLOCK) void scene_swept_kernel(SceneSweptArgs
     put(best, sbest, lbmin < best ? best - lbmin : 0.0, evals);
 }
 
-template <class Eval, bool TIMED>
-hipError_t launch_swept(const SceneSweptArgs& a, hipStream_t s) {
-    if (a.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL((scene_swept_kernel<Eval, TIMED>), dim3((unsigned)((a.n + SCENE_BLOCK - 1) / SCENE_BLOCK)),
+template <class Eval, bool TIMED, class Args>
+hipError_t launch_swept(const Args& a, hipStream_t s) {
+    const long long n = swept_base(a).n;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((scene_swept_kernel<Eval, TIMED, Args>), dim3((unsigned)((n + SCENE_BLOCK - 1) / SCENE_BLOCK)),
                        dim3(SCENE_BLOCK), 0, s, a);
     return hipGetLastError();
 }
@@ -209,5 +226,7 @@ hipError_t launch_scene_swept_mesh(const SceneSweptArgs& a, hipStream_t s) { ret
 hipError_t launch_scene_swept_mesh_mixed(const SceneSweptArgs& a, hipStream_t s) {
     return launch_swept<EvalMeshMixed, true>(a, s);
 }
+// TIMED: the times are read; the engine passes none for a set whose instances all stand still, and vmax is 0 then
+hipError_t launch_scene_swept_inst(const InstSweptArgs& a, hipStream_t s) { return launch_swept<EvalInst, true>(a, s); }
 
 }  // namespace sdfn

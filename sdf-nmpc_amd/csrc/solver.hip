@@ -634,6 +634,9 @@ extern "C" int sdfnmpc_solver_set_sdf_scene(sdfnmpc_solver* s, const sdfnmpc_sce
     if (scene->is_mesh && !scene->sdf_source)  // a mesh set is a source only when it was created as one
         return fail(SDFNMPC_E_UNSUPPORTED, "set_sdf_scene: a mesh set cannot be the SDF source (meshes are rendered and "
                                            "measured, not linearised)");
+    if (scene->is_inst && !scene->sdf_source)
+        return fail(SDFNMPC_E_UNSUPPORTED, "set_sdf_scene: an instanced set created with sdf_source = 0 cannot be the SDF "
+                                           "source");
     if (!(max_df > 0.0) || !std::isfinite(max_df))
         return fail(SDFNMPC_E_ARG, "set_sdf_scene: max_df must be positive and finite");
     ScopedDevice sd(s->device);

@@ -29,6 +29,12 @@ holds one static ``mesh.Mesh`` per scene behind a bounding-volume hierarchy (csr
 the scene is created with ``sdf_source=True`` (csrc/scene_mesh.hip: scene_sdf_rows_mesh_kernel).  Something crossing
 the vehicle's path goes beside it: ``Scene.mesh(ctx, tunnel, movers=[Scene.moving(Scene.sphere(c, 0.4), v=v)])``.
 
+A world of repeated or moving objects -- a forest of tree meshes, shelves with a forklift driving between them, a door
+that swings -- is a list of instances: ``Scene.instanced(ctx, [tree, rock], Scene.scatter(200, lo, hi, parts=2))``
+stores every part once and places it by rigid frames, ``Scene.instance(part, pos, rpy=, v=, yaw_rate=, ...)``, that may
+move as a ``Scene.moving`` primitive does (csrc/scene_inst.hip); up to 256 instances per scene, every query the
+minimum over them at its time.
+
 World frame z up; camera frame x forward, y left, z up, the pixel grid of ``ColChecker``.  There is no CPU path.
 """
 from __future__ import annotations
@@ -215,7 +221,7 @@ class Scene:
                                        motion if any(m is not None for m in motion) else None)
         self.is_dynamic = bool(_lib.load().sdfnmpc_scene_is_dynamic(self.h))
         self.is_indexed = bool(_lib.load().sdfnmpc_scene_is_indexed(self.h))
-        self.is_mesh = False
+        self.is_mesh = self.is_instanced = False
         self.is_sdf_source = bool(_lib.load().sdfnmpc_scene_is_sdf_source(self.h))  # every set that is not a mesh set
         self._set_scene_of(scene_of)
 
@@ -266,6 +272,86 @@ class Scene:
         self.is_dynamic = bool(_lib.load().sdfnmpc_scene_is_dynamic(self.h))
         self.is_indexed = bool(_lib.load().sdfnmpc_scene_is_indexed(self.h))
         self.is_mesh = bool(_lib.load().sdfnmpc_scene_is_mesh(self.h))
+        self.is_instanced = False
+        self.is_sdf_source = bool(_lib.load().sdfnmpc_scene_is_sdf_source(self.h))
+        self._set_scene_of(scene_of)
+        return self
+
+    # ---- instanced mesh scenes
+    @staticmethod
+    def instance(part, pos, *, q=None, rpy=None, v=(0.0, 0.0, 0.0), yaw_rate=0.0, amp=(0.0, 0.0, 0.0), omega=0.0,
+                 phase=0.0):
+        """One instance for ``Scene.instanced``: part ``part`` of the pool with its origin at ``pos`` and the frame of
+        ``Scene.moving`` about it -- orientation q = (w, x, y, z) or rpy (not both), yaw_rate about the world z axis,
+        velocity v, a harmonic term amp sin(omega t + phase): c(t) = pos + v t + amp sin(omega t + phase),
+        R(t) = Rz(yaw_rate t) R(q).  Rigid: there is no scale."""
+        m = Scene.moving(("sphere", [0.0, 0.0, 0.0, 1.0]), v=v, q=q, rpy=rpy, yaw_rate=yaw_rate, amp=amp, omega=omega,
+                         phase=phase)[2]
+        return ("instance", int(part), _three(pos, "pos"), m)
+
+    @staticmethod
+    def scatter(n, lo, hi, parts=1, seed=0, keep_clear=None, yaw=True):
+        """A list of n static instances in the box lo .. hi (three components each), the instances' ``forest``: the part
+        of each drawn uniformly from range(parts) (or from the sequence of indices ``parts``), its origin uniform in
+        the box, and with yaw=True a yaw uniform in [0, 2 pi).  keep_clear = (centre_xy, radius): an origin within that
+        circle is moved radially out of it, onto its rim, as ``forest`` moves an axis.  A pure function of its arguments
+        through numpy.random.default_rng(seed)."""
+        lo, hi = _three(lo, "lo"), _three(hi, "hi")
+        n = int(n)
+        pool = list(range(int(parts))) if np.ndim(parts) == 0 else [int(p) for p in parts]
+        if n < 0 or not (lo[0] <= hi[0] and lo[1] <= hi[1] and lo[2] <= hi[2]) or not pool:
+            raise ValueError("Scene.scatter: n >= 0, lo <= hi and at least one part required")
+        rng = np.random.default_rng(seed)
+        pos = rng.uniform(lo, hi, size=(n, 3))
+        which = rng.integers(0, len(pool), size=n)
+        ang = rng.uniform(0.0, 2.0 * np.pi, size=n)
+        if keep_clear is not None:
+            c, rc = np.asarray(keep_clear[0], dtype=np.float64).reshape(2), float(keep_clear[1])
+            e = pos[:, :2] - c
+            dist = np.hypot(e[:, 0], e[:, 1])
+            inside = dist < rc
+            e[dist == 0.0] = (1.0, 0.0)
+            dist = np.where(dist == 0.0, 1.0, dist)
+            pos[:, :2] = np.where(inside[:, None], c + e * (rc * (1.0 + 1e-9) / dist)[:, None], pos[:, :2])
+        return [Scene.instance(pool[which[i]], pos[i], rpy=(0.0, 0.0, ang[i] if yaw else 0.0)) for i in range(n)]
+
+    @classmethod
+    def instanced(cls, ctx: "_lib.Context", parts, instances, scene_of=None, closed=False, leaf_size=None,
+                  sdf_source=False):
+        """A scene set of instances -- ``is_instanced``: ``parts`` is the pool, one ``mesh.Mesh`` or a list of them, each
+        checked, rounded and put behind its own hierarchy as a scene of ``Scene.mesh`` is and stored once; ``instances``
+        one flat list of ``Scene.instance`` for a single scene (``Scene.scatter(...)`` as it is, [] for an empty scene),
+        or one list per scene (``scene_of`` [B] as above), at most 256 each.  closed, leaf_size and sdf_source mean what
+        they mean for ``Scene.mesh``; closed=True needs every part closed, and ``distance`` is then the minimum of the
+        instances' signed distances -- the union, instances may overlap.
+
+        Every query is the minimum over the scene's instances at its time (csrc/scene_inst.hip): ``render(t=)``,
+        ``render_from_state``, ``distance(t=)``, ``swept_distance``, ``speed_bound``, ``Rollout.clearance``, every
+        ``Nmpc.rollout(scene=)`` and, with sdf_source=True, ``Nmpc.set_sdf_scene(..., predict=)``; the results depend
+        neither on leaf_size nor on the order of the instances.  ``is_dynamic`` exactly when some instance has a
+        non-zero v, amp or yaw_rate; ``is_mesh`` and ``is_indexed`` are False.  A scene without instances renders a miss
+        everywhere and is at distance +inf.
+
+        The library refuses (SdfnmpcError) a part index outside the pool, more than 256 instances in a scene, a zero
+        quaternion, a non-finite value, and of a part what ``Scene.mesh`` refuses of a mesh."""
+        from .mesh import Mesh
+        ps = [parts] if isinstance(parts, Mesh) else list(parts)
+        instances = list(instances)
+        is_inst = lambda p: isinstance(p, tuple) and len(p) == 4 and p[0] == "instance"  # noqa: E731
+        lists = [instances] if all(is_inst(p) for p in instances) else [list(s) for s in instances]
+        for s in lists:
+            if not all(is_inst(p) for p in s):
+                raise ValueError("Scene.instanced: instances holds Scene.instance(...) entries, or one list of them per scene")
+        self = cls.__new__(cls)
+        self.ctx, self.S = ctx, len(lists)
+        self._sdf_users = weakref.WeakSet()
+        self.h = _lib.scene_create_instanced(ctx, [m.verts for m in ps], [m.tris for m in ps], [len(s) for s in lists],
+                                             [(p[1], p[2], p[3]) for s in lists for p in s],
+                                             0 if leaf_size is None else int(leaf_size), bool(closed), sdf_source)
+        self.is_dynamic = bool(_lib.load().sdfnmpc_scene_is_dynamic(self.h))
+        self.is_indexed = bool(_lib.load().sdfnmpc_scene_is_indexed(self.h))
+        self.is_mesh = bool(_lib.load().sdfnmpc_scene_is_mesh(self.h))
+        self.is_instanced = bool(_lib.load().sdfnmpc_scene_is_instanced(self.h))
         self.is_sdf_source = bool(_lib.load().sdfnmpc_scene_is_sdf_source(self.h))
         self._set_scene_of(scene_of)
         return self
@@ -377,7 +463,8 @@ class Scene:
     def speed_bound(self):
         """[S] float64: V of each scene, a bound on the speed of any surface point of any of its movers -- the maximum
         of |v| + |omega| |amp| + |yaw_rate| rho (rho: 0 for a sphere, the half diagonal of a box, sqrt(r^2 + hz^2) for
-        a cylinder), inflated by 1 + 1e-12; 0 for a scene set that is not dynamic.  The scene's distance at a fixed
+        a cylinder, the largest |vertex| of an instance's part), inflated by 1 + 1e-12; 0 for a scene set that is not
+        dynamic.  The scene's distance at a fixed
         point changes no faster than V."""
         return _lib.scene_speed_bound(self.h, self.S)
 

@@ -26,7 +26,17 @@ scene_dist_mesh_mixed and scene_sdf_rows_mesh_mixed is set against the compositi
 left alone in the same process: the *_mesh kernel on the mesh alone, the dynamic kernel on the movers alone and the
 combining pass, timed with torch -- after an assertion that both give the same bits.  The swept kernel has no
 composition: it stands beside scene_swept_mesh on the mesh alone, with the evaluations per chord.  Also printed: how often
-a mover is the nearest thing.  Writes profiles/mesh_mixed_probe.json (one file for every m it is run with)."""
+a mover is the nearest thing.  Writes profiles/mesh_mixed_probe.json (one file for every m it is run with).
+
+--instances n: what do n instances of one part cost (Scene.instanced, the four *_inst kernels), against what they
+replace?  The part is a tree of about 1 300 triangles; n of them stand in a field (Scene.scatter), and --B images, --points
+points, rows at B = 128, N = 40 and --chords chords are timed
+  * static: against the welded Scene.mesh(Mesh.merge(...)) of the same n trees -- another hierarchy over the same
+    triangles, whose fp32 vertices are rounded after the placement, so the results agree to that rounding and not to the
+    bit -- with the bytes of the triangle arrays of both beside the times;
+  * moving (every tree drifts and yaws): against n single-instance scenes, queried in one launch over n times the
+    queries, and one combining pass (torch) -- after an assertion that both give the same bits;
+and the instanced kernels again at n / 4, for the cost per instance.  Writes profiles/mesh_inst_probe.json."""
 import argparse
 import json
 import os
@@ -338,6 +348,152 @@ def movers_main(a):
     print(json.dumps(res))
 
 
+def tree():
+    """a trunk and a crown, both closed: 64 + 1280 triangles"""
+    return Mesh.merge(Mesh.cylinder((0.0, 0.0), 0.15, -1.5, 0.5, 16), Mesh.icosphere((0.0, 0.0, 1.0), 0.8, 3))
+
+
+def inst_main(a):
+    import torch
+    n, N, RB, NP, T, max_df = a.instances, 40, 128, 17, 0.7, 1.0
+    cfg = Config(mpc__N=N)
+    h, w = (int(v) for v in cfg.sensor.shape_imgs[-2:])
+    ctx = _lib.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+    ctx.enable_timing(True)
+    part = tree()
+    ntri = int(part.tris.shape[0])
+    half = 2.0 * np.sqrt(n)  # a quarter of a tree per square metre
+    lo, hi = (-half, -half, 0.0), (half, half, 0.0)
+    rng = np.random.default_rng(2)
+    cam = np.column_stack([rng.uniform(-0.5 * half, 0.5 * half, (a.B, 2)), rng.uniform(-0.5, 0.5, a.B)])
+    yaw = rng.uniform(-np.pi, np.pi, a.B)
+    R = np.stack([[[np.cos(y), -np.sin(y), 0], [np.sin(y), np.cos(y), 0], [0, 0, 1.0]] for y in yaw])
+    pts = np.column_stack([rng.uniform(-half, half, (a.points, 2)), rng.uniform(-1.5, 2.0, a.points)])
+    e = rng.normal(0, 1, (a.chords, 3))
+    p0 = pts[:a.chords]
+    p1 = p0 + e / np.linalg.norm(e, axis=1, keepdims=True) * rng.uniform(0.5, 1.5, (a.chords, 1))
+    x = rng.normal(0, 1, (RB, N + 1, 10))
+    x[..., :3] = pts[rng.integers(0, a.points, RB)][:, None, :] + 0.075 * np.arange(N + 1)[None, :, None] * np.array([1.0, 0.0, 0.0])
+    dv = lambda v, dt=np.float64: _lib.DeviceArray.from_numpy(ctx, np.ascontiguousarray(v, dtype=dt))
+    tau = dv(0.05 * np.arange(N + 1))
+    names = dict(inst=("scene_render_inst", "scene_dist_inst", "scene_sdf_rows_inst", "scene_swept_inst"),
+                 mesh=("scene_render_mesh", "scene_dist_mesh", "scene_sdf_rows_mesh", "scene_swept_mesh"))
+
+    def four(scene, kind, rep_q=1, scene_of=None):
+        """the four queries of `scene`, every array repeated rep_q times (scene k of a set of rep_q takes the k-th copy)
+        -> times (mean, max - min) and results"""
+        tile = lambda v: np.tile(v, (rep_q,) + (1,) * (np.ndim(v) - 1))
+        dP, dR, dpts, d0, d1 = dv(tile(cam)), dv(tile(R.reshape(-1, 9))), dv(tile(pts)), dv(tile(p0)), dv(tile(p1))
+        nB, npts, nch, nRB = a.B * rep_q, a.points * rep_q, a.chords * rep_q, RB * rep_q
+        so = None if scene_of is None else dv(np.repeat(np.arange(rep_q), a.B), np.int32)
+        sor = None if scene_of is None else dv(np.repeat(np.arange(rep_q), RB), np.int32)
+        times, c0, c1 = dv(np.full(npts, T)), dv(np.full(nch, T)), dv(np.full(nch, T + 0.1))
+        dx, dp = dv(tile(x)), dv(np.ones((nRB, N + 1, NP)))
+        img, dist = _lib.DeviceArray(ctx, (nB, h, w), np.float32), _lib.DeviceArray(ctx, (npts,))
+        hh, JJ = _lib.DeviceArray(ctx, (nRB, N + 1, 3)), _lib.DeviceArray(ctx, (nRB, N + 1, 10, 3))
+        sw = [_lib.DeviceArray(ctx, (nch,)) for _ in range(3)] + [_lib.DeviceArray(ctx, (nch,), np.int32)]
+        o = Scene.img_opts(cfg)
+        launch = (lambda: _lib.scene_render_at(ctx, scene.h, so, o, h, w, 1.0, nB, dP, dR, T, img),
+                  lambda: _lib.scene_distance_at(ctx, scene.h, dpts, None, times, npts, dist),
+                  lambda: _lib.scene_sdf_rows(ctx, scene.h, nRB, N, NP, dx, dp, hh, JJ, max_df, scene_of=sor, t0=T, tau=tau),
+                  lambda: _lib.scene_swept_distance(ctx, scene.h, d0, d1, None, c0, c1, nch, 1e-3, a.max_evals, *sw))
+        ms = {q: each_ms(ctx, nm, fn, a.reps) for q, nm, fn in zip(("render", "dist", "rows", "swept"), names[kind], launch)}
+        return ms, dict(img=img.numpy(), dist=dist.numpy(), h=hh.numpy()[..., 2], J=JJ.numpy()[..., 2], dmin=sw[0].numpy(),
+                        evals=sw[3].numpy())
+
+    def line(label, ms, extra=""):
+        print(f"  {label:34s}" + "  ".join(f"{q} {ms[q][0]:9.4f} ({ms[q][1]:.4f})" for q in ("render", "dist", "rows", "swept")) + extra)
+
+    res = dict(instances=n, part_triangles=ntri, B=a.B, shape=[h, w], points=a.points, rows=RB * (N + 1), chords=a.chords,
+               max_evals=a.max_evals, reps=a.reps, t=T, max_df=max_df, field_half_m=half)
+    print(f"{n} instances of a part of {ntri} triangles in a field of {2 * half:.0f} m; {a.B} images of {h} x {w}, {a.points} points, "
+          f"{RB * (N + 1)} rows, {a.chords} chords; mean (max - min) of {a.reps} launches [ms]")
+    # ---- static: instanced against welded
+    static = Scene.scatter(n, lo, hi, parts=1, seed=1, keep_clear=((0.0, 0.0), 1.0))
+    placed = []
+    for _, _, pos, m in static:
+        q0, _, _, q3 = m["q"]
+        c, s_ = q0 * q0 - q3 * q3, 2.0 * q0 * q3
+        placed.append(part.transformed(R=[[c, -s_, 0.0], [s_, c, 0.0], [0.0, 0.0, 1.0]], t=pos))
+    sc_i = Scene.instanced(ctx, part, static, sdf_source=True)
+    sc_w = Scene.mesh(ctx, Mesh.merge(*placed), sdf_source=True)
+    ms_i, r_i = four(sc_i, "inst")
+    ms_w, r_w = four(sc_w, "mesh")
+    sc_c = Scene.instanced(ctx, part, static, closed=True, sdf_source=True)
+    ms_c, _ = four(sc_c, "inst")
+    quarter = Scene.instanced(ctx, part, static[:max(n // 4, 1)], sdf_source=True)
+    ms_q, _ = four(quarter, "inst")
+    for s_ in (sc_i, sc_w, sc_c, quarter):
+        s_.close()
+    tri_b = 64 + 80  # MeshTriF + MeshTriD per triangle of an open set (a closed one adds 168)
+    bytes_w, bytes_i = n * ntri * tri_b, ntri * tri_b + n * 200
+    agree = dict(img=float(np.abs(r_i["img"] - r_w["img"]).max()), img_differ_share=float((np.abs(r_i["img"] - r_w["img"]) > 1e-4).mean()),
+                 dist=float(np.abs(r_i["dist"] - r_w["dist"]).max()), h=float(np.abs(r_i["h"] - r_w["h"]).max()),
+                 dmin=float(np.abs(r_i["dmin"] - r_w["dmin"]).max()))
+    assert agree["dist"] <= 1e-5 and agree["h"] <= 1e-5 and agree["dmin"] <= 2e-3 and agree["img_differ_share"] <= 0.05, agree
+    res["static"] = dict(instanced_ms=ms_i, welded_ms=ms_w, instanced_closed_ms=ms_c, instanced_quarter_ms=ms_q,
+                         triangle_bytes_welded=bytes_w, triangle_bytes_instanced=bytes_i, max_abs_difference=agree,
+                         hit_share=float((r_i["img"] < float(cfg.sensor.dmax)).mean()), rows_near=float((r_i["h"] < max_df).mean()),
+                         swept_evals_instanced=float(r_i["evals"].mean()), swept_evals_welded=float(r_w["evals"].mean()))
+    print(f"static, open: triangle arrays {bytes_w / 1e6:.2f} MB welded, {bytes_i / 1e6:.3f} MB instanced; largest difference "
+          f"distance {agree['dist']:.1e} m, rows {agree['h']:.1e}, swept dmin {agree['dmin']:.1e}, image {agree['img']:.1e} m "
+          f"({100 * agree['img_differ_share']:.3f} % of the pixels beyond 1e-4: silhouettes); {100 * res['static']['hit_share']:.0f} % "
+          f"of the pixels hit, {100 * res['static']['rows_near']:.0f} % of the rows within max_df")
+    line(f"instanced, {n}", ms_i, f"  ({res['static']['swept_evals_instanced']:.1f} evaluations per chord)")
+    line("welded mesh", ms_w, f"  ({res['static']['swept_evals_welded']:.1f})")
+    line(f"instanced, closed, {n}", ms_c)
+    line(f"instanced, {max(n // 4, 1)}", ms_q)
+    # ---- moving: instanced against n single-instance scenes and a combining pass
+    rngm = np.random.default_rng(3)
+    moving = [Scene.instance(0, pos, q=m["q"], v=tuple(rngm.uniform(-0.5, 0.5, 2)) + (0.0,), yaw_rate=rngm.uniform(-0.5, 0.5))
+              for _, _, pos, m in static]
+    sc_m = Scene.instanced(ctx, part, moving, sdf_source=True)
+    ms_m, r_m = four(sc_m, "inst")
+    sc_m.close()
+    singles = Scene.instanced(ctx, part, [[i] for i in moving], sdf_source=True)
+    ms_s, r_s = four(singles, "inst", rep_q=n, scene_of=True)
+    singles.close()
+    dev = torch.device("cuda:0")
+    ti = torch.rand(n, a.B, h, w, device=dev)
+    td = torch.rand(n, a.points, device=dev, dtype=torch.float64)
+    th, tJ = torch.rand(n, RB * (N + 1), device=dev, dtype=torch.float64), torch.rand(n, RB * (N + 1), 3, device=dev, dtype=torch.float64)
+
+    def rows_min():
+        k = th.argmin(0)
+        return th.gather(0, k[None])[0], tJ.gather(0, k[None, :, None].expand(1, -1, 3))[0]
+
+    comb = dict(render=torch_ms(lambda: ti.amin(0), a.reps), dist=torch_ms(lambda: td.amin(0), a.reps), rows=torch_ms(rows_min, a.reps),
+                swept=torch_ms(lambda: td[:, :a.chords].amin(0), a.reps))
+    each = r_s["h"].reshape(n, RB, N + 1)
+    k = each.argmin(0)  # the first of equal values: the lowest index keeps a tie
+    assert (np.array_equal(r_m["img"], r_s["img"].reshape(n, a.B, h, w).min(0)) and
+            np.array_equal(r_m["dist"], r_s["dist"].reshape(n, -1).min(0)) and
+            np.array_equal(r_m["h"], np.take_along_axis(each, k[None], 0)[0]) and
+            np.array_equal(r_m["J"], np.take_along_axis(r_s["J"].reshape(n, RB, N + 1, 10), k[None, ..., None], 0)[0])), \
+        "the instanced kernels and the composition of single-instance scenes differ"
+    res["moving"] = dict(instanced_ms=ms_m, singles_ms=ms_s, combine_pass_ms=comb, bitwise_equal=True,
+                         swept_evals_instanced=float(r_m["evals"].mean()))
+    print(f"moving, open: bitwise equal to the minimum over {n} single-instance scenes; one combining pass: " +
+          ", ".join(f"{q} {comb[q]:.4f}" for q in comb) + " ms")
+    line(f"instanced, {n}", ms_m, f"  ({res['moving']['swept_evals_instanced']:.1f} evaluations per chord)")
+    line(f"{n} single-instance scenes", ms_s)
+    per = {q: 1e6 * ms_i[q][0] / (n * cnt) for q, cnt in (("render", a.B * h * w), ("dist", a.points), ("rows", RB * (N + 1)))}
+    res["per_instance_ns"] = per
+    print("static, per instance and query [ns]: " + ", ".join(f"{q} {v:.3f}" for q, v in per.items()))
+    ctx.enable_timing(False)
+    path = a.out or os.path.join(ROOT, "profiles", "mesh_inst_probe.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    allres = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            allres = json.load(f)
+    allres[f"instances_{n}"] = res
+    with open(path, "w") as f:
+        json.dump(allres, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=101, help="vertices per side of the heightfield: 2 (grid - 1)^2 triangles")
@@ -350,14 +506,17 @@ def main():
     ap.add_argument("--no-brute", action="store_true", help="skip leaf_size = -1 (and the check against it)")
     ap.add_argument("--sdf", action="store_true", help="the mesh as the controller's SDF source: scene_sdf_rows_mesh")
     ap.add_argument("--movers", type=int, default=None, help="movers beside the mesh: the four *_mesh_mixed kernels")
-    ap.add_argument("--out", default=None, help="--sdf, --movers: where the JSON goes (profiles/mesh_sdf_probe.json, "
-                                                "profiles/mesh_mixed_probe.json)")
+    ap.add_argument("--instances", type=int, default=None, help="instances of one part: the four *_inst kernels (1..256)")
+    ap.add_argument("--out", default=None, help="--sdf, --movers, --instances: where the JSON goes (profiles/mesh_sdf_probe.json, "
+                                                "profiles/mesh_mixed_probe.json, profiles/mesh_inst_probe.json)")
     a = ap.parse_args()
     warnings.filterwarnings("ignore")
     if a.sdf:
         return sdf_main(a)
     if a.movers is not None:
         return movers_main(a)
+    if a.instances is not None:
+        return inst_main(a)
     import torch
     cfg = Config()
     ctx = _lib.Context(0, stream=torch.cuda.current_stream().cuda_stream)
