@@ -6,8 +6,10 @@
 // in one launch that writes the OCP's device buffers, replacing 3 (N+1) host setter calls per
 // instance.  One workgroup per instance; node k is computed by thread k (mod 64) from the shared path.
 // Arithmetic follows the numpy order of the reference with contraction off, so every value except the
-// trigonometric ones (atan2 / sin / cos: the device libm, within an ulp of glibc) is bit-exact to
-// sdf-nmpc_amd/ref_gen.py (tests/test_gpu_ref_pack.py).
+// trigonometric ones (atan2 / sin / cos: the device libm, within an ulp of glibc) is bit-exact to the
+// reference's RefGen: tests/test_gpu_ref_pack.py on its recorded outputs, and
+// tests/test_gpu_ref_pack_general.py against the numpy restatement tests/ref_gen_ref.py at general
+// horizons, batches, paths, yaw modes and layouts.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
